@@ -1,6 +1,6 @@
 """SHPL bench: fused frames/s + achieved HBM GB/s of the SHPL gather/scatter.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|3|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|3|5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -27,6 +27,20 @@ rank --frames frames of a global batch of frames*w. The only collectives are
 the barriers around the timed loop, a MAX all-reduce of the elapsed time and
 an all-gather of per-frame output checksums, compared with the N=1 run's
 (profiles/frame_checksums.json, --write-checksums).
+
+A run without --full does what the headline needs and no more: set-up, the
+warm-up steps, the --steps timed steps (value = frames / elapsed, ms_per_step
+= elapsed / steps), the outputs of the last timed step to --dump-outputs DIR
+when asked, and a short result line. --full adds everything below to the
+line (the roofline's event-timed eager steps, the checksum comparison, the
+control-plane report, the CPU baselines), each a run of its own after the
+timed loop; --no-cpu-baseline and the other switches of those parts act
+under --full only. Where the timed steps are launched eagerly (the frames
+workload, --no-graph, the split step's overlap form) --full also records the
+roofline's events inside the timed steps, as every run did before --full
+existed, and a run without it records none: the two time the same kernels,
+--full with a few event records per step on top. The default config-2 path
+and every other graph-replayed path time the same thing in both.
 
 roofline: the SHPL layer kernels (k_dense + k_sparse of every pull in the
 step); algorithmic bytes per step (SURVEY §8d per frame x F) over their
@@ -61,6 +75,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the roofline (event-timed eager steps, pool_fwd, PMC traffic lookup), "
+                         "the per-frame checksums against the stored tables, the control-plane report, the unfused "
+                         "comparison of the conv workload and the CPU baselines. Without it the run sets up, warms "
+                         "up, times --steps steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; "
+                         "an output above 2^21 / N elements per rank as a fixed seeded sample of its elements, under 64 MB "
+                         "over all outputs and ranks, see dump_outputs)")
     ap.add_argument("--frames", type=int, default=None,
                     help="frames per step: the global batch (--partition strong) or per GPU (weak)")
     ap.add_argument("--partition", default="strong", choices=["strong", "weak"],
@@ -113,8 +136,8 @@ def parse():
                     help="layer workloads: consecutive steps captured in one HIP graph (the timed loop replays it "
                          "steps / graph-steps times; --steps must divide). Default at config 3: 8 when --steps divides, "
                          "else 4 when it divides (0.107 -> 0.103 ms per step with 4: the replay boundary's ~8 us "
-                         "once per 4 steps; 8: -1 %, profiles/r05_c3gs_ab.log), else 1; elsewhere 1 (config 2: "
-                         "no change, profiles/r03_graph_steps_ab.log; configs 2 and 6 with 4: within 0.2 %, r05_c6gs_ab.log)")
+                         "once per 4 steps; 8: -1 %%, profiles/r05_c3gs_ab.log), else 1; elsewhere 1 (config 2: "
+                         "no change, profiles/r03_graph_steps_ab.log; configs 2 and 6 with 4: within 0.2 %%, r05_c6gs_ab.log)")
     ap.add_argument("--no-pool-report", action="store_true",
                     help="config 2: skip the separate pool_fwd measurement (PMC passes count the step's launches only)")
     ap.add_argument("--graph", action="store_true",
@@ -158,7 +181,43 @@ def parse():
     ap.add_argument("--maps-after", default="chain", choices=["stream", "chain"],
                     help="frames: write the BEV maps after the streaming pass (side stream) or after the CSR "
                          "(index chain)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.write_checksums and not args.full:
+        ap.error("--write-checksums needs --full (the checksums are computed there)")
+    return args
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per output, over all ranks: 8 MB as float32 (at most 6 outputs: under 64 MB in all)
+
+
+def dump_sample_index(name, n, count=DUMP_MAX_ELEMS):
+    """The sorted row-major positions (int64 [count], drawn with replacement) dump_outputs keeps of an output
+    `name` of n > count elements: torch's CPU generator seeded by sha256("<name>:<n>")."""
+    seed = int.from_bytes(hashlib.sha256(f"{name}:{n}".encode()).digest()[:7], "little")
+    return torch.randint(n, (count,), generator=torch.Generator().manual_seed(seed)).sort().values
+
+
+def dump_outputs(dirpath, named, world=1, rank=0):
+    """--dump-outputs: the tensors the last timed step left (what a caller of the timed path receives), each as
+    DIR/<name>.npy in float32 (N > 1: <name>_rank<r>.npy, every rank its own frames). A rank's share of the
+    limit is DUMP_MAX_ELEMS // N elements per output, so the files of all ranks together stay under 64 MB. An
+    output within that share is written whole, in its own shape; a larger one as a 1-D sample of that many of
+    its elements (dump_sample_index: row-major positions from a generator seeded by the output's name and
+    size), so two runs with the same arguments write the same positions. Returns what was written, for the
+    result line."""
+    os.makedirs(dirpath, exist_ok=True)
+    cap = max(DUMP_MAX_ELEMS // max(world, 1), 1)
+    info = {}
+    for name, t in named:
+        t = t.detach()
+        n = t.numel()
+        if n > cap:
+            t = t.reshape(-1)[dump_sample_index(name, n, cap).to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        fname = name + (f"_rank{rank}" if world > 1 else "") + ".npy"
+        np.save(os.path.join(dirpath, fname), a)
+        info[fname] = {"elements": n, "written": int(a.size), "sampled": n > cap}
+    return info
 
 
 def pull_bytes(rows, c_pass, c_pool, u_src, nnz, esz, write_width):
@@ -413,6 +472,20 @@ def traffic_lookup(key, field="hbm_bytes_per_launch"):
     return tj[field], f"PMC of {key}, libshpl.so {here}, commit {tj.get('commit')}", tj
 
 
+def headline(metric, frames_per_s, elapsed, args, world, dtype, data):
+    """The result line's fields every run prints (a run without --full: these, a short config and the timing):
+    the headline figure, the timed steps and their mean duration, and the library that was timed."""
+    return {"metric": metric, "value": round(frames_per_s, 2), "unit": "frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+            "higher_is_better": True, "scaling": args.partition, "vs_baseline": None, "dtype": dtype, "data": data,
+            "full": args.full, "lib_sha256": lib_sha256()}
+
+
+def plain_line(head, config, tinfo, dumped):
+    """The result line of a run without --full."""
+    return json.dumps({**head, "config": config, "timing": tinfo, **({"dumped": dumped} if dumped else {})})
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -524,10 +597,12 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    nnz = int(pl.frame_nnz.sum().item())
-    u_pix = int(torch.unique(pl.pix[pl.pix >= 0]).numel())
-    u_cell = int(torch.unique(pl.cell[pl.cell >= 0]).numel())
-    err = int(pl.err.item())
+    full = args.full
+    if full:
+        nnz = int(pl.frame_nnz.sum().item())
+        u_pix = int(torch.unique(pl.pix[pl.pix >= 0]).numel())
+        u_cell = int(torch.unique(pl.cell[pl.cell >= 0]).numel())
+        err = int(pl.err.item())
 
     # One step captured as a HIP graph (torch.cuda.graph over hipStreamBeginCapture):
     # the timed loop replays it, so host launch gaps leave the step. Kernel
@@ -552,13 +627,35 @@ def main():
             torch.cuda.synchronize()
         except Exception as e:  # noqa: BLE001 -- report and run eagerly
             graph, graph_note = None, f"graph capture failed, eager launches: {type(e).__name__}: {e}"[:200]
-    n_ev = min(args.steps, 10) if graph is not None else args.steps
+    n_ev = (min(args.steps, 10) if graph is not None else args.steps) if full else 0
     evs = [[torch.cuda.Event(enable_timing=True) for _ in range(6)] for _ in range(n_ev)]
     issue_ms = replay_step_ms = None
+    tinfo = {}
     if graph is not None:
         replays = args.steps // args.graph_steps
-        tinfo = {}
         elapsed = sd.timed(lambda k: graph.replay(), replays, device=dev, info=tinfo)
+    else:
+        elapsed = sd.timed((lambda k: step(evs[k])) if full else (lambda k: step()), args.steps, device=dev, info=tinfo)
+    # every error bit the steps set, the timed ones included (FusedPipeline.check: one read, outside the timed
+    # region): SHPL_EBIT_BARRIER or an input error ends the run here instead of reporting invalid results
+    pl.check()
+    outs = [pl.bv_fused] + ([pl.img_fused] if dual else []) + ([d_bev, d_img] if backward else [])
+    dumped = None
+    if args.dump_outputs:
+        names = ["bv_fused"] + (["img_fused"] if dual else []) + (["d_bev", "d_img"] if backward else [])
+        dumped = dump_outputs(args.dump_outputs, zip(names, outs), world, rank)
+    head = headline("SHPL fused frames/sec + achieved HBM GB/s (% of MI355X peak), 1/2/4/8 GPU",
+                    F * world * args.steps / elapsed, elapsed, args, world, "bf16" if esz == 2 else "f32",
+                    "synthetic (seeded KITTI-shaped frames; no dataset read)")
+    if not full:
+        if rank == 0:
+            print(plain_line(head, {"workload": f"config{cfg}", "global_batch": F * world,
+                                    "frames_per_gpu_per_step": F, "hip_graph": graph is not None}, tinfo, dumped),
+                  flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    if graph is not None:
         # host cost of one replay: issue the replays without waiting (after the timed loop); well
         # under the step at every config (0.03 ms at config 3), so the timed loop is not launch-bound
         torch.cuda.synchronize()
@@ -575,14 +672,8 @@ def main():
         for k in range(n_ev):
             step(evs[k])
         torch.cuda.synchronize()
-    else:
-        tinfo = {}
-        elapsed = sd.timed(lambda k: step(evs[k]), args.steps, device=dev, info=tinfo)
+        pl.check()
     args_steps_ev = n_ev
-    # every error bit the steps set, the timed ones included (FusedPipeline.check: one read, outside the timed
-    # region): SHPL_EBIT_BARRIER or an input error ends the run here instead of reporting invalid results
-    pl.check()
-    outs = [pl.bv_fused] + ([pl.img_fused] if dual else []) + ([d_bev, d_img] if backward else [])
     checks = checksum_report(f"layer_config{cfg}", sd.combine_checksums([sd.frame_checksums(t) for t in outs]), fids,
                              dev, rank, args)
     comm = sd.comm_report(dev)
@@ -628,18 +719,7 @@ def main():
                 5: "dual SHPL fwd (img->BEV and BEV->img)",
                 6: "img->BEV SHPL fwd at RetinaNet's P2 (stride 4, FPN 256 ch; not a BASELINE config)"}[cfg]
         out = {
-            "metric": "SHPL fused frames/sec + achieved HBM GB/s (% of MI355X peak), 1/2/4/8 GPU",
-            "value": round(total_frames / elapsed, 2),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": args.partition,
-            "vs_baseline": None,
-            "dtype": "bf16" if esz == 2 else "f32",
-            "data": "synthetic (seeded KITTI-shaped frames; no dataset on the box)",
+            **head,
             "config": {
                 "workload": (f"config{cfg}: {spec.n_points} pts/frame, BEV {Hb}x{Wb}x{spec.c_bev}, "
                              f"img {Hi}x{Wi}x{spec.c_img}, {what}; step = device index build + sorted M "
@@ -703,7 +783,7 @@ def main():
             "timing": tinfo,
             "frame_checksums": checks,
             "comm": comm,
-            "lib_sha256": lib_sha256(),
+            **({"dumped": dumped} if dumped else {}),
         }
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -781,14 +861,27 @@ def run_frames(args, world, rank, dev):
     for _ in range(args.warmup):
         velo_step()
     torch.cuda.synchronize()
-    nnz = int(pl.frame_nnz.sum().item())
-    u_pix = int(torch.unique(pl.pix[pl.pix >= 0]).numel())
-    n_cam = int(pl.velo.counts.sum().item())
-    n_vox = int(pl.bev.frame_nvox.sum().item())
-    errs = int(pl.err.item()) | int(pl.bev.err.item()) | int(pl.velo.err.item())
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(9)] for _ in range(args.steps)]
+    full = args.full
+    if full:
+        nnz = int(pl.frame_nnz.sum().item())
+        u_pix = int(torch.unique(pl.pix[pl.pix >= 0]).numel())
+        n_cam = int(pl.velo.counts.sum().item())
+        n_vox = int(pl.bev.frame_nvox.sum().item())
+        errs = int(pl.err.item()) | int(pl.bev.err.item()) | int(pl.velo.err.item())
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(9)] for _ in range(args.steps if full else 0)]
     tinfo = {}
-    elapsed = sd.timed(lambda k: velo_step(evs[k]), args.steps, device=dev, info=tinfo)
+    elapsed = sd.timed((lambda k: velo_step(evs[k])) if full else (lambda k: velo_step()), args.steps, device=dev,
+                       info=tinfo)
+    dumped = dump_outputs(args.dump_outputs, [("bv_fused", pl.bv_fused)], world, rank) if args.dump_outputs else None
+    head = headline("SHPL frames/sec from raw velodyne scans (loader + BEV slices + index + fused layer)",
+                    F * world * args.steps / elapsed, elapsed, args, world, "f32",
+                    "synthetic (seeded 64-beam-like velodyne scans, KITTI calib; no dataset read)")
+    if not full:
+        if rank == 0:
+            print(plain_line(head, {"workload": f"frames: {args.scan_points} pts/scan", "maps_form": args.maps_form,
+                                    "global_batch": F * world, "frames_per_gpu_per_step": F}, tinfo, dumped),
+                  flush=True)
+        return
     mean = lambda i, j: sum(e[i].elapsed_time(e[j]) for e in evs) / args.steps  # noqa: E731
     dense_ms, sparse_ms = mean(0, 1), mean(7, 8)
     stages = {"velo_to_cam_ms": mean(2, 3), "bev_slices_ms": mean(3, 4), "index_ms": mean(4, 5),
@@ -819,11 +912,7 @@ def run_frames(args, world, rank, dev):
         cpu = cpu_baseline_frames(scans, calib, fr.planes[0].cpu().numpy(), im_size, C, args.cpu_seconds)
     if rank == 0:
         out = {
-            "metric": "SHPL frames/sec from raw velodyne scans (loader + BEV slices + index + fused layer)",
-            "value": round(F * world * args.steps / elapsed, 2), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True, "scaling": args.partition, "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic (seeded 64-beam-like velodyne scans, KITTI calib; no dataset on the box)",
+            **head,
             "config": {"workload": (f"frames: {args.scan_points} pts/scan -> {n_cam / F:.0f} FOV pts -> "
                                     f"{n_vox / F:.0f} BEV voxel pts -> {nnz / F:.0f} M entries; BEV "
                                     f"{pl.Hb}x{pl.Wb}x{C} (5 slices + density maps"
@@ -845,7 +934,7 @@ def run_frames(args, world, rank, dev):
             "index_errors": errs,
             "timing": tinfo,
             "comm": comm,
-            "lib_sha256": lib_sha256(),
+            **({"dumped": dumped} if dumped else {}),
         }
         print(json.dumps(out), flush=True)
 
@@ -962,7 +1051,9 @@ def run_conv_train(args, world, rank, dev, spec, fids, dtype, pl, pts, vox, off,
     tb, ti = bev.clone().requires_grad_(True), img.clone().requires_grad_(True)
     gy = sd.fill_features(torch.empty((F, Hb, Wb, ci), dtype=dtype, device=dev), fids, 7)
 
-    def step(ev=None):
+    last = {}
+
+    def step(ev=None, keep=False):
         pl.build_index(pts, vox, off, P)
         smap = pl.map()
         for t in (tb, ti, conv.weights, conv.beta):
@@ -975,12 +1066,29 @@ def run_conv_train(args, world, rank, dev, spec, fids, dtype, pl, pts, vox, off,
         y.backward(gy)
         if ev is not None:
             ev[2].record()
+        if keep:
+            last["y"] = y
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     tinfo = {}
-    elapsed = sd.timed(lambda k: step(), args.steps, device=dev, info=tinfo)
+    keep_at = args.steps - 1 if args.dump_outputs else -1  # --dump-outputs: the last timed step's result is kept
+    elapsed = sd.timed(lambda k: step(keep=k == keep_at), args.steps, device=dev, info=tinfo)
+    dname = "bf16" if esz == 2 else "f32"
+    dumped = None
+    if args.dump_outputs:  # the step's result and the four gradients its backward leaves
+        dumped = dump_outputs(args.dump_outputs, [("y", last["y"]), ("d_bev", tb.grad), ("d_img", ti.grad),
+                                                  ("d_weights", conv.weights.grad), ("d_beta", conv.beta.grad)],
+                              world, rank)
+    head = headline("SHPL + post-fusion conv training frames/sec (fwd + bwd), 1/2/4/8 GPU",
+                    F * world * args.steps / elapsed, elapsed, args, world, dname,
+                    "synthetic (seeded KITTI-shaped frames, xavier-initialised conv weights)")
+    if not args.full:
+        if rank == 0:
+            print(plain_line(head, {"workload": "conv training: config2", "global_batch": F * world,
+                                    "frames_per_gpu_per_step": F, "hip_graph": False}, tinfo, dumped), flush=True)
+        return
     n_ev = min(args.steps, 5)
     evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(n_ev)]
     for k in range(n_ev):
@@ -1028,11 +1136,7 @@ def run_conv_train(args, world, rank, dev, spec, fids, dtype, pl, pts, vox, off,
         cpu = cpu_baseline_train(spec, [synth.make_frame(spec, seed=fids[0], n_outside=200)], args.cpu_seconds)
     if rank == 0:
         print(json.dumps({
-            "metric": "SHPL + post-fusion conv training frames/sec (fwd + bwd), 1/2/4/8 GPU",
-            "value": round(F * world * args.steps / elapsed, 2), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True, "scaling": args.partition, "vs_baseline": None, "dtype": dname,
-            "data": "synthetic (seeded KITTI-shaped frames, xavier-initialised conv weights)",
+            **head,
             "config": {"workload": (f"conv training: config2 -> index -> conv3x3 {cb + ci}->{ci} + BatchNorm (batch "
                                     "statistics) + ReLU of [bev || pool(img)] (bf16: pooling inside the forward conv and "
                                     "the weight gradient, bv_fused never stored; f32: the pooled map built once in the "
@@ -1059,7 +1163,7 @@ def run_conv_train(args, world, rank, dev, spec, fids, dtype, pl, pts, vox, off,
             "cpu_baseline": cpu,
             "timing": tinfo,
             "comm": comm,
-            "lib_sha256": lib_sha256(),
+            **({"dumped": dumped} if dumped else {}),
         }), flush=True)
 
 
@@ -1127,7 +1231,8 @@ def run_conv(args, world, rank, dev):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    err = int(pl.err.item())
+    full = args.full
+    err = int(pl.err.item()) if full else None
     graph = None
     if not args.no_graph and not train:
         gstream = torch.cuda.Stream(device=dev)
@@ -1145,6 +1250,17 @@ def run_conv(args, world, rank, dev):
     else:
         tinfo = {}
         elapsed = sd.timed(lambda k: step(), args.steps, device=dev, info=tinfo)
+    dname = "bf16" if dtype == torch.bfloat16 else "f32"
+    dumped = dump_outputs(args.dump_outputs, [("out", out)], world, rank) if args.dump_outputs else None
+    head = headline("SHPL + post-fusion conv frames/sec (MFMA roofline), 1/2/4/8 GPU",
+                    F * world * args.steps / elapsed, elapsed, args, world, dname,
+                    "synthetic (seeded KITTI-shaped frames, xavier-initialised conv weights; no dataset read)")
+    if not full:
+        if rank == 0:
+            print(plain_line(head, {"workload": f"conv: config{args.config}", "global_batch": F * world,
+                                    "frames_per_gpu_per_step": F, "hip_graph": graph is not None}, tinfo, dumped),
+                  flush=True)
+        return
     for k in range(n_ev):
         step(evs[k])
     uev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(n_ev)]
@@ -1172,11 +1288,7 @@ def run_conv(args, world, rank, dev):
     if rank == 0:
         dname = "bf16" if esz == 2 else "f32"
         out_j = {
-            "metric": "SHPL + post-fusion conv frames/sec (MFMA roofline), 1/2/4/8 GPU",
-            "value": round(F * world * args.steps / elapsed, 2), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True, "scaling": args.partition, "vs_baseline": None, "dtype": dname,
-            "data": "synthetic (seeded KITTI-shaped frames, xavier-initialised conv weights; no dataset on the box)",
+            **head,
             "config": {"workload": (f"conv: config{args.config} ({spec.n_points} pts/frame, BEV {Hb}x{Wb}x{cb}, img "
                                     f"{Hi}x{Wi}x{ci}) -> index -> cell CSR -> conv3x3 {cb + ci}->{c_out} + "
                                     + ("bias + ReLU of [bev || pool(img)] (retinanet_model.py:334-348)" if retina else
@@ -1212,7 +1324,7 @@ def run_conv(args, world, rank, dev):
             "index_errors": err,
             "timing": tinfo,
             "comm": comm,
-            "lib_sha256": lib_sha256(),
+            **({"dumped": dumped} if dumped else {}),
         }
         print(json.dumps(out_j), flush=True)
 

@@ -4,6 +4,7 @@
 #   bash scripts/ab_kernels.sh TAG "BENCH ARGS" PATTERN NAME=LIB ...
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 tag=$1; bargs=$2; pat=$3; shift 3
+bargs="--full $bargs"  # the roofline frac and the checksum match printed below are in the --full result line
 out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 for nl in "$@"; do

@@ -9,7 +9,10 @@ export TMPDIR=/tmp
 DT="${DT:-f32}"
 CFG="${CFG:-2}"  # 6: RetinaNet's 512 -> 256 conv (k_conv_wide for bf16); tags conv_c6_<dt>
 T=$DT; [ "$CFG" = 6 ] && T=c6_$DT
-B="bench.py --workload conv --config $CFG --dtype $DT --steps 3 --warmup 1 --no-cpu-baseline --no-graph"
+# The counter passes run bench.py --full (their per-kernel averages keep the unfused comparison's launches, as
+# profiles/traffic.json's conv entries were measured); the kernel trace below is of the lean run on purpose: its
+# per-kernel stats then describe the timed fused step's launches alone.
+B="bench.py --full --workload conv --config $CFG --dtype $DT --steps 3 --warmup 1 --no-cpu-baseline --no-graph"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_conv_$T -o run --output-format csv -- \
   python3 bench.py --workload conv --config $CFG --dtype $DT --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/prof_conv_$T.log 2>&1
 rc=$?; echo "trace rc=$rc"; [ $rc -eq 0 ] || exit $rc

@@ -7,6 +7,8 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 ok() { local rc=$1; [ "$rc" -eq 0 ] || [ "$rc" -eq 1 ]; }
 STEPS="${STEPS:-tests smoke bench prof}"
+# the bench, prof and pmc steps use the whole result line (roofline, checksums, CPU baselines) and every launch behind it
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for s in $STEPS; do
   case $s in
     tests)

@@ -3,7 +3,7 @@
 Test infrastructure (imports the CPU oracle): used by tests/test_checksum_tables.py (CPU, a sample of every
 table's frames) and tests/golden/make_checksum_tables.py (all frames: the generator of the file).
 
-bench.py reports ``frame_checksums.match_n1`` by comparing each frame's output checksum with these tables.
+bench.py --full reports ``frame_checksums.match_n1`` by comparing each frame's output checksum with these tables.
 Each entry is computed here, on the host, from the inputs the bench draws for that global frame id --
 ``synth.make_frame(spec, seed=frame id, n_outside=200)`` and ``dist.fill_features`` (integer-hash features
 whose host mirror is ``dist.feature_values_np``) -- run through the C oracle (oracle/shpl_oracle.c: the

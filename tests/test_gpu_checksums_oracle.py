@@ -22,7 +22,7 @@ def _bench(args, timeout=300):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-                        "--no-cpu-baseline", *args], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", *args], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=timeout)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
