@@ -308,11 +308,13 @@ def test_bf16_rows_empty_map_stats_and_wgrad():
     assert not dw_f[:, :, 32:].any()
 
 
-def test_batch_norm_training_vs_oracle():
+@pytest.mark.parametrize("Cout", [40, 32])
+def test_batch_norm_training_vs_oracle(Cout):
     """is_training: conv statistics -> batch moments -> normalise + ReLU in
-    place, moving averages with the Bessel-corrected variance."""
+    place, moving averages with the Bessel-corrected variance. Cout = 40: the
+    scalar BatchNorm kernel (40 / 4 = 10 is no power of two); 32: the vector one."""
     from sparse_pooling_amd import fusion_conv as fc
-    B, H, W, Cin, Cout = 2, 19, 37, 24, 40
+    B, H, W, Cin = 2, 19, 37, 24
     x = synth.make_features((B, H, W, Cin), 9) + 0.5
     w = _weights(Cin, Cout, 10)
     conv = fc.FusionConv(Cin, Cout, device=DEV)

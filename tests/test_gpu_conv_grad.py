@@ -220,9 +220,11 @@ def test_wgrad_two_sources_and_pooled():
     _check(pooled, ref, bound, "pooled")
 
 
-@pytest.mark.parametrize("training,C", [(True, 40), (False, 40), (True, 7), (False, 7)])
+@pytest.mark.parametrize("training,C", [(True, 40), (False, 40), (True, 7), (False, 7), (True, 32), (False, 32),
+                                        (True, 64), (False, 64)])
 def test_batch_norm_backward(training, C):
-    """C = 40: the 16-byte vector kernels; C = 7: the scalar ones."""
+    """C = 32, 64: the 16-byte vector kernels (C / 4 = 8, 16, a power of two); C = 40 (C / 4 = 10 is none)
+    and C = 7 (no multiple of 4): the scalar ones. Every dispatch form: tests/test_gpu_batch_norm.py."""
     from sparse_pooling_amd import fusion_conv as fc
     rng = np.random.default_rng(7)
     raw = (rng.standard_normal((3, 11, 13, C)) * 2.0 + 0.5).astype(np.float32)
@@ -236,12 +238,15 @@ def test_batch_norm_backward(training, C):
         var = rng.uniform(0.5, 2.0, C)
     scale = (1.0 / np.sqrt(var + 1e-3)).astype(np.float32)
     y = np.maximum((raw - mean) * scale + beta, 0.0).astype(np.float32)
-    gr, db, _ = fc.batch_norm_backward(_t(g), y=_t(y), raw=_t(raw), mean=_t(mean.astype(np.float32)),
-                                       scale=_t(scale), relu=True, training=training)
-    e_raw, e_db, _ = orc.batch_norm_backward(raw.astype(np.float64), g, training, mean, var, 1e-3, None, beta, True)
+    gr, db, dg = fc.batch_norm_backward(_t(g), y=_t(y), raw=_t(raw), mean=_t(mean.astype(np.float32)),
+                                        scale=_t(scale), relu=True, training=training)
+    e_raw, e_db, e_dg = orc.batch_norm_backward(raw.astype(np.float64), g, training, mean, var, 1e-3, None, beta,
+                                                True)
     # values of order |scale * g|; the training form subtracts two O(1) means in f32
     _check(gr, e_raw, 1e-5 + 1e-5 * np.abs(scale) * (np.abs(g) + 1.0), "g_raw")
     _check(db, e_db, 1e-4 + 1e-6 * np.abs(g).reshape(-1, C).sum(0), "dbeta")
+    xhat = (raw.astype(np.float64) - mean) / np.sqrt(var + 1e-3)
+    _check(dg, e_dg, 1e-4 + 1e-6 * np.abs(g * xhat).reshape(-1, C).sum(0), "dgamma")
     # the ReLU mask recomputed from raw (y not read) with the forward's rounding, (raw - mean) * scale + beta
     # one rounded op at a time (as torch's separate kernels do): bitwise the same result as reading y
     t_raw, t_mean, t_scale, t_beta = _t(raw), _t(mean.astype(np.float32)), _t(scale), _t(beta)

@@ -73,3 +73,81 @@ def test_oracle_conv_and_bn_backward_match_torch_autograd():
     np.testing.assert_allclose(dr, t.grad.permute(0, 2, 3, 1).numpy(), rtol=1e-10, atol=1e-12)
     np.testing.assert_allclose(db, tb.grad.numpy(), rtol=1e-10, atol=1e-12)
     np.testing.assert_allclose(dg, tg.grad.numpy(), rtol=1e-10, atol=1e-12)
+
+
+def _signed_gamma(rng, C):
+    """gamma away from ones: both signs, |gamma| in [0.25, 2]."""
+    g = rng.uniform(0.25, 2.0, C) * np.where(np.arange(C) % 2 == 0, 1.0, -1.0)
+    return g.astype(np.float32)
+
+
+def _torch_bn_backward(raw, g, gamma, beta, relu, training, mean=None, var=None):
+    """(d_raw, dbeta, dgamma) of relu?(F.batch_norm(raw)) by torch's CPU autograd in float64."""
+    C = raw.shape[-1]
+    t = torch.from_numpy(raw).reshape(-1, C).clone().requires_grad_()
+    tg = (torch.ones(C, dtype=torch.float64) if gamma is None else torch.from_numpy(gamma).double()).requires_grad_()
+    tb = (torch.zeros(C, dtype=torch.float64) if beta is None else torch.from_numpy(beta).double()).requires_grad_()
+    rm = None if training else torch.from_numpy(np.asarray(mean, np.float64).copy())
+    rv = None if training else torch.from_numpy(np.asarray(var, np.float64).copy())
+    y = torch.nn.functional.batch_norm(t, rm, rv, tg, tb, training=training, eps=1e-3)
+    if relu:
+        y = torch.relu(y)
+    y.backward(torch.from_numpy(g).double().reshape(-1, C))
+    return t.grad.reshape(raw.shape).numpy(), tb.grad.numpy(), tg.grad.numpy()
+
+
+@pytest.mark.parametrize("relu", [True, False])
+def test_oracle_bn_backward_training_gamma_matches_torch(relu):
+    rng = np.random.default_rng(11)
+    C = 6
+    raw = rng.standard_normal((3, 5, 7, C)) * 2 + 1
+    g = rng.standard_normal(raw.shape).astype(np.float32)
+    gamma = _signed_gamma(rng, C)
+    assert (gamma > 0).any() and (gamma < 0).any() and (np.abs(gamma) >= 0.25).all()
+    beta = rng.standard_normal(C).astype(np.float32)
+    dr, db, dg = orc.batch_norm_backward(raw, g, True, eps=1e-3, gamma=gamma, beta=beta, relu=relu)
+    tr, tb, tg = _torch_bn_backward(raw, g, gamma, beta, relu, True)
+    np.testing.assert_allclose(dr, tr, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(db, tb, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(dg, tg, rtol=1e-10, atol=1e-12)
+
+
+@pytest.mark.parametrize("relu", [True, False])
+@pytest.mark.parametrize("with_gamma", [True, False])
+def test_oracle_bn_backward_inference_matches_torch(with_gamma, relu):
+    """training=False: the moving statistics are constants of the graph."""
+    rng = np.random.default_rng(12)
+    C = 5
+    raw = rng.standard_normal((2, 7, 3, C)) * 2 + 1
+    g = rng.standard_normal(raw.shape).astype(np.float32)
+    gamma = _signed_gamma(rng, C) if with_gamma else None
+    beta = rng.standard_normal(C).astype(np.float32)
+    mean = rng.standard_normal(C)
+    var = rng.uniform(0.5, 2.0, C)
+    dr, db, dg = orc.batch_norm_backward(raw, g, False, mean, var, 1e-3, gamma, beta, relu)
+    tr, tb, tg = _torch_bn_backward(raw, g, gamma, beta, relu, False, mean, var)
+    np.testing.assert_allclose(dr, tr, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(db, tb, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(dg, tg, rtol=1e-10, atol=1e-12)
+
+
+@pytest.mark.parametrize("relu", [True, False])
+def test_oracle_batch_norm_training_gamma_matches_torch(relu):
+    rng = np.random.default_rng(13)
+    C = 6
+    raw = rng.standard_normal((3, 7, 5, C)) * 2.0 + 1.0
+    gamma = _signed_gamma(rng, C)
+    beta = rng.standard_normal(C).astype(np.float32)
+    mm = rng.standard_normal(C).astype(np.float32)
+    mv = rng.uniform(0.5, 2, C).astype(np.float32)
+    y, bm, bv, emm, emv = orc.batch_norm_train(raw, 1e-3, gamma, beta, relu, mm, mv, 0.999)
+    rm, rv = torch.from_numpy(mm.astype(np.float64)), torch.from_numpy(mv.astype(np.float64))
+    t = torch.nn.functional.batch_norm(torch.from_numpy(raw).reshape(-1, C), rm, rv,
+                                       torch.from_numpy(gamma).double(), torch.from_numpy(beta).double(),
+                                       training=True, momentum=0.001, eps=1e-3)
+    t = (torch.relu(t) if relu else t).reshape(raw.shape).numpy()
+    np.testing.assert_allclose(y, t.astype(np.float32), rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(bm, raw.reshape(-1, C).mean(0), rtol=1e-12)
+    np.testing.assert_allclose(bv, raw.reshape(-1, C).var(0, ddof=1), rtol=1e-12)
+    np.testing.assert_allclose(emm, rm.numpy().astype(np.float32), rtol=1e-6, atol=1e-7)
+    np.testing.assert_allclose(emv, rv.numpy().astype(np.float32), rtol=1e-6, atol=1e-7)
