@@ -31,9 +31,7 @@
 // arithmetic of k_sparse (shpl_pull.hip: TF order, separate multiply and
 // add), so the conv of the fused form is bitwise the conv of
 // [bev || shpl_pull(...)] and bv_fused never reaches HBM.
-#include <type_traits>
-
-#include "shpl_common.h"
+#include "shpl_conv_bn.h"
 #include "shpl_conv_rows.h"
 #include "shpl_conv_wide.h"
 
@@ -43,37 +41,12 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 8, TW = 32;              // output tile (rows x columns)
 constexpr int HH = TH + 2, HWD = TW + 2;    // halo tile
 constexpr int NCO = 32;                     // output channels per workgroup
 constexpr int CONV_BLOCK = 256;             // 4 waves, wave w: tile rows 2w, 2w+1
 constexpr int W_ROWS = 9 * NCO;             // weight rows of a chunk (tap, out channel)
-
-// One chunk = the input channels staged per LDS round, 32 B per pixel: 8
-// f32 channels (4 f32 MFMAs of K=2 per tap) or 16 bf16 channels (one bf16
-// MFMA of K=16 per tap). 64 B bf16 chunks measured slower (fewer workgroups
-// per CU).
-template <typename T>
-struct Elem {
-    static constexpr int CB = 32;                        // chunk bytes per pixel
-    static constexpr int CK = CB / sizeof(T);            // channels per chunk
-    static constexpr int HE = 16 / sizeof(T);            // channels per 16-byte piece
-    static constexpr int NP = CB / 16;                   // pieces per pixel
-    static __device__ __forceinline__ float f(T v) {
-        if constexpr (sizeof(T) == 4)
-            return v;
-        else
-            return bf16_to_f32(v);
-    }
-    static __device__ __forceinline__ T back(float v) {
-        if constexpr (sizeof(T) == 4)
-            return v;
-        else
-            return f32_to_bf16(v);
-    }
-};
 
 // ReLU of a stored value as max(bits, 0) on its bit pattern as a signed integer of its width: negatives,
 // -0 and -NaN become +0, +NaN stays -- k_conv_rows' packed 16-bit max, so both kernels give the same bits.
@@ -753,37 +726,7 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_row_ptr(const int32_t *dst, cons
 
 // Per-channel sum / sum of squares of the pre-activation output, summed over
 // the per-tile partials in a fixed order (deterministic): one block per
-// (channel, statistic).
-// Deterministic sums of long strided lists (the per-tile / per-block /
-// per-group partials): thread t adds elements t, t + n_thr, ... into 8
-// independent accumulators (8 loads in flight, then a fixed pairwise
-// combine), the wave and the block then reduce in a fixed order. A thread per
-// list walking it serially (550-4096 dependent loads) cost 0.2-0.3 ms per
-// reduction.
-template <int NT>
-__device__ __forceinline__ double strided_sum(const double *v, int64_t n, int64_t step, int t) {
-    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    int64_t i = t;
-    for (; i + 7 * NT < n; i += 8 * NT) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] += v[(i + u * NT) * step];
-    }
-    for (int u = 0; i < n; i += NT, ++u) acc[u & 7] += v[i * step];
-    return ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-}
-
-// Block sum of one double per thread (fixed order); valid in thread 0.
-template <int NT>
-__device__ __forceinline__ double block_sum(double s, double *red) {
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < NT / 64; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
-
+// (channel, statistic; strided_sum / block_sum of shpl_conv_bn.h).
 constexpr int RED_BLOCK = 1024;
 __global__ __launch_bounds__(RED_BLOCK) void k_stats_reduce(const double *part, int n_tiles, int c_out,
                                                             double *stats) {
@@ -792,371 +735,6 @@ __global__ __launch_bounds__(RED_BLOCK) void k_stats_reduce(const double *part, 
     const double s = block_sum<RED_BLOCK>(
         strided_sum<RED_BLOCK>(part + ((int64_t)ch * 2 + st) * n_tiles, n_tiles, 1, threadIdx.x), red);
     if (threadIdx.x == 0 && ch < c_out) stats[st * c_out + ch] = s;
-}
-
-// BatchNorm (training) from the batch statistics: mean, biased variance for
-// the normalisation, Bessel-corrected variance for the moving average (TF
-// FusedBatchNorm), then y = act((x - mean) * gamma / sqrt(var + eps) + beta)
-// in place.
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_finalize(const double *stats, double count, int c, float eps,
-                                                            const float *gamma, float *mean_out, float *scale_out,
-                                                            float *moving_mean, float *moving_var, float decay,
-                                                            float *batch_mean, float *batch_var) {
-    for (int ch = threadIdx.x; ch < c; ch += SHPL_BLOCK) {
-        const double mean = stats[ch] / count;
-        double var = stats[c + ch] / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)mean, vf = (float)var;
-        const float g = gamma ? gamma[ch] : 1.0f;
-        mean_out[ch] = mf;
-        scale_out[ch] = __fmul_rn(g, __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(vf, eps))));
-        const float vu = count > 1.0 ? (float)(var * count / (count - 1.0)) : vf;
-        if (moving_mean) moving_mean[ch] = __fsub_rn(moving_mean[ch], __fmul_rn(__fsub_rn(moving_mean[ch], mf), 1.0f - decay));
-        if (moving_var) moving_var[ch] = __fsub_rn(moving_var[ch], __fmul_rn(__fsub_rn(moving_var[ch], vu), 1.0f - decay));
-        if (batch_mean) batch_mean[ch] = mf;
-        if (batch_var) batch_var[ch] = vu;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_apply(const T *x, T *y, int64_t rows, int64_t stride, int c,
-                                                         const float *mean, const float *scale, const float *beta,
-                                                         int act) {
-    const int64_t total = rows * c;
-    for (int64_t t = (int64_t)blockIdx.x * SHPL_BLOCK + threadIdx.x; t < total;
-         t += (int64_t)gridDim.x * SHPL_BLOCK) {
-        const int64_t r = t / c;
-        const int ch = (int)(t - r * c);
-        float v = __fmul_rn(__fsub_rn(Elem<T>::f(x[r * stride + ch]), mean[ch]), scale[ch]);
-        if (beta) v = __fadd_rn(v, beta[ch]);
-        if (act == 1) v = v > 0.0f ? v : 0.0f;
-        y[r * stride + ch] = Elem<T>::back(v);
-    }
-}
-
-// 16-byte pieces of a row (VEC channels): the vector forms of the BatchNorm
-// streams, used when rows and channel counts are multiples of VEC and aligned.
-// Rows per thread of the BatchNorm apply kernels' grid-stride loops: enough
-// to amortise the per-thread channel parameters (six loads and a division
-// per channel in the backward), few enough to keep loads in flight. Measured
-// at 64 frames: f32 17 -> 4 rows took apply 1.78 -> 1.61 ms and backward
-// apply 2.68 -> 2.35 ms; bf16 at 2 rows per thread was 1.7x slower than at 8.
-constexpr int64_t bn_rows_per_thread(int esz) { return esz == 4 ? 4 : 8; }
-
-// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...) for run-time switches b0, b1, ...: the
-// instance of a vector BatchNorm kernel for one combination of its compile-time forms.
-template <bool... Bs, typename F>
-void bn_forms(F &&f) {
-    f(std::bool_constant<Bs>{}...);
-}
-template <bool... Bs, typename F, typename... R>
-void bn_forms(F &&f, bool b, R... rest) {
-    if (b)
-        bn_forms<Bs..., true>(f, rest...);
-    else
-        bn_forms<Bs..., false>(f, rest...);
-}
-
-// 16-byte pieces of the BatchNorm streams, nontemporal (each byte is touched
-// once per pass; the maps are far larger than the caches).
-template <typename T, int VEC>
-struct Piece {
-    static __device__ __forceinline__ void load(const T *p, float (&x)[VEC]) {
-        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-        T e[VEC];
-        __builtin_memcpy(e, &r, 16);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) x[k] = Elem<T>::f(e[k]);
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&x)[VEC]) {
-        T e[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) e[k] = Elem<T>::back(x[k]);
-        u32x4 r;
-        __builtin_memcpy(&r, e, 16);
-        __builtin_nontemporal_store(r, reinterpret_cast<u32x4 *>(p));
-    }
-};
-
-constexpr int BN_U = 4;  // rows per iteration of the vector apply kernels: their loads in flight together
-
-// Thread layout of the vector forms: c / VEC piece lanes (a power of two
-// dividing the block) times SHPL_BLOCK / (c / VEC) row lanes, so each thread
-// keeps one channel group and its per-channel coefficients in registers.
-// The vector apply kernels take their switches (ReLU, beta, y, training) as
-// template arguments: as run-time flags they put a branch around every element
-// of the unrolled loops (bn_forms picks the instance; bf16 at 64 frames: the
-// backward apply 1,199 -> 1,147 us, the forward apply 777 -> 750 us,
-// profiles/r04_bn_ab.log).
-template <typename T, bool BETA, bool ACT>
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_apply_vec(const T *x, T *y, int64_t rows, int64_t stride, int c,
-                                                             const float *mean, const float *scale,
-                                                             const float *beta) {
-    constexpr int VEC = 16 / sizeof(T);
-    const int pr = c / VEC, rpb = SHPL_BLOCK / pr;
-    const int ch0 = (threadIdx.x % pr) * VEC;
-    float m[VEC], sc[VEC], b[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        m[k] = mean[ch0 + k];
-        sc[k] = scale[ch0 + k];
-        b[k] = BETA ? beta[ch0 + k] : 0.0f;
-    }
-    const int64_t step = (int64_t)gridDim.x * rpb;
-    for (int64_t r0 = (int64_t)blockIdx.x * rpb + threadIdx.x / pr; r0 < rows; r0 += BN_U * step) {
-        float v[BN_U][VEC];
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u)
-            if (r0 + u * step < rows) Piece<T, VEC>::load(x + (r0 + u * step) * stride + ch0, v[u]);
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) {
-            if (r0 + u * step >= rows) break;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                float t = __fmul_rn(__fsub_rn(v[u][k], m[k]), sc[k]);
-                if constexpr (BETA) t = __fadd_rn(t, b[k]);
-                v[u][k] = (ACT && !(t > 0.0f)) ? 0.0f : t;
-            }
-            Piece<T, VEC>::store(y + (r0 + u * step) * stride + ch0, v[u]);
-        }
-    }
-}
-
-// ---------------------------------------------------------------- backward
-// BatchNorm (+ ReLU) backward. g_bn = g * [y > 0] (act), xhat = (raw - mean)
-// * scale / gamma; per-channel sums dbeta = sum g_bn, dgamma = sum g_bn xhat
-// over rows in a fixed order (f64 partials per block, then per channel), and
-//   training:  g_raw = scale * (g_bn - dbeta / N - xhat * dgamma / N)
-//   inference: g_raw = scale * g_bn     (moving statistics are constants)
-// mean / scale NULL: 0 / 1 (a conv bias instead of BN: g_raw = g_bn).
-// The ReLU mask [y > 0] is read from y, or (y NULL) recomputed from the BN
-// input with the forward's rounded operations, u = (raw - mean) * scale
-// (+ beta), so that it is bitwise the forward's: [u > 0] == [y > 0].
-__device__ __forceinline__ float bn_pre_act(float x, float m, float sc, const float *beta, int ch) {
-    const float u = __fmul_rn(__fsub_rn(x, m), sc);
-    return beta ? __fadd_rn(u, beta[ch]) : u;
-}
-
-template <typename T>
-__device__ __forceinline__ float bn_gbn(const T *y, const T *raw, const T *gy, int64_t o, int ch, int act,
-                                        const float *mean, const float *scale, const float *beta) {
-    const float gv = Elem<T>::f(gy[o]);
-    if (act != 1) return gv;
-    const float yv = y ? Elem<T>::f(y[o])
-                       : bn_pre_act(Elem<T>::f(raw[o]), mean ? mean[ch] : 0.0f, scale ? scale[ch] : 1.0f, beta, ch);
-    return yv > 0.0f ? gv : 0.0f;
-}
-
-template <typename T>
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_bwd_partial(const T *y, const T *raw, const T *gy, int64_t rows,
-                                                               int64_t stride, int c, const float *mean,
-                                                               const float *scale, const float *gamma,
-                                                               const float *beta, int act, int64_t rows_per_block,
-                                                               double *part) {
-    __shared__ double red[2][SHPL_BLOCK];
-    int cc_n = 1;
-    while (cc_n * 2 <= c && cc_n * 2 <= SHPL_BLOCK) cc_n *= 2;  // channels per pass (a power of two)
-    const int rl_n = SHPL_BLOCK / cc_n, rl = threadIdx.x / cc_n, cc = threadIdx.x % cc_n;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    for (int c0 = 0; c0 < c; c0 += cc_n) {
-        const int ch = c0 + cc;
-        double s1 = 0.0, s2 = 0.0;
-        if (ch < c) {
-            const float m = mean ? mean[ch] : 0.0f;
-            const float inv = scale ? __fdiv_rn(scale[ch], gamma ? gamma[ch] : 1.0f) : 1.0f;
-            for (int64_t r = r0 + rl; r < r1; r += rl_n) {
-                const int64_t o = r * stride + ch;
-                const float gb = bn_gbn(y, raw, gy, o, ch, act, mean, scale, beta);
-                const float xh = __fmul_rn(__fsub_rn(Elem<T>::f(raw[o]), m), inv);
-                s1 += (double)gb;
-                s2 += (double)gb * (double)xh;
-            }
-        }
-        red[0][threadIdx.x] = s1;
-        red[1][threadIdx.x] = s2;
-        __syncthreads();
-        if ((int)threadIdx.x < cc_n && c0 + (int)threadIdx.x < c) {
-            double a = 0.0, b = 0.0;
-            for (int k = 0; k < rl_n; ++k) {
-                a += red[0][k * cc_n + threadIdx.x];
-                b += red[1][k * cc_n + threadIdx.x];
-            }
-            part[((int64_t)blockIdx.x * 2 + 0) * c + c0 + threadIdx.x] = a;
-            part[((int64_t)blockIdx.x * 2 + 1) * c + c0 + threadIdx.x] = b;
-        }
-        __syncthreads();
-    }
-}
-
-// Vector form of k_bn_bwd_partial: thread (row lane rl, channel group cg)
-// reads VEC channels of every rl_n-th row; c / VEC a power of two <= 256.
-template <typename T>
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_bwd_partial_vec(const T *y, const T *raw, const T *gy,
-                                                                   int64_t rows, int64_t stride, int c,
-                                                                   const float *mean, const float *scale,
-                                                                   const float *gamma, const float *beta, int act,
-                                                                   int64_t rows_per_block, double *part) {
-    constexpr int VEC = 16 / sizeof(T);
-    __shared__ double red[2][SHPL_BLOCK * VEC];
-    const int cg_n = c / VEC, rl_n = SHPL_BLOCK / cg_n;
-    const int rl = threadIdx.x / cg_n, cg = threadIdx.x % cg_n, ch0 = cg * VEC;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    float m[VEC], inv[VEC], sc[VEC], b[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        m[k] = mean ? mean[ch0 + k] : 0.0f;
-        sc[k] = scale ? scale[ch0 + k] : 1.0f;
-        inv[k] = scale ? __fdiv_rn(scale[ch0 + k], gamma ? gamma[ch0 + k] : 1.0f) : 1.0f;
-        b[k] = beta ? beta[ch0 + k] : 0.0f;
-    }
-    double s1[VEC], s2[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) s1[k] = s2[k] = 0.0;
-    // rows in flight per iteration (the sums stay in row order): bf16 4 (0.81 -> 0.73 ms per 64-frame
-    // step; the apply kernels are slower with more, profiles/r02_bn_sweep.log)
-    constexpr int U = sizeof(T) == 2 ? 4 : BN_U / 2;
-    for (int64_t rb = r0 + rl; rb < r1; rb += U * rl_n) {
-        float gv[U][VEC], xv[U][VEC], yv[U][VEC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (rb + u * rl_n >= r1) break;
-            const int64_t o = (rb + u * rl_n) * stride + ch0;
-            Piece<T, VEC>::load(gy + o, gv[u]);
-            Piece<T, VEC>::load(raw + o, xv[u]);
-            if (act == 1 && y) Piece<T, VEC>::load(y + o, yv[u]);
-        }
-        // the sums in row order, as before
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (rb + u * rl_n >= r1) break;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                if (act == 1 && !y) {
-                    const float t = __fmul_rn(__fsub_rn(xv[u][k], m[k]), sc[k]);
-                    yv[u][k] = beta ? __fadd_rn(t, b[k]) : t;
-                }
-                const float gb = (act == 1 && !(yv[u][k] > 0.0f)) ? 0.0f : gv[u][k];
-                const float xh = __fmul_rn(__fsub_rn(xv[u][k], m[k]), inv[k]);
-                s1[k] += (double)gb;
-                s2[k] += (double)gb * (double)xh;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        red[0][threadIdx.x * VEC + k] = s1[k];
-        red[1][threadIdx.x * VEC + k] = s2[k];
-    }
-    __syncthreads();
-    for (int ch = threadIdx.x; ch < c; ch += SHPL_BLOCK) {
-        const int g2 = ch / VEC, k = ch % VEC;
-        double a = 0.0, b = 0.0;
-        for (int q = 0; q < rl_n; ++q) {
-            a += red[0][(q * cg_n + g2) * VEC + k];
-            b += red[1][(q * cg_n + g2) * VEC + k];
-        }
-        part[((int64_t)blockIdx.x * 2 + 0) * c + ch] = a;
-        part[((int64_t)blockIdx.x * 2 + 1) * c + ch] = b;
-    }
-}
-
-template <typename T, bool ACT, bool HASY, bool BETA, bool TRAIN>
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_bwd_apply_vec(const T *y, const T *raw, const T *gy,
-                                                                 int64_t rows, int64_t stride, int c,
-                                                                 const float *mean, const float *scale,
-                                                                 const float *gamma, const float *beta,
-                                                                 const float *mean_terms, T *graw) {
-    constexpr int VEC = 16 / sizeof(T);
-    const int pr = c / VEC, rpb = SHPL_BLOCK / pr;
-    const int ch0 = (threadIdx.x % pr) * VEC;
-    float sc[VEC], m[VEC], inv[VEC], t0[VEC], t1[VEC], b[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        const int ch = ch0 + k;
-        b[k] = BETA ? beta[ch] : 0.0f;
-        sc[k] = scale ? scale[ch] : 1.0f;
-        m[k] = mean ? mean[ch] : 0.0f;
-        inv[k] = __fdiv_rn(sc[k], gamma ? gamma[ch] : 1.0f);
-        t0[k] = TRAIN ? mean_terms[ch] : 0.0f;
-        t1[k] = TRAIN ? mean_terms[c + ch] : 0.0f;
-    }
-    const int64_t step = (int64_t)gridDim.x * rpb;
-    constexpr int U = BN_U / 2;  // two or three streams in per row
-    for (int64_t r0 = (int64_t)blockIdx.x * rpb + threadIdx.x / pr; r0 < rows; r0 += U * step) {
-        float gv[U][VEC], yv[U][VEC], xv[U][VEC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (r0 + u * step >= rows) break;
-            const int64_t o = (r0 + u * step) * stride + ch0;
-            Piece<T, VEC>::load(gy + o, gv[u]);
-            if constexpr (ACT && HASY) Piece<T, VEC>::load(y + o, yv[u]);
-            if constexpr (TRAIN || (ACT && !HASY)) Piece<T, VEC>::load(raw + o, xv[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (r0 + u * step >= rows) break;
-            float out[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                if constexpr (ACT && !HASY) {
-                    const float t = __fmul_rn(__fsub_rn(xv[u][k], m[k]), sc[k]);
-                    yv[u][k] = BETA ? __fadd_rn(t, b[k]) : t;
-                }
-                const float gb = (ACT && !(yv[u][k] > 0.0f)) ? 0.0f : gv[u][k];
-                if constexpr (TRAIN) {
-                    const float xh = __fmul_rn(__fsub_rn(xv[u][k], m[k]), inv[k]);
-                    out[k] = __fmul_rn(sc[k], __fsub_rn(__fsub_rn(gb, t0[k]), __fmul_rn(xh, t1[k])));
-                } else {
-                    out[k] = __fmul_rn(sc[k], gb);
-                }
-            }
-            Piece<T, VEC>::store(graw + (r0 + u * step) * stride + ch0, out);
-        }
-    }
-}
-
-// one block per channel (strided_sum / block_sum above)
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_bwd_finalize(const double *part, int n_blocks, int c,
-                                                                double count, float *dbeta, float *dgamma,
-                                                                float *mean_terms) {
-    __shared__ double red[SHPL_BLOCK / 64];
-    const int ch = blockIdx.x;
-    const double a = block_sum<SHPL_BLOCK>(strided_sum<SHPL_BLOCK>(part + ch, n_blocks, 2 * c, threadIdx.x), red);
-    const double b =
-        block_sum<SHPL_BLOCK>(strided_sum<SHPL_BLOCK>(part + c + ch, n_blocks, 2 * c, threadIdx.x), red);
-    if (threadIdx.x == 0) {
-        if (dbeta) dbeta[ch] = (float)a;
-        if (dgamma) dgamma[ch] = (float)b;
-        mean_terms[ch] = (float)(a / count);
-        mean_terms[c + ch] = (float)(b / count);
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_bwd_apply(const T *y, const T *raw, const T *gy, int64_t rows,
-                                                             int64_t stride, int c, const float *mean,
-                                                             const float *scale, const float *gamma, const float *beta,
-                                                             int act, int training, const float *mean_terms, T *graw) {
-    const int64_t total = rows * c;
-    for (int64_t t = (int64_t)blockIdx.x * SHPL_BLOCK + threadIdx.x; t < total;
-         t += (int64_t)gridDim.x * SHPL_BLOCK) {
-        const int64_t r = t / c;
-        const int ch = (int)(t - r * c);
-        const int64_t o = r * stride + ch;
-        const float gb = bn_gbn(y, raw, gy, o, ch, act, mean, scale, beta);
-        const float sc = scale ? scale[ch] : 1.0f;
-        float v;
-        if (training) {
-            const float inv = __fdiv_rn(sc, gamma ? gamma[ch] : 1.0f);
-            const float xh = __fmul_rn(__fsub_rn(Elem<T>::f(raw[o]), mean ? mean[ch] : 0.0f), inv);
-            v = __fmul_rn(sc, __fsub_rn(__fsub_rn(gb, mean_terms[ch]), __fmul_rn(xh, mean_terms[c + ch])));
-        } else {
-            v = __fmul_rn(sc, gb);
-        }
-        graw[o] = Elem<T>::back(v);
-    }
 }
 
 // Weight gradient: dW[tap][ci][co] = sum over pixels p of x[p + tap offset][ci] * g[p][co].
@@ -1553,22 +1131,6 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_wgrad_reduce(const float *part, 
     }
 }
 
-struct ConvPlan {
-    int ck, qa, qb, n_cob, tiles_x, tiles_y, tiles_per_frame;
-    int64_t n_tiles;
-    size_t wp_bytes, rp_bytes, part_bytes, total;
-    // k_conv_rows (bf16, at most 4 input chunks): band rows, bands per frame,
-    // occupancy words per BEV row; the pooled runs' buffers (pooled only)
-    bool rows;
-    int band, n_bands, wpr;
-    size_t occ_bytes, cmp_bytes, junk_bytes;
-    // k_conv_wide (bf16, input chunks of 64 channels, whole 256-channel output blocks, no statistics); pooled:
-    // the pooled map materialised in the workspace (map_bytes) by shpl_pull first
-    bool wide, wide_cmp;
-    size_t map_bytes;
-    int64_t pool_cap;
-};
-
 #ifndef SHPL_CONV_ROWS
 #define SHPL_CONV_ROWS 1  // 0: the tiled kernel for every forward (A/B builds)
 #endif
@@ -1578,6 +1140,76 @@ struct ConvPlan {
 #ifndef SHPL_ROWS_BAND
 #define SHPL_ROWS_BAND 0  // 0: about 60 rows, equal bands (k_conv_rows stages band + 2 rows, at most 64)
 #endif
+
+// ---------------------------------------------------------------- host: plans
+// One source of the conv: rows of `stride` elements, of which the channels [off, off + c) are read.
+struct Src { const void *p; int64_t stride, off, c; };
+
+bool vec16(const Src &s, int he) { return aligned16(s.p) && s.stride % he == 0 && s.off % he == 0; }
+
+// A workspace is a run of regions, each a multiple of 256 bytes; take(bytes) is the next one's byte offset.
+// Only the plans below lay one out: everything else reads a region's address from the plan (region<T>; NULL
+// in a NULL workspace, which shpl_conv3x3_rows_form plans with).
+struct Layout {
+    size_t end = 0;
+    size_t take(size_t bytes) { const size_t at = end; end = at + align_up(bytes, 256); return at; }
+};
+
+template <typename T>
+T *region(const void *ws, size_t at) {
+    return ws ? reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(const_cast<void *>(ws)) + at) : nullptr;
+}
+
+// The pooled operand of the row and wide forms (rows::prep_pooled, wide::prep; bf16): the occupancy words of
+// every BEV row, their prefix counts, one compact pooled row per run -- as byte offsets and as addresses.
+struct PooledAt { size_t occ, occ_base, cmp; };
+struct Pooled { uint32_t *occ; int32_t *occ_base; uint16_t *cmp; };
+
+PooledAt pooled_layout(Layout &l, bool on, int n_frames, int64_t h, int wpr, int64_t pool_cap, int64_t c_b) {
+    const size_t words = on ? (size_t)n_frames * h * wpr * 4 : 0, runs = on ? (size_t)pool_cap * c_b * 2 : 0;
+    const size_t occ = l.take(words), occ_base = l.take(words);
+    return {occ, occ_base, l.take(runs)};
+}
+
+Pooled pooled_in(const void *ws, const PooledAt &at) {
+    return {region<uint32_t>(ws, at.occ), region<int32_t>(ws, at.occ_base), region<uint16_t>(ws, at.cmp)};
+}
+
+// How the row kernels (k_conv_rows, k_wgrad_rows) cut an h x w map: strips of TW columns, wpr occupancy
+// words per row, n_bands equal bands of about 60 rows -- or bands of `band` rows (the forward's
+// SHPL_ROWS_BAND; the kernels stage band + 2 rows, at most 64).
+struct RowGeom { int strips, wpr, n_bands, band; };
+
+RowGeom row_geom(int64_t h, int64_t w, int band = 0) {
+    RowGeom g;
+    g.strips = (int)((w + TW - 1) / TW);
+    g.wpr = (int)((w + 31) / 32);
+    g.n_bands = (int)((h + 59) / 60);
+    g.band = (int)((h + g.n_bands - 1) / g.n_bands);
+    if (band > 0 && band <= 62) {
+        g.band = band;
+        g.n_bands = (int)((h + band - 1) / band);
+    }
+    return g;
+}
+
+struct ConvPlan {
+    int ck, qa, qb, n_cob, tiles_x, tiles_y, tiles_per_frame;
+    int64_t n_tiles;
+    // the workspace, as byte offsets in this order: packed weights; k_row_ptr's row pointers (pooled); statistics
+    // partials; the pooled operand (pooled, rows or wide_cmp); k_conv_rows' junk rows; the pooled map
+    // materialised by shpl_pull (pooled, wide and not wide_cmp); its size
+    size_t wp, row_ptr, part;
+    PooledAt pooled;
+    size_t junk, map, total;
+    // k_conv_rows (bf16, at most 4 input chunks) and its bands and strips
+    bool rows;
+    RowGeom g;
+    // k_conv_wide (bf16, input chunks of 64 channels, whole 256-channel output blocks, no statistics); pooled:
+    // wide_cmp, or past the occupancy table's limits the materialised map
+    bool wide, wide_cmp;
+    int64_t pool_cap;
+};
 
 // th: output tile rows -- the forward's ConvTile (8 f32, 16 bf16) unless the
 // weight gradient asks for its own 8. pool_cap: the pooling CSR's entry
@@ -1600,57 +1232,83 @@ int conv_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_
     pl->tiles_per_frame = pl->tiles_x * pl->tiles_y;
     pl->n_tiles = (int64_t)n_frames * pl->tiles_per_frame;
     if (pl->n_tiles >= (1LL << 31) || (int64_t)n_frames * h * w >= (1LL << 31)) return SHPL_ERR_BAD_SHAPE;
-    pl->wp_bytes = align_up((size_t)pl->n_cob * (pl->qa + pl->qb) * W_ROWS * chunk_b, 256);
-    pl->rp_bytes = pooled ? align_up((size_t)n_frames * (h + 1) * 4, 256) : 0;
-    pl->part_bytes = stats ? align_up((size_t)pl->n_cob * NCO * 2 * pl->n_tiles * 8, 256) : 0;
-    pl->wpr = (int)((w + 31) / 32);
+    pl->g = row_geom(h, w, SHPL_ROWS_BAND);
+    const int64_t n_items = (int64_t)n_frames * pl->g.n_bands * pl->g.strips;
+    // the occupancy table and the compact pooled rows hold this map
+    const bool occ_fits = h * pl->g.wpr <= rows::OCC_MAX_WORDS && pool_cap * c_b * 2 < (1LL << 31);
     pl->rows = SHPL_CONV_ROWS && dtype == SHPL_BF16 && pl->qa + pl->qb <= 4 && c_a % 8 == 0 && c_b % 8 == 0 && h > 0 &&
-               w > 0 && rows::supported(pl->qa + pl->qb, pl->qa) &&
-               (!pooled || (h * pl->wpr <= rows::OCC_MAX_WORDS && pool_cap * c_b * esz < (1LL << 31)));
-    pl->n_bands = (int)((h + 59) / 60);
-    pl->band = (int)((h + pl->n_bands - 1) / pl->n_bands);
-    if (SHPL_ROWS_BAND > 0 && SHPL_ROWS_BAND <= 62) {
-        pl->band = SHPL_ROWS_BAND;
-        pl->n_bands = (int)((h + pl->band - 1) / pl->band);
-    }
-    if ((int64_t)n_frames * pl->n_bands * pl->tiles_x >= (1LL << 31)) pl->rows = false;
-    // statistics partials: one per tile (tiled kernel) or per item (k_conv_rows, SHPL_ROWS_BAND may cut more
-    // bands than there are tile rows)
-    if (stats && pl->rows) {
-        const int64_t n_items = (int64_t)n_frames * pl->n_bands * pl->tiles_x;
-        if (n_items > pl->n_tiles) pl->part_bytes = align_up((size_t)pl->n_cob * NCO * 2 * n_items * 8, 256);
-    }
-    pl->occ_bytes = pl->rows && pooled ? 2 * align_up((size_t)n_frames * h * pl->wpr * 4, 256) : 0;
-    pl->pool_cap = pool_cap;
-    pl->cmp_bytes = pl->rows && pooled ? align_up((size_t)pool_cap * c_b * esz, 256) : 0;
-    pl->junk_bytes = pl->rows ? 32 * NCO * 2 : 0;
+               w > 0 && rows::supported(pl->qa + pl->qb, pl->qa) && (!pooled || occ_fits) && n_items < (1LL << 31);
     pl->wide = SHPL_CONV_WIDE && dtype == SHPL_BF16 && !stats && !pl->rows && h > 0 && w > 0 &&
                wide::supported(c_a, c_b, c_out) && (int64_t)n_frames * h * w * (c_b > 0 ? c_b : 1) < (1LL << 40);
-    pl->map_bytes = 0;
-    pl->wide_cmp = false;
-    if (pl->wide) {
-        const size_t wb = align_up(wide::packed_bytes(c_a, c_b, c_out), 256);
-        if (wb > pl->wp_bytes) pl->wp_bytes = wb;
-        // pooled: the occupancy words + prefixes and the compact pooled runs (wide::prep), read by the halo
-        // staging -- or, past the occupancy table's limits, the pooled map materialised by shpl_pull
-        pl->wide_cmp = pooled && h * pl->wpr <= rows::OCC_MAX_WORDS && pool_cap * c_b * 2 < (1LL << 31);
-        if (pooled && pl->wide_cmp)
-            pl->map_bytes = 2 * align_up((size_t)n_frames * h * pl->wpr * 4, 256) + align_up((size_t)pool_cap * c_b * 2, 256);
-        else if (pooled)
-            pl->map_bytes = align_up((size_t)n_frames * h * w * c_b * 2, 256);
-    }
-    pl->total = pl->wp_bytes + pl->rp_bytes + pl->part_bytes + pl->occ_bytes + pl->cmp_bytes + pl->junk_bytes +
-                pl->map_bytes;
+    pl->wide_cmp = pl->wide && pooled && occ_fits;
+    pl->pool_cap = pool_cap;
+    size_t wp_bytes = (size_t)pl->n_cob * (pl->qa + pl->qb) * W_ROWS * chunk_b;
+    if (pl->wide && wide::packed_bytes(c_a, c_b, c_out) > wp_bytes) wp_bytes = wide::packed_bytes(c_a, c_b, c_out);
+    // statistics partials: one per tile (tiled kernel) or per item (k_conv_rows, SHPL_ROWS_BAND may cut more
+    // bands than there are tile rows)
+    const int64_t n_part = !stats ? 0 : pl->rows && n_items > pl->n_tiles ? n_items : pl->n_tiles;
+    Layout l;
+    pl->wp = l.take(wp_bytes);
+    pl->row_ptr = l.take(pooled ? (size_t)n_frames * (h + 1) * 4 : 0);
+    pl->part = l.take((size_t)pl->n_cob * NCO * 2 * n_part * 8);
+    pl->pooled = pooled_layout(l, pooled && (pl->rows || pl->wide_cmp), n_frames, h, pl->g.wpr, pool_cap, c_b);
+    pl->junk = l.take(pl->rows ? 32 * NCO * 2 : 0);
+    pl->map = l.take(pl->wide && pooled && !pl->wide_cmp ? (size_t)n_frames * h * w * c_b * 2 : 0);
+    pl->total = l.end;
     return SHPL_OK;
 }
 
-bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
+// The fields of ConvArgs every form fills: frame and tile geometry, the sources, the pool's arrays; the rest 0.
+ConvArgs conv_args(int dtype, int n_frames, int64_t h, int64_t w, const ConvPlan &pl, const Src &A, const Src &B,
+                   const shpl_csr *pool) {
+    const int he = dtype == SHPL_F32 ? 4 : 8;
+    ConvArgs a = {};
+    a.n_frames = n_frames;
+    a.h = (int)h;
+    a.w = (int)w;
+    a.tiles_x = pl.tiles_x;
+    a.tiles_per_frame = pl.tiles_per_frame;
+    a.n_tiles = (int)pl.n_tiles;
+    a.a = A.p;
+    a.a_stride = A.stride;
+    a.a_off = A.off;
+    a.c_a = (int)A.c;
+    a.qa = pl.qa;
+    a.b = B.p;
+    a.b_stride = B.stride;
+    a.b_off = B.off;
+    a.c_b = (int)B.c;
+    a.qb = pl.qb;
+    a.vec_a = vec16(A, he);
+    a.vec_b = vec16(B, he);
+    a.ent_dst = pool ? pool->ent_dst : nullptr;
+    a.ent_src = pool ? pool->ent_src : nullptr;
+    a.ent_val = pool ? pool->ent_val : nullptr;
+    return a;
+}
 
+// The checks on the sources and the pool that the forward and the weight gradient share, in their order.
+// o_stride: the row stride of the map of c_out channels (the output, or its gradient).
+int check_sources(int n_frames, int64_t h, int64_t w, const Src &A, const Src &B, const shpl_csr *pool,
+                  const int64_t *d_frame_off, int64_t o_stride, int64_t c_out) {
+    if (A.stride < A.off + A.c || o_stride < c_out || A.off < 0 || B.off < 0) return SHPL_ERR_BAD_SHAPE;
+    if (B.c > 0 && B.stride < B.off + B.c) return SHPL_ERR_BAD_SHAPE;
+    if (pool) {
+        if (!d_frame_off || B.c < 1 || !B.p) return SHPL_ERR_ARG;
+        if (pool->n_keys != (int64_t)n_frames * h * w) return SHPL_ERR_BAD_SHAPE;
+        if (pool->nnz_cap > 0 && (!pool->ent_dst || !pool->ent_src || !pool->ent_val)) return SHPL_ERR_ARG;
+    } else if (B.c > 0 && !B.p) {
+        return SHPL_ERR_ARG;
+    }
+    return SHPL_OK;
+}
+
+// ---------------------------------------------------------------- host: forward and input gradient
 // k_conv_rows (shpl_conv_rows.hip) and, pooled, its two preparatory launches
 // (occupancy words + prefix counts per frame; the pooled vector of every run
 // into the compact buffer). The packed weights are already in a.wp.
-int conv_rows_launch(const ConvPlan &pl, const ConvArgs &a, bool pooled, bool stats, const int64_t *frame_off,
-                     double *d_stats, hipStream_t s) {
+int conv_rows_launch(const ConvPlan &pl, const ConvArgs &a, void *ws, bool pooled, bool stats,
+                     const int64_t *frame_off, double *d_stats, hipStream_t s) {
     rows::RowArgs r = {};
     r.a = reinterpret_cast<const uint16_t *>(a.a) + a.a_off;
     r.b = reinterpret_cast<const uint16_t *>(a.b) + a.b_off;
@@ -1660,37 +1318,34 @@ int conv_rows_launch(const ConvPlan &pl, const ConvArgs &a, bool pooled, bool st
     r.c_b = a.c_b;
     r.h = a.h;
     r.w = a.w;
-    r.strips = pl.tiles_x;
-    r.band = pl.band;
-    r.n_bands = pl.n_bands;
-    r.n_items = a.n_frames * pl.n_bands * pl.tiles_x;
+    r.strips = pl.g.strips;
+    r.band = pl.g.band;
+    r.n_bands = pl.g.n_bands;
+    r.n_items = a.n_frames * pl.g.n_bands * pl.g.strips;
     r.wp = reinterpret_cast<const uint16_t *>(a.wp);
     r.center = a.center;
     r.scale = a.scale;
     r.shift = a.shift;
     r.out = reinterpret_cast<uint16_t *>(a.out);
     r.out_stride = a.out_stride;
-    r.wpr = pl.wpr;
+    r.wpr = pl.g.wpr;
     r.frame_off = frame_off;
     r.out2 = reinterpret_cast<uint16_t *>(a.out2);
     r.out2_stride = a.out2_stride;
     r.c_split = a.c_split;
     r.occ2 = a.occ2;
     r.n_cob = pl.n_cob;
-    r.part = stats ? a.part : nullptr;  // n_items <= n_tiles: the tiled plan's partials hold the rows kernel's
-    uint8_t *ws = reinterpret_cast<uint8_t *>(const_cast<void *>(a.wp)) + pl.wp_bytes + pl.rp_bytes + pl.part_bytes;
-    r.junk = reinterpret_cast<uint16_t *>(ws + pl.occ_bytes + pl.cmp_bytes);
+    r.part = stats ? a.part : nullptr;
+    r.junk = region<uint16_t>(ws, pl.junk);
     if (pooled) {
-        uint32_t *occ = reinterpret_cast<uint32_t *>(ws);
-        int32_t *occ_base = reinterpret_cast<int32_t *>(ws + pl.occ_bytes / 2);
-        uint16_t *cmp = reinterpret_cast<uint16_t *>(ws + pl.occ_bytes);
-        const int rc = rows::prep_pooled(a.n_frames, a.h, a.w, pl.wpr, a.ent_dst, a.ent_src, a.ent_val, pl.pool_cap,
+        const Pooled po = pooled_in(ws, pl.pooled);
+        const int rc = rows::prep_pooled(a.n_frames, a.h, a.w, pl.g.wpr, a.ent_dst, a.ent_src, a.ent_val, pl.pool_cap,
                                          frame_off, reinterpret_cast<const uint16_t *>(a.b), a.b_stride, a.b_off,
-                                         a.c_b, occ, occ_base, cmp, s);
+                                         a.c_b, po.occ, po.occ_base, po.cmp, s);
         if (rc) return rc;
-        r.occ = occ;
-        r.occ_base = occ_base;
-        r.cmp = cmp;
+        r.occ = po.occ;
+        r.occ_base = po.occ_base;
+        r.cmp = po.cmp;
     }
     int rc = rows::launch(r, pl.qa + pl.qb, pl.qa, pooled, a.act == 1, stats, s);
     if (rc || !stats) return rc;
@@ -1709,9 +1364,10 @@ bool rows_forward(const ConvPlan &pl, const ConvArgs &a, bool pooled, bool stats
            (!stats || (a.act == 0 && rows::supported_st(pl.qa + pl.qb, pl.qa, pooled)));
 }
 
-// The wide bf16 form (k_conv_wide): pooled, the pooled map first into the workspace's last region by
-// shpl_pull (the same arithmetic as the tiled staging: the conv of [a || map] is the fused conv's).
-int conv_wide_launch(const ConvPlan &pl, const ConvArgs &a, const shpl_csr *pool, const int64_t *frame_off,
+// The wide bf16 form (k_conv_wide). Pooled: B's rows are the compact pooled runs (wide::prep), or -- past
+// the occupancy table -- the pooled map, materialised first by shpl_pull (the same arithmetic as the tiled
+// staging: the conv of [a || map] is the fused conv's).
+int conv_wide_launch(const ConvPlan &pl, const ConvArgs &a, void *ws, const shpl_csr *pool, const int64_t *frame_off,
                      const void *w, hipStream_t s) {
     wide::WideArgs r = {};
     r.a = reinterpret_cast<const uint16_t *>(a.a) + a.a_off;
@@ -1719,23 +1375,18 @@ int conv_wide_launch(const ConvPlan &pl, const ConvArgs &a, const shpl_csr *pool
     r.c_a = a.c_a;
     r.c_b = a.c_b;
     if (pool && pl.wide_cmp) {
-        uint8_t *ws = reinterpret_cast<uint8_t *>(const_cast<void *>(a.wp)) + pl.total - pl.map_bytes;
-        const size_t ob = align_up((size_t)a.n_frames * a.h * pl.wpr * 4, 256);
-        uint32_t *occ = reinterpret_cast<uint32_t *>(ws);
-        int32_t *occ_base = reinterpret_cast<int32_t *>(ws + ob);
-        uint16_t *cmp = reinterpret_cast<uint16_t *>(ws + 2 * ob);
-        const int rc = wide::prep(a.n_frames, a.h, a.w, pl.wpr, pool->ent_dst, pool->ent_src, pool->ent_val,
+        const Pooled po = pooled_in(ws, pl.pooled);
+        const int rc = wide::prep(a.n_frames, a.h, a.w, pl.g.wpr, pool->ent_dst, pool->ent_src, pool->ent_val,
                                   pool->nnz_cap, frame_off, reinterpret_cast<const uint16_t *>(a.b), a.b_stride, a.b_off,
-                                  a.c_b, occ, occ_base, cmp, s);
+                                  a.c_b, po.occ, po.occ_base, po.cmp, s);
         if (rc) return rc;
-        r.occ = occ;
-        r.occ_base = occ_base;
+        r.occ = po.occ;
+        r.occ_base = po.occ_base;
         r.frame_off = frame_off;
-        r.cmp = cmp;
-        r.wpr = pl.wpr;
+        r.cmp = po.cmp;
+        r.wpr = pl.g.wpr;
     } else if (pool) {
-        uint16_t *map = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(const_cast<void *>(a.wp)) + pl.total -
-                                                     pl.map_bytes);
+        uint16_t *map = region<uint16_t>(ws, pl.map);
         const int rc = shpl_pull(SHPL_BY_CELL, SHPL_BF16, pool, a.b, a.b_stride, a.b_off, a.c_b, nullptr, 0, 0, 0,
                                  SHPL_OUT_POOL, map, a.c_b, s);
         if (rc) return rc;
@@ -1759,13 +1410,15 @@ int conv_wide_launch(const ConvPlan &pl, const ConvArgs &a, const shpl_csr *pool
                         reinterpret_cast<uint16_t *>(const_cast<void *>(a.wp)), s);
 }
 
+// ws: the call's workspace, laid out by pl.
 template <typename T>
-int conv_launch(const ConvPlan &pl, ConvArgs &a, bool pooled, bool stats, const void *w, const int64_t *frame_off,
-                double *d_stats, hipStream_t s, int transpose = 0, const shpl_csr *pool = nullptr) {
+int conv_launch(const ConvPlan &pl, ConvArgs &a, void *ws, bool pooled, bool stats, const void *w,
+                const int64_t *frame_off, double *d_stats, hipStream_t s, int transpose = 0,
+                const shpl_csr *pool = nullptr) {
     if constexpr (sizeof(T) == 2) {
         if (pl.wide && !stats && !transpose && !a.out2 && a.vec_a && (a.c_b == 0 || a.vec_b) && a.vec_out &&
             a.n_frames > 0 && (!pooled || pool))
-            return conv_wide_launch(pl, a, pooled ? pool : nullptr, frame_off, w, s);
+            return conv_wide_launch(pl, a, ws, pooled ? pool : nullptr, frame_off, w, s);
     }
     T *wp = reinterpret_cast<T *>(const_cast<void *>(a.wp));
     const int64_t wtot = (int64_t)pl.n_cob * (pl.qa + pl.qb) * W_ROWS * Elem<T>::CK;
@@ -1775,7 +1428,8 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, bool pooled, bool stats, const 
     if constexpr (sizeof(T) == 2) {
         // bf16 with at most 64 input channels: the row-streaming kernel (k_conv_rows), also for the input
         // gradient's two maps (split at a whole output block) and the training forward's statistics
-        if (rows_forward(pl, a, pooled, stats)) return conv_rows_launch(pl, a, pooled, stats, frame_off, d_stats, s);
+        if (rows_forward(pl, a, pooled, stats))
+            return conv_rows_launch(pl, a, ws, pooled, stats, frame_off, d_stats, s);
     }
     if (pooled) {
         hipLaunchKernelGGL(k_row_ptr, dim3(16, a.n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, frame_off, a.h, a.w,
@@ -1788,19 +1442,11 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, bool pooled, bool stats, const 
     // nothing (2.73 / 2.77 ms: 3 waves per SIMD instead of 6 for a
     // memory-pipeline-bound kernel) and keeps one.
     const bool pair = sizeof(T) == 4 && !pooled && !stats && pl.n_cob % 2 == 0;
-    if (pooled) {
-        if (stats)
-            hipLaunchKernelGGL((k_conv3x3<T, true, true>), grid, dim3(CONV_BLOCK), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_conv3x3<T, true, false>), grid, dim3(CONV_BLOCK), 0, s, a);
-    } else {
-        if (stats)
-            hipLaunchKernelGGL((k_conv3x3<T, false, true>), grid, dim3(CONV_BLOCK), 0, s, a);
-        else if (pair)
-            hipLaunchKernelGGL((k_conv3x3<T, false, false, 2>), dim3(grid.x, grid.y / 2), dim3(CONV_BLOCK), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_conv3x3<T, false, false>), grid, dim3(CONV_BLOCK), 0, s, a);
-    }
+    const auto kernel = pooled  ? (stats ? k_conv3x3<T, true, true> : k_conv3x3<T, true, false>)
+                        : stats ? k_conv3x3<T, false, true>
+                        : pair  ? k_conv3x3<T, false, false, 2>
+                                : k_conv3x3<T, false, false>;
+    hipLaunchKernelGGL(kernel, pair ? dim3(grid.x, grid.y / 2) : grid, dim3(CONV_BLOCK), 0, s, a);
     SHPL_LAUNCH_CHECK();
     if (stats) {
         hipLaunchKernelGGL(k_stats_reduce, dim3(pl.n_cob * NCO * 2), dim3(RED_BLOCK), 0, s, a.part, (int)pl.n_tiles,
@@ -1810,79 +1456,29 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, bool pooled, bool stats, const 
     return SHPL_OK;
 }
 
-}  // namespace
-}  // namespace shpl
-
-using namespace shpl;
-
-extern "C" int shpl_conv3x3_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b,
-                                            int64_t c_out, int64_t pool_nnz_cap, int stats, size_t *bytes) {
-    if (!bytes) return SHPL_ERR_ARG;
-    ConvPlan pl;
-    const bool pooled = pool_nnz_cap >= 0;
-    const int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, stats != 0, &pl, 0,
-                             pooled ? pool_nnz_cap : 0);
-    if (rc) return rc;
-    *bytes = pl.total;
-    return SHPL_OK;
-}
-
-namespace shpl {
-namespace {
 // shpl_conv3x3's argument checks and kernel arguments (shared with shpl_conv3x3_rows_form). *empty: no pixel.
-int forward_setup(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride, int64_t a_off,
-                  int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, const shpl_csr *pool,
+int forward_setup(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, const Src &B, const shpl_csr *pool,
                   const int64_t *d_frame_off, const void *d_weights, int64_t c_out, const float *d_center,
-                  const float *d_scale, const float *d_shift, int act, void *d_out, int64_t out_stride,
-                  bool stats, void *d_ws, size_t ws_bytes, bool check_ws, ConvPlan &pl, ConvArgs &a, bool *empty) {
+                  const float *d_scale, const float *d_shift, int act, void *d_out, int64_t out_stride, bool stats,
+                  void *d_ws, size_t ws_bytes, bool check_ws, ConvPlan &pl, ConvArgs &a, bool *empty) {
     const bool pooled = pool != nullptr;
     *empty = false;
-    int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, stats, &pl, 0, pooled ? pool->nnz_cap : 0);
+    int rc = conv_plan(dtype, n_frames, h, w, A.c, B.c, c_out, pooled, stats, &pl, 0, pooled ? pool->nnz_cap : 0);
     if (rc) return rc;
     if (act != 0 && act != 1) return SHPL_ERR_ARG;
     if (!d_weights || (check_ws && ws_bytes > 0 && !d_ws)) return SHPL_ERR_ARG;
     if (check_ws && ws_bytes < pl.total) return SHPL_ERR_WORKSPACE;
-    if (a_stride < a_off + c_a || out_stride < c_out || a_off < 0 || b_off < 0) return SHPL_ERR_BAD_SHAPE;
-    if (c_b > 0 && b_stride < b_off + c_b) return SHPL_ERR_BAD_SHAPE;
-    if (pooled) {
-        if (!d_frame_off || c_b < 1 || !d_b) return SHPL_ERR_ARG;
-        if (pool->n_keys != (int64_t)n_frames * h * w) return SHPL_ERR_BAD_SHAPE;
-        if (pool->nnz_cap > 0 && (!pool->ent_dst || !pool->ent_src || !pool->ent_val)) return SHPL_ERR_ARG;
-    } else if (c_b > 0 && !d_b) {
-        return SHPL_ERR_ARG;
-    }
+    rc = check_sources(n_frames, h, w, A, B, pool, d_frame_off, out_stride, c_out);
+    if (rc) return rc;
     if (pl.n_tiles == 0) {
         *empty = true;
         return SHPL_OK;
     }
-    if (!d_out || (c_a > 0 && !d_a)) return SHPL_ERR_ARG;
-    const int esz = dtype == SHPL_F32 ? 4 : 2, he = 16 / esz;
-    a = ConvArgs{};  // every field the forward does not set (out2: the dgrad split) is zero
-    a.n_frames = n_frames;
-    a.h = (int)h;
-    a.w = (int)w;
-    a.tiles_x = pl.tiles_x;
-    a.tiles_per_frame = pl.tiles_per_frame;
-    a.n_tiles = (int)pl.n_tiles;
-    a.a = d_a;
-    a.a_stride = a_stride;
-    a.a_off = a_off;
-    a.c_a = (int)c_a;
-    a.qa = pl.qa;
-    a.b = d_b;
-    a.b_stride = b_stride;
-    a.b_off = b_off;
-    a.c_b = (int)c_b;
-    a.qb = pl.qb;
-    a.vec_a = aligned16(d_a) && a_stride % he == 0 && a_off % he == 0;
-    a.vec_b = aligned16(d_b) && b_stride % he == 0 && b_off % he == 0;
-    a.ent_dst = pooled ? pool->ent_dst : nullptr;
-    a.ent_src = pooled ? pool->ent_src : nullptr;
-    a.ent_val = pooled ? pool->ent_val : nullptr;
-    uint8_t *ws = reinterpret_cast<uint8_t *>(d_ws);
-    a.wp = ws;
-    a.row_ptr = pooled && ws ? reinterpret_cast<const int32_t *>(ws + pl.wp_bytes) : nullptr;
-    a.part = stats && ws ? reinterpret_cast<double *>(ws + pl.wp_bytes + pl.rp_bytes) : nullptr;
+    if (!d_out || (A.c > 0 && !A.p)) return SHPL_ERR_ARG;
+    a = conv_args(dtype, n_frames, h, w, pl, A, B, pool);  // what the forward does not set (out2: the dgrad split) is zero
+    a.wp = region<void>(d_ws, pl.wp);
+    a.row_ptr = pooled ? region<int32_t>(d_ws, pl.row_ptr) : nullptr;
+    a.part = stats ? region<double>(d_ws, pl.part) : nullptr;
     a.center = d_center;
     a.scale = d_scale;
     a.shift = d_shift;
@@ -1890,169 +1486,26 @@ int forward_setup(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a
     a.out = d_out;
     a.out_stride = out_stride;
     a.c_out = (int)c_out;
-    a.vec_out = aligned16(d_out) && out_stride % he == 0;
+    a.vec_out = vec16({d_out, out_stride, 0, c_out}, dtype == SHPL_F32 ? 4 : 8);
     return SHPL_OK;
 }
-}  // namespace
-}  // namespace shpl
 
-extern "C" int shpl_conv3x3(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
-                            int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off,
-                            int64_t c_b, const shpl_csr *pool, const int64_t *d_frame_off, const void *d_weights,
-                            int64_t c_out, const float *d_center, const float *d_scale, const float *d_shift,
-                            int act, void *d_out, int64_t out_stride, double *d_stats, void *d_ws, size_t ws_bytes,
-                            void *stream) {
-    const bool pooled = pool != nullptr, stats = d_stats != nullptr;
-    ConvPlan pl;
-    ConvArgs a;
-    bool empty;
-    const int rc = forward_setup(dtype, n_frames, h, w, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, pool,
-                                 d_frame_off, d_weights, c_out, d_center, d_scale, d_shift, act, d_out, out_stride,
-                                 stats, d_ws, ws_bytes, true, pl, a, &empty);
-    if (rc || empty) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == SHPL_F32) return conv_launch<float>(pl, a, pooled, stats, d_weights, d_frame_off, d_stats, s);
-    return conv_launch<uint16_t>(pl, a, pooled, stats, d_weights, d_frame_off, d_stats, s, 0, pool);
-}
-
-extern "C" int shpl_conv3x3_rows_form(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a,
-                                      int64_t a_stride, int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride,
-                                      int64_t b_off, int64_t c_b, const shpl_csr *pool, const int64_t *d_frame_off,
-                                      const void *d_weights, int64_t c_out, int act, const void *d_out,
-                                      int64_t out_stride, int stats, int *rows_form) {
-    if (!rows_form) return SHPL_ERR_ARG;
-    *rows_form = 0;
-    ConvPlan pl;
-    ConvArgs a;
-    bool empty;
-    const int rc = forward_setup(dtype, n_frames, h, w, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, pool,
-                                 d_frame_off, d_weights, c_out, nullptr, nullptr, nullptr, act,
-                                 const_cast<void *>(d_out), out_stride, stats != 0, nullptr, 0, false, pl, a, &empty);
+// The pooled operand that a pooled bf16 forward (shpl_conv3x3 of [A (c_a) || B pooled (c_b)] to c_out channels,
+// with statistics or not) left in its workspace, where its plan put it. SHPL_ERR_ARG when that forward did not
+// run the row form or its workspace is smaller than its plan, as far as can be told here: the rest of
+// rows_forward (its act and output alignment) is the caller's to establish with shpl_conv3x3_rows_form (shpl.h).
+int forward_pooled(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b, int64_t c_out,
+                   int64_t pool_cap, int fwd_stats, const void *d_fwd_ws, size_t fwd_ws_bytes, Pooled *po) {
+    ConvPlan fp;
+    const int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, true, fwd_stats != 0, &fp, 0, pool_cap);
     if (rc) return rc;
-    *rows_form = !empty && dtype == SHPL_BF16 && rows_forward(pl, a, pool != nullptr, stats != 0);
+    if (!fp.rows || fwd_ws_bytes < fp.total || c_out % NCO != 0 ||
+        (fwd_stats != 0 && !rows::supported_st(fp.qa + fp.qb, fp.qa, true)))
+        return SHPL_ERR_ARG;
+    *po = pooled_in(d_fwd_ws, fp.pooled);
     return SHPL_OK;
 }
 
-extern "C" int shpl_batch_norm(int dtype, int64_t rows, void *d_x, void *d_y, int64_t stride, int64_t c,
-                               const double *d_stats, double count, float eps, const float *d_gamma,
-                               const float *d_beta, int act, float *d_moving_mean, float *d_moving_var, float decay,
-                               float *d_batch_mean, float *d_batch_var, float *d_ws, void *stream) {
-    if (dtype != SHPL_F32 && dtype != SHPL_BF16) return SHPL_ERR_ARG;
-    if (rows < 0 || c < 1 || stride < c || c > (1 << 16)) return SHPL_ERR_BAD_SHAPE;
-    if (act != 0 && act != 1) return SHPL_ERR_ARG;
-    if (!d_stats || !d_ws || (rows > 0 && !d_x) || !(count > 0.0)) return SHPL_ERR_ARG;
-    if (!d_y) d_y = d_x;
-    hipStream_t s = (hipStream_t)stream;
-    float *mean = d_ws, *scale = d_ws + c;
-    hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(SHPL_BLOCK), 0, s, d_stats, count, (int)c, eps, d_gamma, mean,
-                       scale, d_moving_mean, d_moving_var, decay, d_batch_mean, d_batch_var);
-    SHPL_LAUNCH_CHECK();
-    if (rows == 0) return SHPL_OK;
-    const int vec = dtype == SHPL_F32 ? 4 : 8;
-    const int pr = (int)(c / vec);
-    const bool vform = c % vec == 0 && stride % vec == 0 && pr <= SHPL_BLOCK && (pr & (pr - 1)) == 0 &&
-                       aligned16(d_x) && aligned16(d_y);
-    const int grid = grid_for(rows * c / (vform ? vec : 1), SHPL_BLOCK * bn_rows_per_thread(16 / vec), 1 << 22);
-    if (dtype == SHPL_F32) {
-        if (vform)
-            bn_forms([&](auto B, auto A) {
-                hipLaunchKernelGGL((k_bn_apply_vec<float, B.value, A.value>), dim3(grid), dim3(SHPL_BLOCK), 0, s,
-                                   reinterpret_cast<const float *>(d_x), reinterpret_cast<float *>(d_y), rows, stride,
-                                   (int)c, mean, scale, d_beta);
-            }, d_beta != nullptr, act == 1);
-        else
-            hipLaunchKernelGGL(k_bn_apply<float>, dim3(grid), dim3(SHPL_BLOCK), 0, s,
-                               reinterpret_cast<const float *>(d_x), reinterpret_cast<float *>(d_y), rows, stride,
-                               (int)c, mean, scale, d_beta, act);
-    } else {
-        if (vform)
-            bn_forms([&](auto B, auto A) {
-                hipLaunchKernelGGL((k_bn_apply_vec<uint16_t, B.value, A.value>), dim3(grid), dim3(SHPL_BLOCK), 0, s,
-                                   reinterpret_cast<const uint16_t *>(d_x), reinterpret_cast<uint16_t *>(d_y), rows,
-                                   stride, (int)c, mean, scale, d_beta);
-            }, d_beta != nullptr, act == 1);
-        else
-            hipLaunchKernelGGL(k_bn_apply<uint16_t>, dim3(grid), dim3(SHPL_BLOCK), 0, s,
-                               reinterpret_cast<const uint16_t *>(d_x), reinterpret_cast<uint16_t *>(d_y), rows,
-                               stride, (int)c, mean, scale, d_beta, act);
-    }
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
-}
-
-namespace {
-int bn_bwd_blocks(int64_t rows) {
-    int64_t nb = (rows + 4095) / 4096;
-    if (nb < 1) nb = 1;
-    if (nb > 1024) nb = 1024;
-    return (int)nb;
-}
-}  // namespace
-
-extern "C" int shpl_batch_norm_backward_workspace_bytes(int64_t rows, int64_t c, size_t *bytes) {
-    if (!bytes || rows < 0 || c < 1) return SHPL_ERR_ARG;
-    *bytes = align_up((size_t)bn_bwd_blocks(rows) * 2 * c * sizeof(double), 256) + align_up(2 * c * sizeof(float), 256);
-    return SHPL_OK;
-}
-
-extern "C" int shpl_batch_norm_backward(int dtype, int64_t rows, const void *d_y, const void *d_raw,
-                                        const void *d_gy, int64_t stride, int64_t c, const float *d_mean,
-                                        const float *d_scale, const float *d_gamma, const float *d_beta, int act,
-                                        int training, void *d_graw, float *d_dbeta, float *d_dgamma, void *d_ws,
-                                        size_t ws_bytes, void *stream) {
-    if (dtype != SHPL_F32 && dtype != SHPL_BF16) return SHPL_ERR_ARG;
-    if (rows < 0 || c < 1 || stride < c || c > (1 << 16)) return SHPL_ERR_BAD_SHAPE;
-    if (act != 0 && act != 1) return SHPL_ERR_ARG;
-    size_t need;
-    shpl_batch_norm_backward_workspace_bytes(rows, c, &need);
-    if (!d_ws || ws_bytes < need) return SHPL_ERR_WORKSPACE;
-    if (rows > 0 && (!d_gy || !d_graw || (act == 1 && !d_y && !d_raw) || (training && !d_raw))) return SHPL_ERR_ARG;
-    if (rows == 0) return SHPL_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = bn_bwd_blocks(rows);
-    const int64_t rpb = (rows + nb - 1) / nb;
-    double *part = reinterpret_cast<double *>(d_ws);
-    float *mt = reinterpret_cast<float *>((uint8_t *)d_ws + align_up((size_t)nb * 2 * c * sizeof(double), 256));
-    // x-hat needs raw only in training (dgamma); otherwise any row-shaped input stands in
-    const void *rw = d_raw ? d_raw : d_gy;
-    const int vec = dtype == SHPL_F32 ? 4 : 8;
-    const int cg = (int)(c / vec);
-    const bool vform = c % vec == 0 && stride % vec == 0 && cg <= SHPL_BLOCK && (cg & (cg - 1)) == 0 &&
-                       aligned16(d_gy) && aligned16(rw) && aligned16(d_graw) && (!d_y || aligned16(d_y));
-    // y NULL: the ReLU mask from raw (bn_pre_act), so only the y argument of the kernels changes
-    const float *beta = act == 1 && !d_y ? d_beta : nullptr;
-    const int grid = grid_for(rows * c / (vform ? vec : 1), SHPL_BLOCK * bn_rows_per_thread(16 / vec), 1 << 22);
-    auto launch = [&](auto tag) {
-        typedef decltype(tag) T;
-        const T *y = (const T *)d_y, *r = (const T *)rw, *g = (const T *)d_gy;
-        if (vform)
-            // (its switches as template arguments measured slower: 785 vs 747 us, profiles/r04_bn_ab.log)
-            hipLaunchKernelGGL(k_bn_bwd_partial_vec<T>, dim3(nb), dim3(SHPL_BLOCK), 0, s, y, r, g, rows, stride,
-                               (int)c, d_mean, d_scale, d_gamma, beta, act, rpb, part);
-        else
-            hipLaunchKernelGGL(k_bn_bwd_partial<T>, dim3(nb), dim3(SHPL_BLOCK), 0, s, y, r, g, rows, stride, (int)c,
-                               d_mean, d_scale, d_gamma, beta, act, rpb, part);
-        hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)c), dim3(SHPL_BLOCK), 0, s, part, nb,
-                           (int)c, (double)rows, d_dbeta, d_raw ? d_dgamma : nullptr, mt);
-        if (vform)
-            bn_forms([&](auto A, auto Y, auto B, auto TR) {
-                hipLaunchKernelGGL((k_bn_bwd_apply_vec<T, A.value, Y.value, B.value, TR.value>), dim3(grid),
-                                   dim3(SHPL_BLOCK), 0, s, y, r, g, rows, stride, (int)c, d_mean, d_scale, d_gamma,
-                                   beta, mt, (T *)d_graw);
-            }, act == 1, d_y != nullptr, beta != nullptr, training != 0);
-        else
-            hipLaunchKernelGGL(k_bn_bwd_apply<T>, dim3(grid), dim3(SHPL_BLOCK), 0, s, y, r, g, rows, stride, (int)c,
-                               d_mean, d_scale, d_gamma, beta, act, training, mt, (T *)d_graw);
-    };
-    if (dtype == SHPL_F32)
-        launch(float());
-    else
-        launch(uint16_t());
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
-}
-
-namespace {
 // shpl_conv3x3_dgrad; occ2: the occupancy words (wpr per row) limiting d_dx_b's stores (shpl_conv3x3_dgrad_reuse)
 int dgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, int64_t gy_stride, int64_t c_gy,
                const void *d_weights, int64_t c_dx, void *d_dx, int64_t dx_stride, int64_t c_split, void *d_dx_b,
@@ -2068,22 +1521,9 @@ int dgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, 
         return SHPL_ERR_BAD_SHAPE;
     if (pl.n_tiles == 0) return SHPL_OK;
     if (!d_gy || (c_split > 0 && !d_dx)) return SHPL_ERR_ARG;
-    const int esz = dtype == SHPL_F32 ? 4 : 2, he = 16 / esz;
-    ConvArgs a = {};
-    a.n_frames = n_frames;
-    a.h = (int)h;
-    a.w = (int)w;
-    a.tiles_x = pl.tiles_x;
-    a.tiles_per_frame = pl.tiles_per_frame;
-    a.n_tiles = (int)pl.n_tiles;
-    a.a = d_gy;
-    a.a_stride = gy_stride;
-    a.a_off = 0;
-    a.c_a = (int)c_gy;
-    a.qa = pl.qa;
-    a.vec_a = aligned16(d_gy) && gy_stride % he == 0;
-    a.wp = d_ws;
-    a.act = 0;
+    const int he = dtype == SHPL_F32 ? 4 : 8;
+    ConvArgs a = conv_args(dtype, n_frames, h, w, pl, {d_gy, gy_stride, 0, c_gy}, {}, nullptr);
+    a.wp = region<void>(d_ws, pl.wp);
     a.out = d_dx;
     a.out_stride = dx_stride;
     a.c_out = (int)c_dx;
@@ -2094,49 +1534,23 @@ int dgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, 
                 (!d_dx_b || (aligned16(d_dx_b) && dx_b_stride % he == 0 && c_split % he == 0));
     a.occ2 = d_dx_b ? occ2 : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SHPL_F32) return conv_launch<float>(pl, a, false, false, d_weights, nullptr, nullptr, s, 1);
-    return conv_launch<uint16_t>(pl, a, false, false, d_weights, nullptr, nullptr, s, 1);
-}
-}  // namespace
-
-extern "C" int shpl_conv3x3_dgrad(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, int64_t gy_stride,
-                                  int64_t c_gy, const void *d_weights, int64_t c_dx, void *d_dx, int64_t dx_stride,
-                                  int64_t c_split, void *d_dx_b, int64_t dx_b_stride, void *d_ws, size_t ws_bytes,
-                                  void *stream) {
-    return dgrad_impl(dtype, n_frames, h, w, d_gy, gy_stride, c_gy, d_weights, c_dx, d_dx, dx_stride, c_split, d_dx_b,
-                      dx_b_stride, d_ws, ws_bytes, nullptr, stream);
+    if (dtype == SHPL_F32) return conv_launch<float>(pl, a, d_ws, false, false, d_weights, nullptr, nullptr, s, 1);
+    return conv_launch<uint16_t>(pl, a, d_ws, false, false, d_weights, nullptr, nullptr, s, 1);
 }
 
-extern "C" int shpl_conv3x3_dgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy,
-                                        int64_t gy_stride, int64_t c_gy, const void *d_weights, int64_t c_dx,
-                                        void *d_dx, int64_t dx_stride, int64_t c_split, void *d_dx_b,
-                                        int64_t dx_b_stride, void *d_ws, size_t ws_bytes, const shpl_csr *pool,
-                                        const void *d_fwd_ws, size_t fwd_ws_bytes, int fwd_stats, void *stream) {
-    // the forward's occupancy words, where its plan put them: the forward is the conv of [A (c_split) || B pooled
-    // (c_dx - c_split)] to c_gy channels, the plan wgrad_impl's reuse checks too
-    if (!pool || !d_fwd_ws || !d_dx_b) return SHPL_ERR_ARG;
-    if (pool->n_keys != (int64_t)n_frames * h * w || c_split < 1 || c_split >= c_dx) return SHPL_ERR_BAD_SHAPE;
-    ConvPlan fp;
-    int rc = conv_plan(dtype, n_frames, h, w, c_split, c_dx - c_split, c_gy, true, fwd_stats != 0, &fp, 0,
-                       pool->nnz_cap);
-    if (rc) return rc;
-    if (!fp.rows || fwd_ws_bytes < fp.total || c_gy % NCO != 0 ||
-        (fwd_stats != 0 && !rows::supported_st(fp.qa + fp.qb, fp.qa, true)))
-        return SHPL_ERR_ARG;
-    const uint32_t *occ = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(d_fwd_ws) + fp.wp_bytes +
-                                                             fp.rp_bytes + fp.part_bytes);
-    return dgrad_impl(dtype, n_frames, h, w, d_gy, gy_stride, c_gy, d_weights, c_dx, d_dx, dx_stride, c_split, d_dx_b,
-                      dx_b_stride, d_ws, ws_bytes, occ, stream);
-}
-
-namespace {
+// ---------------------------------------------------------------- host: weight gradient
 struct WgPlan {
     ConvPlan cp;
     int n_cib, n_groups, tiles_per_group;
-    size_t rp_bytes, part_bytes, total;
-    bool rows;  // bf16: k_wgrad_rows when the pointers are 16-byte aligned
+    // the workspace holds either form. The tiled form's regions (byte offsets): row pointers (pooled), partials
+    size_t row_ptr, part, total;
+    // bf16: k_wgrad_rows when the pointers are 16-byte aligned, over its own 60-row bands. Its regions: the
+    // groups' partials, their f64 sums, the pooled operand (pooled; unused when a forward lends its own)
+    bool rows;
+    RowGeom g;
     int r_groups;
-    size_t r_part_bytes, r_part2_bytes, r_occ_bytes, r_cmp_bytes;
+    size_t r_part, r_part2;
+    PooledAt r_pooled;
 };
 
 int wgrad_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b, int64_t c_out, bool pooled,
@@ -2153,31 +1567,209 @@ int wgrad_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64
     if (wp->tiles_per_group < 1) wp->tiles_per_group = 1;
     wp->n_groups = (int)((wp->cp.n_tiles + wp->tiles_per_group - 1) / wp->tiles_per_group);
     if (wp->n_groups < 1) wp->n_groups = 1;
-    wp->rp_bytes = wp->cp.rp_bytes;
-    wp->part_bytes = align_up((size_t)wp->n_groups * blocks_per_group * 9 * WG_CI * NCO * sizeof(float), 256);
-    wp->total = wp->rp_bytes + wp->part_bytes;
+    Layout t;
+    wp->row_ptr = t.take(pooled ? (size_t)n_frames * (h + 1) * 4 : 0);
+    wp->part = t.take((size_t)wp->n_groups * blocks_per_group * 9 * WG_CI * NCO * sizeof(float));
+    wp->total = t.end;
     // the row-streaming bf16 weight gradient: bands and strips of the forward's row kernel
-    const int n_bands = (int)((h + 59) / 60);
-    const int64_t n_items = (int64_t)n_frames * n_bands * ((w + TW - 1) / TW);
+    wp->g = row_geom(h, w);
+    const int64_t n_items = (int64_t)n_frames * wp->g.n_bands * wp->g.strips;
     // pooled: B gathered from the compact pooled rows of prep_pooled (the forward's k_occ_frame + k_pool_runs)
-    const int64_t wpr = (w + 31) / 32;
     wp->rows = SHPL_CONV_ROWS && dtype == SHPL_BF16 && h > 0 && w > 0 && n_items > 0 && n_items < (1LL << 31) &&
                rows::wgrad_supported((int)c_a, (int)c_b, (int)c_out) &&
-               (!pooled || (c_a > 0 && c_b <= 64 && h * wpr <= rows::OCC_MAX_WORDS && pool_cap >= 0 &&
+               (!pooled || (c_a > 0 && c_b <= 64 && h * wp->g.wpr <= rows::OCC_MAX_WORDS && pool_cap >= 0 &&
                             pool_cap * c_b * 2 < (1LL << 31)));
     if (wp->rows) {
-        rows::wgrad_sizes((int)n_items, (int)c_a, (int)c_b, (int)c_out, &wp->r_groups, &wp->r_part_bytes,
-                          &wp->r_part2_bytes);
-        wp->r_part_bytes = align_up(wp->r_part_bytes, 256);
-        wp->r_part2_bytes = align_up(wp->r_part2_bytes, 256);
-        wp->r_occ_bytes = pooled ? 2 * align_up((size_t)n_frames * h * wpr * 4, 256) : 0;
-        wp->r_cmp_bytes = pooled ? align_up((size_t)pool_cap * c_b * 2, 256) : 0;
-        const size_t rt = wp->r_part_bytes + wp->r_part2_bytes + wp->r_occ_bytes + wp->r_cmp_bytes;
-        if (rt > wp->total) wp->total = rt;
+        size_t part_bytes, part2_bytes;
+        rows::wgrad_sizes((int)n_items, (int)c_a, (int)c_b, (int)c_out, &wp->r_groups, &part_bytes, &part2_bytes);
+        Layout r;
+        wp->r_part = r.take(part_bytes);
+        wp->r_part2 = r.take(part2_bytes);
+        wp->r_pooled = pooled_layout(r, pooled, n_frames, h, wp->g.wpr, pool_cap, c_b);
+        if (r.end > wp->total) wp->total = r.end;
     }
     return SHPL_OK;
 }
+
+// shpl_conv3x3_wgrad; d_fwd_ws: the workspace of a pooled bf16 forward shpl_conv3x3 call over the same map
+// (shpl_conv3x3_wgrad_reuse) whose pooled operand the row-streaming form reads instead of preparing its own
+int wgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, const Src &B, const shpl_csr *pool,
+               const int64_t *d_frame_off, const void *d_gy, int64_t gy_stride, int64_t c_out, float *d_dw,
+               void *d_ws, size_t ws_bytes, const void *d_fwd_ws, size_t fwd_ws_bytes, int fwd_stats,
+               void *stream) {
+    const bool pooled = pool != nullptr;
+    WgPlan wp;
+    int rc = wgrad_plan(dtype, n_frames, h, w, A.c, B.c, c_out, pooled, &wp, pooled ? pool->nnz_cap : 0);
+    if (rc) return rc;
+    if (!d_dw || (ws_bytes > 0 && !d_ws)) return SHPL_ERR_ARG;
+    if (ws_bytes < wp.total) return SHPL_ERR_WORKSPACE;
+    rc = check_sources(n_frames, h, w, A, B, pool, d_frame_off, gy_stride, c_out);
+    if (rc) return rc;
+    if ((A.c > 0 && !A.p) || !d_gy) return SHPL_ERR_ARG;
+    const ConvPlan &pl = wp.cp;
+    const int he = dtype == SHPL_F32 ? 4 : 8;
+    const bool vec_g = vec16({d_gy, gy_stride, 0, c_out}, he);
+    hipStream_t s = (hipStream_t)stream;
+    if (pl.n_tiles == 0) {  // no pixels: dW = 0
+        SHPL_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 9 * (size_t)(A.c + B.c) * c_out, s));
+        return SHPL_OK;
+    }
+    if (wp.rows && (A.c == 0 || vec16(A, he)) && (B.c == 0 || vec16(B, he)) && vec_g &&
+        (!pooled || A.c % 32 == 0)) {
+        rows::WgRowArgs r = {};
+        r.a = reinterpret_cast<const uint16_t *>(A.p) + A.off;
+        r.b = B.c > 0 ? reinterpret_cast<const uint16_t *>(B.p) + B.off : nullptr;
+        r.a_stride = A.stride;
+        r.b_stride = B.stride;
+        r.c_a = (int)A.c;
+        r.c_b = (int)B.c;
+        r.gy = reinterpret_cast<const uint16_t *>(d_gy);
+        r.gy_stride = gy_stride;
+        r.c_out = (int)c_out;
+        r.h = (int)h;
+        r.w = (int)w;
+        r.strips = wp.g.strips;
+        r.n_bands = wp.g.n_bands;
+        r.band = wp.g.band;
+        r.n_items = n_frames * r.n_bands * r.strips;
+        r.n_cit = (int)((A.c + 31) / 32 + (B.c + 31) / 32);
+        r.n_cot = (int)((c_out + 31) / 32);
+        r.n_groups = wp.r_groups;
+        r.part = region<float>(d_ws, wp.r_part);
+        if (pooled) {
+            // the forward call's occupancy maps and pooled runs when it lends them (what is checkable of that and
+            // fails is an error, not a fallback); otherwise this call's own, by the forward's prep
+            Pooled po = pooled_in(d_ws, wp.r_pooled);
+            if (d_fwd_ws) {
+                if (forward_pooled(dtype, n_frames, h, w, A.c, B.c, c_out, pool->nnz_cap, fwd_stats, d_fwd_ws,
+                                   fwd_ws_bytes, &po) != SHPL_OK)
+                    return SHPL_ERR_ARG;
+            } else {
+                rc = rows::prep_pooled(n_frames, (int)h, (int)w, wp.g.wpr, pool->ent_dst, pool->ent_src,
+                                       pool->ent_val, pool->nnz_cap, d_frame_off,
+                                       reinterpret_cast<const uint16_t *>(B.p), B.stride, B.off, (int)B.c, po.occ,
+                                       po.occ_base, po.cmp, s);
+                if (rc) return rc;
+            }
+            r.b = nullptr;
+            r.cmp = po.cmp;
+            r.cmp_stride = (int)B.c;
+            r.occ = po.occ;
+            r.occ_base = po.occ_base;
+            r.wpr = wp.g.wpr;
+            r.frame_off = d_frame_off;
+        }
+        return rows::wgrad_launch(r, d_dw, region<double>(d_ws, wp.r_part2), s);
+    }
+    ConvArgs a = conv_args(dtype, n_frames, h, w, pl, A, B, pool);
+    a.row_ptr = pooled ? region<int32_t>(d_ws, wp.row_ptr) : nullptr;
+    a.c_out = (int)c_out;
+    WgArgs g = {};
+    g.gy = d_gy;
+    g.gy_stride = gy_stride;
+    g.n_cib = wp.n_cib;
+    g.n_cob = pl.n_cob;
+    g.tiles_per_group = wp.tiles_per_group;
+    g.vec_g = vec_g;
+    g.whole = (A.c == 0 || (a.vec_a && A.c % pl.ck == 0)) && (B.c == 0 || (a.vec_b && B.c % pl.ck == 0)) &&
+              g.vec_g && c_out % NCO == 0;
+    g.part = region<float>(d_ws, wp.part);
+    if (pooled) {
+        hipLaunchKernelGGL(k_row_ptr, dim3(16, n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, d_frame_off, a.h, a.w,
+                           const_cast<int32_t *>(a.row_ptr));
+        SHPL_LAUNCH_CHECK();
+    }
+    const dim3 grid((unsigned)wp.n_groups, (unsigned)wp.n_cib, (unsigned)pl.n_cob);
+    const auto kernel = dtype == SHPL_F32 ? (pooled ? k_conv3x3_wgrad<float, true> : k_conv3x3_wgrad<float, false>)
+                        : pooled          ? k_conv3x3_wgrad<uint16_t, true>
+                                          : k_wgrad_bf16;
+    hipLaunchKernelGGL(kernel, grid, dim3(CONV_BLOCK), 0, s, a, g);
+    SHPL_LAUNCH_CHECK();
+    const int64_t n_out = 9 * (A.c + B.c) * c_out;
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3(grid_for(n_out, WR_OUT, 4096)), dim3(SHPL_BLOCK), 0, s, g.part,
+                       wp.n_groups, wp.n_cib, pl.n_cob, (int)A.c, (int)B.c, pl.qa, pl.ck, (int)c_out, d_dw);
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
+
 }  // namespace
+}  // namespace shpl
+
+using namespace shpl;
+
+// ---------------------------------------------------------------- the C ABI (include/shpl.h)
+extern "C" int shpl_conv3x3_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b,
+                                            int64_t c_out, int64_t pool_nnz_cap, int stats, size_t *bytes) {
+    if (!bytes) return SHPL_ERR_ARG;
+    ConvPlan pl;
+    const bool pooled = pool_nnz_cap >= 0;
+    const int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, stats != 0, &pl, 0,
+                             pooled ? pool_nnz_cap : 0);
+    if (rc) return rc;
+    *bytes = pl.total;
+    return SHPL_OK;
+}
+
+extern "C" int shpl_conv3x3(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
+                            int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off,
+                            int64_t c_b, const shpl_csr *pool, const int64_t *d_frame_off, const void *d_weights,
+                            int64_t c_out, const float *d_center, const float *d_scale, const float *d_shift,
+                            int act, void *d_out, int64_t out_stride, double *d_stats, void *d_ws, size_t ws_bytes,
+                            void *stream) {
+    const bool pooled = pool != nullptr, stats = d_stats != nullptr;
+    ConvPlan pl;
+    ConvArgs a;
+    bool empty;
+    const int rc = forward_setup(dtype, n_frames, h, w, {d_a, a_stride, a_off, c_a}, {d_b, b_stride, b_off, c_b}, pool,
+                                 d_frame_off, d_weights, c_out, d_center, d_scale, d_shift, act, d_out, out_stride,
+                                 stats, d_ws, ws_bytes, true, pl, a, &empty);
+    if (rc || empty) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SHPL_F32) return conv_launch<float>(pl, a, d_ws, pooled, stats, d_weights, d_frame_off, d_stats, s);
+    return conv_launch<uint16_t>(pl, a, d_ws, pooled, stats, d_weights, d_frame_off, d_stats, s, 0, pool);
+}
+
+extern "C" int shpl_conv3x3_rows_form(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a,
+                                      int64_t a_stride, int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride,
+                                      int64_t b_off, int64_t c_b, const shpl_csr *pool, const int64_t *d_frame_off,
+                                      const void *d_weights, int64_t c_out, int act, const void *d_out,
+                                      int64_t out_stride, int stats, int *rows_form) {
+    if (!rows_form) return SHPL_ERR_ARG;
+    *rows_form = 0;
+    ConvPlan pl;
+    ConvArgs a;
+    bool empty;
+    const int rc = forward_setup(dtype, n_frames, h, w, {d_a, a_stride, a_off, c_a}, {d_b, b_stride, b_off, c_b}, pool,
+                                 d_frame_off, d_weights, c_out, nullptr, nullptr, nullptr, act,
+                                 const_cast<void *>(d_out), out_stride, stats != 0, nullptr, 0, false, pl, a, &empty);
+    if (rc) return rc;
+    *rows_form = !empty && dtype == SHPL_BF16 && rows_forward(pl, a, pool != nullptr, stats != 0);
+    return SHPL_OK;
+}
+
+extern "C" int shpl_conv3x3_dgrad(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, int64_t gy_stride,
+                                  int64_t c_gy, const void *d_weights, int64_t c_dx, void *d_dx, int64_t dx_stride,
+                                  int64_t c_split, void *d_dx_b, int64_t dx_b_stride, void *d_ws, size_t ws_bytes,
+                                  void *stream) {
+    return dgrad_impl(dtype, n_frames, h, w, d_gy, gy_stride, c_gy, d_weights, c_dx, d_dx, dx_stride, c_split, d_dx_b,
+                      dx_b_stride, d_ws, ws_bytes, nullptr, stream);
+}
+
+extern "C" int shpl_conv3x3_dgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy,
+                                        int64_t gy_stride, int64_t c_gy, const void *d_weights, int64_t c_dx,
+                                        void *d_dx, int64_t dx_stride, int64_t c_split, void *d_dx_b,
+                                        int64_t dx_b_stride, void *d_ws, size_t ws_bytes, const shpl_csr *pool,
+                                        const void *d_fwd_ws, size_t fwd_ws_bytes, int fwd_stats, void *stream) {
+    // the forward is the conv of [A (c_split) || B pooled (c_dx - c_split)] to c_gy channels
+    if (!pool || !d_fwd_ws || !d_dx_b) return SHPL_ERR_ARG;
+    if (pool->n_keys != (int64_t)n_frames * h * w || c_split < 1 || c_split >= c_dx) return SHPL_ERR_BAD_SHAPE;
+    Pooled po;
+    const int rc = forward_pooled(dtype, n_frames, h, w, c_split, c_dx - c_split, c_gy, pool->nnz_cap, fwd_stats,
+                                  d_fwd_ws, fwd_ws_bytes, &po);
+    if (rc) return rc;
+    return dgrad_impl(dtype, n_frames, h, w, d_gy, gy_stride, c_gy, d_weights, c_dx, d_dx, dx_stride, c_split, d_dx_b,
+                      dx_b_stride, d_ws, ws_bytes, po.occ, stream);
+}
 
 extern "C" int shpl_conv3x3_wgrad_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a,
                                                   int64_t c_b, int64_t c_out, int64_t pool_nnz_cap, size_t *bytes) {
@@ -2190,167 +1782,13 @@ extern "C" int shpl_conv3x3_wgrad_workspace_bytes(int dtype, int n_frames, int64
     return SHPL_OK;
 }
 
-namespace {
-// shpl_conv3x3_wgrad; d_fwd_ws: the workspace of a pooled bf16 forward shpl_conv3x3 call over the same map
-// (shpl_conv3x3_wgrad_reuse) whose pooled operand the row-streaming form reads instead of preparing its own
-int wgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride, int64_t a_off,
-               int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, const shpl_csr *pool,
-               const int64_t *d_frame_off, const void *d_gy, int64_t gy_stride, int64_t c_out, float *d_dw,
-               void *d_ws, size_t ws_bytes, const void *d_fwd_ws, size_t fwd_ws_bytes, int fwd_stats,
-               void *stream) {
-    const bool pooled = pool != nullptr;
-    WgPlan wp;
-    int rc = wgrad_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, &wp, pooled ? pool->nnz_cap : 0);
-    if (rc) return rc;
-    if (!d_dw || (ws_bytes > 0 && !d_ws)) return SHPL_ERR_ARG;
-    if (ws_bytes < wp.total) return SHPL_ERR_WORKSPACE;
-    if (a_stride < a_off + c_a || a_off < 0 || b_off < 0 || gy_stride < c_out) return SHPL_ERR_BAD_SHAPE;
-    if (c_b > 0 && b_stride < b_off + c_b) return SHPL_ERR_BAD_SHAPE;
-    if (pooled) {
-        if (!d_frame_off || c_b < 1 || !d_b) return SHPL_ERR_ARG;
-        if (pool->n_keys != (int64_t)n_frames * h * w) return SHPL_ERR_BAD_SHAPE;
-        if (pool->nnz_cap > 0 && (!pool->ent_dst || !pool->ent_src || !pool->ent_val)) return SHPL_ERR_ARG;
-    } else if (c_b > 0 && !d_b) {
-        return SHPL_ERR_ARG;
-    }
-    if ((c_a > 0 && !d_a) || !d_gy) return SHPL_ERR_ARG;
-    const ConvPlan &pl = wp.cp;
-    const int esz = dtype == SHPL_F32 ? 4 : 2, he = 16 / esz;
-    hipStream_t s = (hipStream_t)stream;
-    if (pl.n_tiles == 0) {  // no pixels: dW = 0
-        SHPL_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 9 * (size_t)(c_a + c_b) * c_out, s));
-        return SHPL_OK;
-    }
-    if (wp.rows && (c_a == 0 || (aligned16(d_a) && a_stride % he == 0 && a_off % he == 0)) &&
-        (c_b == 0 || (aligned16(d_b) && b_stride % he == 0 && b_off % he == 0)) && aligned16(d_gy) &&
-        gy_stride % he == 0 && (!pooled || c_a % 32 == 0)) {
-        rows::WgRowArgs r = {};
-        r.a = reinterpret_cast<const uint16_t *>(d_a) + a_off;
-        r.b = c_b > 0 ? reinterpret_cast<const uint16_t *>(d_b) + b_off : nullptr;
-        r.a_stride = a_stride;
-        r.b_stride = b_stride;
-        r.c_a = (int)c_a;
-        r.c_b = (int)c_b;
-        r.gy = reinterpret_cast<const uint16_t *>(d_gy);
-        r.gy_stride = gy_stride;
-        r.c_out = (int)c_out;
-        r.h = (int)h;
-        r.w = (int)w;
-        r.strips = (int)((w + TW - 1) / TW);
-        r.n_bands = (int)((h + 59) / 60);
-        r.band = (int)((h + r.n_bands - 1) / r.n_bands);
-        r.n_items = n_frames * r.n_bands * r.strips;
-        r.n_cit = (int)((c_a + 31) / 32 + (c_b + 31) / 32);
-        r.n_cot = (int)((c_out + 31) / 32);
-        r.n_groups = wp.r_groups;
-        uint8_t *ws = reinterpret_cast<uint8_t *>(d_ws);
-        r.part = reinterpret_cast<float *>(ws);
-        if (pooled) {  // the pooled vector of every run once into the compact buffer (the forward's prep)
-            uint8_t *po = ws + wp.r_part_bytes + wp.r_part2_bytes;
-            uint32_t *occ = reinterpret_cast<uint32_t *>(po);
-            int32_t *occ_base = reinterpret_cast<int32_t *>(po + wp.r_occ_bytes / 2);
-            uint16_t *cmp = reinterpret_cast<uint16_t *>(po + wp.r_occ_bytes);
-            const int wpr = (int)((w + 31) / 32);
-            // the forward call's occupancy maps and pooled runs, where its plan put them (when it has them)
-            ConvPlan fp;
-            const bool reuse = d_fwd_ws &&
-                               conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, true, fwd_stats != 0, &fp, 0,
-                                         pool->nnz_cap) == SHPL_OK &&
-                               fp.rows && fwd_ws_bytes >= fp.total && fp.wpr == wpr && c_out % NCO == 0 &&
-                               (fwd_stats == 0 || rows::supported_st(fp.qa + fp.qb, fp.qa, true));
-            // the rest of rows_forward (the forward's act and output alignment) is the caller's to establish
-            // with shpl_conv3x3_rows_form (shpl.h); what is checkable here and fails is an error, not a fallback
-            if (d_fwd_ws && !reuse) return SHPL_ERR_ARG;
-            if (reuse) {
-                uint8_t *fo = reinterpret_cast<uint8_t *>(const_cast<void *>(d_fwd_ws)) + fp.wp_bytes + fp.rp_bytes +
-                              fp.part_bytes;
-                occ = reinterpret_cast<uint32_t *>(fo);
-                occ_base = reinterpret_cast<int32_t *>(fo + fp.occ_bytes / 2);
-                cmp = reinterpret_cast<uint16_t *>(fo + fp.occ_bytes);
-            } else {
-                rc = rows::prep_pooled(n_frames, (int)h, (int)w, wpr, pool->ent_dst, pool->ent_src, pool->ent_val,
-                                       pool->nnz_cap, d_frame_off, reinterpret_cast<const uint16_t *>(d_b), b_stride,
-                                       b_off, (int)c_b, occ, occ_base, cmp, s);
-                if (rc) return rc;
-            }
-            r.b = nullptr;
-            r.cmp = cmp;
-            r.cmp_stride = (int)c_b;
-            r.occ = occ;
-            r.occ_base = occ_base;
-            r.wpr = wpr;
-            r.frame_off = d_frame_off;
-        }
-        return rows::wgrad_launch(r, d_dw, reinterpret_cast<double *>(ws + wp.r_part_bytes), s);
-    }
-    ConvArgs a = {};
-    a.n_frames = n_frames;
-    a.h = (int)h;
-    a.w = (int)w;
-    a.tiles_x = pl.tiles_x;
-    a.tiles_per_frame = pl.tiles_per_frame;
-    a.n_tiles = (int)pl.n_tiles;
-    a.a = d_a;
-    a.a_stride = a_stride;
-    a.a_off = a_off;
-    a.c_a = (int)c_a;
-    a.qa = pl.qa;
-    a.b = d_b;
-    a.b_stride = b_stride;
-    a.b_off = b_off;
-    a.c_b = (int)c_b;
-    a.qb = pl.qb;
-    a.vec_a = aligned16(d_a) && a_stride % he == 0 && a_off % he == 0;
-    a.vec_b = aligned16(d_b) && b_stride % he == 0 && b_off % he == 0;
-    a.ent_dst = pooled ? pool->ent_dst : nullptr;
-    a.ent_src = pooled ? pool->ent_src : nullptr;
-    a.ent_val = pooled ? pool->ent_val : nullptr;
-    uint8_t *ws = reinterpret_cast<uint8_t *>(d_ws);
-    a.row_ptr = pooled ? reinterpret_cast<const int32_t *>(ws) : nullptr;
-    a.c_out = (int)c_out;
-    WgArgs g = {};
-    g.gy = d_gy;
-    g.gy_stride = gy_stride;
-    g.n_cib = wp.n_cib;
-    g.n_cob = pl.n_cob;
-    g.tiles_per_group = wp.tiles_per_group;
-    g.vec_g = aligned16(d_gy) && gy_stride % he == 0;
-    g.whole = (c_a == 0 || (a.vec_a && c_a % pl.ck == 0)) && (c_b == 0 || (a.vec_b && c_b % pl.ck == 0)) &&
-              g.vec_g && c_out % NCO == 0;
-    g.part = reinterpret_cast<float *>(ws + wp.rp_bytes);
-    if (pooled) {
-        hipLaunchKernelGGL(k_row_ptr, dim3(16, n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, d_frame_off, a.h, a.w,
-                           const_cast<int32_t *>(a.row_ptr));
-        SHPL_LAUNCH_CHECK();
-    }
-    const dim3 grid((unsigned)wp.n_groups, (unsigned)wp.n_cib, (unsigned)pl.n_cob);
-    if (dtype == SHPL_F32) {
-        if (pooled)
-            hipLaunchKernelGGL((k_conv3x3_wgrad<float, true>), grid, dim3(CONV_BLOCK), 0, s, a, g);
-        else
-            hipLaunchKernelGGL((k_conv3x3_wgrad<float, false>), grid, dim3(CONV_BLOCK), 0, s, a, g);
-    } else {
-        if (pooled)
-            hipLaunchKernelGGL((k_conv3x3_wgrad<uint16_t, true>), grid, dim3(CONV_BLOCK), 0, s, a, g);
-        else
-            hipLaunchKernelGGL(k_wgrad_bf16, grid, dim3(CONV_BLOCK), 0, s, a, g);
-    }
-    SHPL_LAUNCH_CHECK();
-    const int64_t n_out = 9 * (c_a + c_b) * c_out;
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3(grid_for(n_out, WR_OUT, 4096)), dim3(SHPL_BLOCK), 0, s, g.part,
-                       wp.n_groups, wp.n_cib, pl.n_cob, (int)c_a, (int)c_b, pl.qa, pl.ck, (int)c_out, d_dw);
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
-}
-}  // namespace
-
 extern "C" int shpl_conv3x3_wgrad(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
                                   int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off,
                                   int64_t c_b, const shpl_csr *pool, const int64_t *d_frame_off, const void *d_gy,
                                   int64_t gy_stride, int64_t c_out, float *d_dw, void *d_ws, size_t ws_bytes,
                                   void *stream) {
-    return wgrad_impl(dtype, n_frames, h, w, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, pool, d_frame_off,
-                      d_gy, gy_stride, c_out, d_dw, d_ws, ws_bytes, nullptr, 0, 0, stream);
+    return wgrad_impl(dtype, n_frames, h, w, {d_a, a_stride, a_off, c_a}, {d_b, b_stride, b_off, c_b}, pool,
+                      d_frame_off, d_gy, gy_stride, c_out, d_dw, d_ws, ws_bytes, nullptr, 0, 0, stream);
 }
 
 extern "C" int shpl_conv3x3_wgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a,
@@ -2360,6 +1798,7 @@ extern "C" int shpl_conv3x3_wgrad_reuse(int dtype, int n_frames, int64_t h, int6
                                         int64_t c_out, float *d_dw, void *d_ws, size_t ws_bytes,
                                         const void *d_fwd_ws, size_t fwd_ws_bytes, int fwd_stats, void *stream) {
     if (!pool || !d_fwd_ws || dtype != SHPL_BF16) return SHPL_ERR_ARG;
-    return wgrad_impl(dtype, n_frames, h, w, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, pool, d_frame_off,
-                      d_gy, gy_stride, c_out, d_dw, d_ws, ws_bytes, d_fwd_ws, fwd_ws_bytes, fwd_stats, stream);
+    return wgrad_impl(dtype, n_frames, h, w, {d_a, a_stride, a_off, c_a}, {d_b, b_stride, b_off, c_b}, pool,
+                      d_frame_off, d_gy, gy_stride, c_out, d_dw, d_ws, ws_bytes, d_fwd_ws, fwd_ws_bytes, fwd_stats,
+                      stream);
 }

@@ -1,5 +1,5 @@
-// shpl_conv_rows.h -- the row-streaming bf16 conv (shpl_conv_rows.hip) as the
-// tiled conv's host code (shpl_conv.hip) launches it.
+// shpl_conv_rows.h -- the row-streaming bf16 conv (shpl_conv_rows.hip) as the conv's host code launches it:
+// the plans, launches and C ABI in shpl_conv.hip (the pieces shared with shpl_bn.hip: shpl_conv_bn.h).
 #pragma once
 
 #include "shpl_common.h"

@@ -1,5 +1,5 @@
 // shpl_conv_wide.h -- the bf16 3x3 conv for wide channel counts (shpl_conv_wide.hip) as the conv's host
-// code (shpl_conv.hip) launches it.
+// code launches it: conv_plan lays out its workspace, conv_wide_launch fills WideArgs (shpl_conv.hip).
 #pragma once
 
 #include "shpl_common.h"

@@ -8,7 +8,7 @@ host in double with count = rows, so nothing of the conv is in the comparison.
 bf16 inputs are rounded through the oracle's bf16 first: device and oracle read
 the same values.
 
-Which kernel runs is decided by the `vform` predicate of csrc/shpl_conv.hip,
+Which kernel runs is decided by `bn_vector_form` of csrc/shpl_bn.hip,
 restated in vform() below: the 16-byte vector kernels need c a multiple of
 VEC (4 f32 / 8 bf16 elements), stride a multiple of VEC, c / VEC a power of
 two of at most SHPL_BLOCK = 256, and every map 16-byte aligned. Every entry

@@ -274,6 +274,39 @@ def test_fused_conv_noncanonical_map():
     _assert_within(fused, orc.conv3x3(x, wts), _bound(x, wts))
 
 
+def test_bf16_wide_fused_materialised_map():
+    """The pooled wide forward past the occupancy table (h * words per row = 18433 > 18432, the smallest map
+    that gets there): the pooled map is materialised in the workspace's last region by shpl_pull and read as a
+    dense second source. Fused == the conv of [a || shpl_pull(...)], bitwise; bias + ReLU. The workspace
+    holds the whole map, so the call took that form and not the compact pooled runs."""
+    from sparse_pooling_amd import _lib as L, fusion_conv as fc, shpl_map as sm
+    rng = np.random.default_rng(91)
+    n, hb, wb, h, w, cb, ci, cout = 300, 18433, 3, 15, 17, 64, 64, 256
+    R = hb * wb
+    idx = np.stack([np.zeros(n, np.int64), rng.integers(0, h, n), rng.integers(0, w, n)], 1)
+    rows = rng.integers(0, R, n)
+    rows[:6] = [0, 1, 2, R - 3, R - 2, R - 1]  # the first and the last row, every column
+    rows[100:140] = rows[100]                  # one cell with 40 entries
+    extra = np.stack([rng.integers(0, R, 100), rng.integers(0, n, 100)], 1)
+    mij = np.concatenate([np.stack([rows, np.arange(n)], 1), extra]).astype(np.int64)
+    mij = mij[rng.permutation(len(mij))]
+    mval = rng.uniform(-2, 2, len(mij)).astype(np.float32)
+    img = _bf16(rng.standard_normal((1, h, w, ci)).astype(np.float32))
+    bev = _bf16(rng.standard_normal((1, hb, wb, cb)).astype(np.float32))
+    smap = sm.pack_map(_t(mij), _t(mval), [R, n], _t(idx), img.shape)
+    pool = smap.csr(0, 0)
+    assert (fc.conv_ws_bytes(L.BF16, 1, hb, wb, cb, ci, cout, pool.nnz_cap, False) -
+            fc.conv_ws_bytes(L.BF16, 1, hb, wb, cb, ci, cout, None, False)) >= R * ci * 2
+    wts = _bf16(_weights(cb + ci, cout, 92))
+    bias = _t(np.random.default_rng(93).standard_normal(cout).astype(np.float32) * 0.5)
+    fused = fc.conv3x3(bev, wts, b=img, pool=pool, frame_off=smap.frame_off, shift=bias, relu=True)
+    bv = sm.pool_img_to_bev(smap, img, (1, hb, wb, cb), bev=bev)
+    assert bool((bv[..., cb:] != 0).any())
+    unf = fc.conv3x3(bv[..., :cb].contiguous(), wts, b=bv[..., cb:].contiguous(), shift=bias, relu=True)
+    torch.cuda.synchronize()
+    assert torch.equal(fused, unf)
+
+
 def test_fused_conv_empty_map():
     from sparse_pooling_amd import fusion_conv as fc, shpl_map as sm
     bev = synth.make_features((1, 6, 7, 8), 2)
