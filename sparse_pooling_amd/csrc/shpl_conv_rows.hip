@@ -51,83 +51,89 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
-#ifndef SHPL_ROWS_M16
-// 1: even chunk counts multiply with v_mfma_f32_16x16x32_bf16 (K = 32 input channels, the block's 32 output
-// channels as two halves of 16, the row's 32 pixels as two halves of 16) instead of 32x32x16 -- the same
-// cycles per FLOP; under the chip's load-dependent clock the 16x16 shape has measured more FLOP/s
-// (MI355X_MICROARCH.md, DVFS item 7)
-#define SHPL_ROWS_M16 1
-#endif
-#ifndef SHPL_ROWS_M16_ST
-#define SHPL_ROWS_M16_ST 1  // the statistics forms too (pooled: one operand read ahead of the MFMAs)
-#endif
-#ifndef SHPL_ROWS_STREG
-// 1: the 16x16 statistics forms sum each row straight from the accumulators (a lane's two pixels, then one
-// DPP exchange across lane ^ 8) into per-lane band sums in LDS, reduced over the pixel lanes once per band;
-// 2: the same with the band sums in 8 registers (training forward 1,287-1,313 -> 1,271-1,278 us,
-// profiles/r04_streg2_ab.log); 0: each row's f32 accumulators through a transpose in the ring slot (the
-// 32x32 forms always do)
-#define SHPL_ROWS_STREG 2
-#endif
 constexpr int NCO = 32;           // output channels per wave
 constexpr int TW = 32;            // strip width (output pixels)
 constexpr int HWD = TW + 2;       // halo row (pixels)
 constexpr int W_ROWS = 9 * NCO;   // packed weight rows of a chunk
 constexpr int RING = 3;           // ring slots per wave = the row loop's unroll (accumulator roles)
 constexpr int REPI = NCO * 2 + 16;  // epilogue transpose pitch (bytes per pixel)
-#ifndef SHPL_ROWS_XCD
-#define SHPL_ROWS_XCD 1  // XCD-contiguous item order (0: blockIdx order)
-#endif
-#ifndef SHPL_ROWS_EPI8
-#define SHPL_ROWS_EPI8 0  // 1: 8-byte stores straight from the accumulators (4 per lane and row), no LDS transpose: correct
-                          // with RSTORES = 4, measured 1.2-1.6x slower (profiles/r04_epi_ab.log)
-#endif
-#ifndef SHPL_ROWS_DEAD3
-#define SHPL_ROWS_DEAD3 0  // 1: masked input-gradient waves skip three dead rows' MFMAs (A/B: within noise, profiles/r06_ab/dead3_*)
-#endif
-#ifndef SHPL_ROWS_NTSTORE
-#define SHPL_ROWS_NTSTORE 1  // the epilogue's stores nontemporal (0: plain stores, A/B)
-#endif
-#ifndef SHPL_ROWS_RSTORES
-#define SHPL_ROWS_RSTORES (SHPL_ROWS_EPI8 ? 4 : 2)
-#endif
-constexpr int RSTORES = SHPL_ROWS_RSTORES;  // output stores per row step, always issued (the vmcnt arithmetic)
+constexpr int RSTORES = 2;        // output stores per row step, always issued (the vmcnt arithmetic)
 constexpr uint32_t OOB = 0x80000000u;  // an offset past every descriptor's num_records: reads zeros
+constexpr int SPF = NCO + 4;      // ST: f32 transpose pitch (floats per pixel; 16-byte rows, conflict-free b64 reads)
+
+// The build switches that remain (the settled A/B switches of earlier rounds are gone: docs/HISTORY.md).
 #ifndef SHPL_ROWS_PROBE
-// timing probes of k_conv_rows: 1 no epilogue, 2 no in-loop DMAs (wrong results); 3 s_memtime stamps of each
-// row step's phases (ring wait, operand reads + MFMA issue, epilogue, staging) summed per wave into g_cprobe
-// (shpl_probe_conv_phases reads them; the stamps' lgkmcnt(0) waits cost a few % of the loop)
+// Stays: the timing probes of k_conv_rows, built by scripts/conv_phases.py. 1 no epilogue, 2 no in-loop DMAs
+// (wrong results); 3 s_memtime stamps of each row step's phases (ring wait, operand reads + MFMA issue,
+// epilogue, staging) summed per wave into g_cprobe (shpl_probe_conv_phases reads them; the stamps'
+// lgkmcnt(0) waits cost a few % of the loop)
 #define SHPL_ROWS_PROBE 0
 #endif
+#ifndef SHPL_ROWS_WLATE
+// Stays: a negative control of tests/test_isa_guard.py. 1: no wait for the weights before the loop (the round-3
+// form, whose ring the compiler's waits drain)
+#define SHPL_ROWS_WLATE 0
+#endif
+#ifndef SHPL_ROWS_WPE
+// Stays: a negative control of tests/test_isa_guard.py, which forces 4 (spills). Waves per SIMD of the row kernels
+#define SHPL_ROWS_WPE 2
+#endif
+
+// Probe 3's stamps: one macro per stamp, nothing in product builds (as SHPL_IDX1_STAMP, shpl_compact.h).
+// SHPL_PH_STAMP(k) in step() ends phase k - 1 (0: only starts the clock) and adds its cycles to the wave's
+// sums `ph`, which reach step() through SHPL_PH_PARAM / SHPL_PH_ARG; SHPL_KSTAMP(t) / SHPL_RSTAMP(t) declare
+// and take one s_memtime / s_memrealtime stamp of the kernel's own.
 #if SHPL_ROWS_PROBE == 3
 constexpr int CPROBE_WAVES = 1 << 17;
 __device__ uint64_t g_cprobe[CPROBE_WAVES * 10];
-#define SHPL_RSTAMP(t) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory")
-#define SHPL_STAMP(t)                                                                  \
-    do {                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                             \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");     \
-        __builtin_amdgcn_sched_barrier(0);                                             \
+struct Phases {
+    uint64_t last, sum[4];  // the step's previous stamp; ring wait, operand reads + MFMA issue, epilogue, staging
+};
+#define SHPL_RSTAMP(t) \
+    uint64_t t;        \
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory")
+#define SHPL_KSTAMP(t)                                                             \
+    uint64_t t;                                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                             \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");     \
+    __builtin_amdgcn_sched_barrier(0)
+#define SHPL_PH_STAMP(k)                                   \
+    do {                                                   \
+        SHPL_KSTAMP(t_);                                   \
+        if ((k) > 0) ph.sum[((k) + 3) % 4] += t_ - ph.last; \
+        ph.last = t_;                                      \
     } while (0)
-#endif
-constexpr int SPF = NCO + 4;      // ST: f32 transpose pitch (floats per pixel; 16-byte rows, conflict-free b64 reads)
-#ifndef SHPL_ROWS_WLATE
-#define SHPL_ROWS_WLATE 0  // 1: no wait for the weights before the loop (the round-3 form, A/B)
-#endif
-#ifndef SHPL_ROWS_WPE
-#define SHPL_ROWS_WPE 2  // waves per SIMD of the row kernels (tests/test_isa_guard.py forces 4: spills)
+#define SHPL_PH_PARAM , Phases &ph
+#define SHPL_PH_ARG , ph
+#else
+#define SHPL_RSTAMP(t) \
+    do {               \
+    } while (0)
+#define SHPL_KSTAMP(t) \
+    do {               \
+    } while (0)
+#define SHPL_PH_STAMP(k) \
+    do {                 \
+    } while (0)
+#define SHPL_PH_PARAM
+#define SHPL_PH_ARG
 #endif
 
-// The 16x16x32 shape: even chunk counts without statistics (the statistics forms keep 32x32x16: at 4 chunks
-// pooled they would spill). Independent of the A / B split and of pooling, so that those forms stay bitwise
-// equal to each other.
-template <int Q, bool ST>
-constexpr bool m16() { return SHPL_ROWS_M16 && Q % 2 == 0 && (SHPL_ROWS_M16_ST || !ST); }
+// The 16x16x32 shape: even chunk counts multiply with v_mfma_f32_16x16x32_bf16 (K = 32 input channels, the
+// block's 32 output channels as two halves of 16, the row's 32 pixels as two halves of 16) instead of 32x32x16 --
+// the same cycles per FLOP; under the chip's load-dependent clock the 16x16 shape has measured more FLOP/s
+// (MI355X_MICROARCH.md, DVFS item 7). With and without statistics (the pooled statistics forms hold one
+// operand read ahead of the MFMAs, for registers). Independent of the A / B split and of pooling, so that
+// those forms stay bitwise equal to each other.
+template <int Q>
+constexpr bool m16() { return Q % 2 == 0; }
 
-// The statistics forms that sum from the accumulators (SHPL_ROWS_STREG): the 16x16 ones but the dense 1 + 3
-// chunk form (its registers spill)
+// The statistics forms that sum each row straight from the accumulators (a lane's two pixels, then one DPP
+// exchange across lane ^ 8) into per-lane band sums in 8 registers, reduced over the pixel lanes once per band:
+// the 16x16 ones but the dense 1 + 3 chunk form (its registers spill). The other statistics forms pass each
+// row's f32 accumulators through a transpose in the ring slot and keep their band sums in LDS.
 template <int Q, int QA, bool CMP, bool ST>
-constexpr bool streg() { return SHPL_ROWS_STREG && ST && m16<Q, ST>() && !(Q == 4 && QA == 1 && !CMP); }
+constexpr bool streg() { return ST && m16<Q>() && !(Q == 4 && QA == 1 && !CMP); }
 
 // v of lane i ^ 8 inside each row of 16 lanes (DPP row_ror:8, no LDS)
 __device__ __forceinline__ float lane_xor8(float v) {
@@ -149,14 +155,7 @@ __device__ __forceinline__ void set_tile4(f32x16 &a, int t, const f32x4 &v) {
 // stores of the RING-1 later steps -- in flight. expcnt(6) is a no-op in a compute kernel (no exports)
 // that marks the wait as this one, so tests/test_isa_guard.py can find it in the disassembly and
 // check that every path between two of them issues exactly K / (RING-1) vector-memory operations.
-#ifndef SHPL_ROWS_DRAIN
-#define SHPL_ROWS_DRAIN 0  // 1: every ring wait drains (vmcnt(0); probes of the epilogue variants only)
-#endif
-#if SHPL_ROWS_DRAIN
-#define SHPL_RING_WAIT(K) asm volatile("s_waitcnt vmcnt(0) expcnt(6)" ::: "memory")
-#else
 #define SHPL_RING_WAIT(K) asm volatile("s_waitcnt vmcnt(%0) expcnt(6)" ::"n"(K) : "memory")
-#endif
 
 // Forms whose per-lane DMA offsets live in LDS instead of VGPRs (one ds_read_b32 each per row): pooled with
 // statistics, and every 4-chunk form (they would otherwise spill to scratch, whose reloads inside the loop
@@ -371,7 +370,8 @@ __device__ __forceinline__ void stage(const RowArgs &r, int64_t pix0, bool yok, 
 #pragma unroll
         for (int i = 0; i < L::NB; ++i) {
             uint32_t o = (uint32_t)offb[i];
-            if constexpr (CMP) {
+            if constexpr (CMP) {  // the pooled piece's run and offset: the same arithmetic as in wstage (a shared
+                                  // helper changed the pooled kernels' instruction order; the copies stay)
                 const int px = (offb[i] >> 16) & 63;
                 const bool hit = offb[i] >= 0 && ((occ >> px) & 1);
                 const int rank = first + (int)__popcll(occ & ((1ull << px) - 1));
@@ -382,18 +382,40 @@ __device__ __forceinline__ void stage(const RowArgs &r, int64_t pix0, bool yok, 
     }
 }
 
+// The forms whose out2 stores may be limited to occupied cells (RowArgs::occ2): the input gradient's (dense A,
+// no ReLU, no statistics) of at most 32 gradient channels (the 4-chunk form has no register for the mask: it
+// spills; it writes out2 whole)
+template <int Q, bool CMP, bool RELU, bool ST>
+constexpr bool occ2_form() { return Q <= 2 && !CMP && !RELU && !ST; }
+static_assert(TW == 32, "occ2: one occupancy word per strip row");
+
+// The epilogue's arithmetic on 4 consecutive channels cl .. cl + 3 of one pixel (accumulator elements i0 ..
+// i0 + 3) into two packed bf16 pairs: fma(acc, scale, shift - center * scale) (scale 1 / shift 0 when absent),
+// rounded once to bf16, ReLU as max(bits, 0) on the bf16 bit patterns as signed 16-bit integers (negatives, -0
+// and -NaN -> +0, +NaN kept): the tiled kernel's epilogue, bit for bit (shpl.h).
+template <bool RELU>
+__device__ __forceinline__ void epi_pack4(const f32x16 &a, int i0, const float (*s_par)[NCO], int cl,
+                                          uint32_t (&pk)[2]) {
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) {
+        const float v0 = __builtin_fmaf(a[i0 + k], s_par[0][cl + k], s_par[1][cl + k]);
+        const float v1 = __builtin_fmaf(a[i0 + k + 1], s_par[0][cl + k + 1], s_par[1][cl + k + 1]);
+        uint32_t w = (uint32_t)f32_to_bf16(v0) | ((uint32_t)f32_to_bf16(v1) << 16);
+        if (RELU) {
+            s16x2 h;
+            __builtin_memcpy(&h, &w, 4);
+            h = __builtin_elementwise_max(h, s16x2{0, 0});
+            __builtin_memcpy(&w, &h, 4);
+        }
+        pk[k >> 1] = w;
+    }
+}
+
 // One staged input row j (j % RING == U: its slot and the accumulators'
 // roles) of the band: wait for its slot, 3 kx x Q chunks x 3 ky MFMAs, the
 // epilogue of output row j-2 of the band (always stored: rows and pixels
 // outside the map go to the junk line; its accumulator is cleared), then
 // stage input row j + RING into the slot just read.
-// The forms whose out2 stores may be limited to occupied cells (RowArgs::occ2): the input gradient's (dense A,
-// no ReLU, no statistics) of at most 32 gradient channels (the 4-chunk form has no register for the mask: it
-// spills; it writes out2 whole)
-template <int Q, bool CMP, bool RELU, bool ST>
-constexpr bool occ2_form() { return Q <= 2 && !CMP && !RELU && !ST && !SHPL_ROWS_EPI8; }
-static_assert(TW == 32, "occ2: one occupancy word per strip row");
-
 template <int Q, int QA, bool CMP, bool RELU, bool ST, int U>
 __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9], f32x16 (&acc)[3],
                                      const float (*s_par)[NCO], const uint8_t *rd, uint8_t *s_ring,
@@ -403,24 +425,14 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
                                      const uint32_t (&offa)[Layout<Q, QA>::NA],
                                      const int32_t (&offb)[Layout<Q, QA>::NB > 0 ? Layout<Q, QA>::NB : 1],
                                      const uint32_t *s_offs, const uint32_t (&rdq)[2], int lane,
-                                     f32x4 (&str)[2], uint64_t (&ph)[5], uint32_t m2row, bool m2, uint64_t m2live) {
+                                     f32x4 (&str)[2], uint32_t m2row, bool m2 SHPL_PH_PARAM) {
     typedef Layout<Q, QA, ST> L;
-#if SHPL_ROWS_PROBE == 3
-    uint64_t t0, t1, t2, t3, t4;
-    SHPL_STAMP(t0);
-#endif
+    SHPL_PH_STAMP(0);
     // rows j+1 .. j+RING-1 may still be in flight: per later step RSTORES stores and NDMA DMAs
     SHPL_RING_WAIT((L::NDMA + RSTORES) * (RING - 1));
-#if SHPL_ROWS_PROBE == 3
-    SHPL_STAMP(t1);
-#endif
+    SHPL_PH_STAMP(1);
     f32x16 &a0 = acc[(U + 1) % 3], &a1 = acc[U], &a2 = acc[(U + 2) % 3];
-    // m2: output rows j-2 .. j (the three accumulators' rows) all without an occupied cell -- none of them is
-    // stored, so their MFMAs are skipped (a uniform branch: no memory operation inside)
-    bool dead3 = false;
-    if constexpr (occ2_form<Q, CMP, RELU, ST>()) dead3 = SHPL_ROWS_DEAD3 && m2 && (((m2live << 2) >> j) & 7ull) == 0;
-    if (!dead3) {
-    if constexpr (m16<Q, ST>()) {
+    if constexpr (m16<Q>()) {
         // K-chunk c (32 channels: pieces 4c .. 4c+3, each lane its piece 4c + lane / 16 from A or B), then kx,
         // then the pixel half nb; both output halves h per operand read. A split between A and B and the
         // skipped pooled chunks leave every accumulator's summation order unchanged, as below
@@ -448,38 +460,35 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
                 }
         }
     } else {
-    // chunk-major (q outer): a split of the channels between A and B, and the skipped pooled chunks below,
-    // leave every accumulator's summation order unchanged
+        // chunk-major (q outer): a split of the channels between A and B, and the skipped pooled chunks below,
+        // leave every accumulator's summation order unchanged
 #pragma unroll
-    for (int q = 0; q < QA; ++q) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const bf16x8 xv = *reinterpret_cast<const bf16x8 *>(rd + U * L::SLOT + kx * 16 + 2 * q * HWD * 16);
-            a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][kx], xv, a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][3 + kx], xv, a1, 0, 0, 0);
-            a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][6 + kx], xv, a2, 0, 0, 0);
-        }
-    }
-    // pooled rows without an occupied cell in the window are all zeros: their MFMAs would add exact zeros
-    // to accumulators that are never -0, so skipping them is bitwise the same
-    if (L::QB > 0 && (!CMP || ((b_rows >> j) & 1))) {
-#pragma unroll
-        for (int q = QA; q < Q; ++q) {
+        for (int q = 0; q < QA; ++q) {
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
-                const bf16x8 xv = *reinterpret_cast<const bf16x8 *>(rd + U * L::SLOT + kx * 16 +
-                                                                    (L::RB + 2 * (q - QA) * HWD) * 16);
+                const bf16x8 xv = *reinterpret_cast<const bf16x8 *>(rd + U * L::SLOT + kx * 16 + 2 * q * HWD * 16);
                 a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][kx], xv, a0, 0, 0, 0);
                 a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][3 + kx], xv, a1, 0, 0, 0);
                 a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][6 + kx], xv, a2, 0, 0, 0);
             }
         }
+        // pooled rows without an occupied cell in the window are all zeros: their MFMAs would add exact zeros
+        // to accumulators that are never -0, so skipping them is bitwise the same
+        if (L::QB > 0 && (!CMP || ((b_rows >> j) & 1))) {
+#pragma unroll
+            for (int q = QA; q < Q; ++q) {
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const bf16x8 xv = *reinterpret_cast<const bf16x8 *>(rd + U * L::SLOT + kx * 16 +
+                                                                        (L::RB + 2 * (q - QA) * HWD) * 16);
+                    a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][kx], xv, a0, 0, 0, 0);
+                    a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][3 + kx], xv, a1, 0, 0, 0);
+                    a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[q][6 + kx], xv, a2, 0, 0, 0);
+                }
+            }
+        }
     }
-    }
-    }
-#if SHPL_ROWS_PROBE == 3
-    SHPL_STAMP(t2);
-#endif
+    SHPL_PH_STAMP(2);
     // epilogue of band output row b: acc * scale + (shift - center * scale), ReLU on the bf16 pairs;
     // the lane's 4 runs of 4 channels to rows of the slot just read, then 2 x 16-byte stores per lane
     // (consecutive lanes, consecutive pieces)
@@ -492,74 +501,23 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
         const bool row_ok = b >= 0 && b < n_out;
         uint16_t *orow = obase + (frame_row0 + (int64_t)(ya + b) * r.w + x0) * ostr;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the MFMAs' operand reads of the slot are done
-#if SHPL_ROWS_EPI8
-        // 8-byte stores straight from the accumulators: 4 per lane and row (RSTORES = 4 in the ring's counted
-        // wait; with 2 the wait left two of the next row's DMAs unwaited-for -- the round-2 failure)
-    #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int cl = 8 * g + 4 * hf;
-            uint32_t pk[2];
-    #pragma unroll
-            for (int k = 0; k < 4; k += 2) {
-                const float v0 = __builtin_fmaf(a2[4 * g + k], s_par[0][cl + k], s_par[1][cl + k]);
-                const float v1 = __builtin_fmaf(a2[4 * g + k + 1], s_par[0][cl + k + 1], s_par[1][cl + k + 1]);
-                uint32_t w = (uint32_t)f32_to_bf16(v0) | ((uint32_t)f32_to_bf16(v1) << 16);
-                if (RELU) {
-                    s16x2 h;
-                    __builtin_memcpy(&h, &w, 4);
-                    h = __builtin_elementwise_max(h, s16x2{0, 0});
-                    __builtin_memcpy(&w, &h, 4);
-                }
-                pk[k >> 1] = w;
-            }
-            uint16_t *dst = row_ok && x0 + pl < r.w ? orow + pl * (int)ostr + cl : r.junk + lane * 16 + 4 * g;
-            __builtin_memcpy(dst, pk, sizeof(pk));
-        }
-#else
-        if constexpr (m16<Q, ST>()) {
+        if constexpr (m16<Q>()) {
             // tile t = 2h + nb: the lane's 4 consecutive channels 16h + 4 (lane / 16) .. of pixel 16 nb + lane % 16
-    #pragma unroll
+#pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int cl = 16 * (t >> 1) + 4 * (lane >> 4), px = 16 * (t & 1) + (lane & 15);
                 uint32_t pk[2];
-    #pragma unroll
-                for (int k = 0; k < 4; k += 2) {
-                    const float v0 = __builtin_fmaf(a2[4 * t + k], s_par[0][cl + k], s_par[1][cl + k]);
-                    const float v1 = __builtin_fmaf(a2[4 * t + k + 1], s_par[0][cl + k + 1], s_par[1][cl + k + 1]);
-                    uint32_t w = (uint32_t)f32_to_bf16(v0) | ((uint32_t)f32_to_bf16(v1) << 16);
-                    if (RELU) {
-                        s16x2 hh;
-                        __builtin_memcpy(&hh, &w, 4);
-                        hh = __builtin_elementwise_max(hh, s16x2{0, 0});
-                        __builtin_memcpy(&w, &hh, 4);
-                    }
-                    pk[k >> 1] = w;
-                }
+                epi_pack4<RELU>(a2, 4 * t, s_par, cl, pk);
                 __builtin_memcpy(s_o + px * REPI + cl * 2, pk, sizeof(pk));
             }
         } else {
-    #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int cl = 8 * g + 4 * hf;
-            uint32_t pk[2];
-    #pragma unroll
-            for (int k = 0; k < 4; k += 2) {
-                // fma(acc, scale, shift - center * scale) (scale 1 / shift 0 when absent), rounded to bf16,
-                // ReLU as max(bits, 0) on the bf16 bit patterns as signed 16-bit integers (negatives, -0
-                // and -NaN -> +0, +NaN kept): the tiled kernel's epilogue, bit for bit (shpl.h).
-                const float v0 = __builtin_fmaf(a2[4 * g + k], s_par[0][cl + k], s_par[1][cl + k]);
-                const float v1 = __builtin_fmaf(a2[4 * g + k + 1], s_par[0][cl + k + 1], s_par[1][cl + k + 1]);
-                uint32_t w = (uint32_t)f32_to_bf16(v0) | ((uint32_t)f32_to_bf16(v1) << 16);
-                if (RELU) {
-                    s16x2 h;
-                    __builtin_memcpy(&h, &w, 4);
-                    h = __builtin_elementwise_max(h, s16x2{0, 0});
-                    __builtin_memcpy(&w, &h, 4);
-                }
-                pk[k >> 1] = w;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int cl = 8 * g + 4 * hf;
+                uint32_t pk[2];
+                epi_pack4<RELU>(a2, 4 * g, s_par, cl, pk);
+                __builtin_memcpy(s_o + pl * REPI + cl * 2, pk, sizeof(pk));
             }
-            __builtin_memcpy(s_o + pl * REPI + cl * 2, pk, sizeof(pk));
-        }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if constexpr (occ2_form<Q, CMP, RELU, ST>()) {
@@ -570,40 +528,35 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
             const uint32_t m = m2 ? (uint32_t)__builtin_amdgcn_readlane((int)m2row, b < 0 ? 0 : b) : 0xffffffffu;
             const __amdgpu_buffer_rsrc_t rs =
                 __builtin_amdgcn_make_buffer_rsrc(orow, (short)0, (int)((31 * ostr + 32) * 2), 0x00020000);
-    #pragma unroll
+#pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int pc = lane + 64 * k, px = pc >> 2, pi = pc & 3;
                 const u32x4 v = *reinterpret_cast<const u32x4 *>(s_o + px * REPI + pi * 16);
                 const bool ok = row_ok && x0 + px < r.w && ((m >> px) & 1u);
                 const int off = ok ? (int)((px * ostr + pi * 8) * 2) : (int)0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, SHPL_ROWS_NTSTORE ? 2 : 0);  // 2: nt
+                __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 2);  // 2: nt
             }
         } else {
-    #pragma unroll
-        for (int k = 0; k < 2; ++k) {  // 32 pixels x 4 pieces of 8 channels
-            const int pc = lane + 64 * k, px = pc >> 2, pi = pc & 3;
-            const u32x4 v = *reinterpret_cast<const u32x4 *>(s_o + px * REPI + pi * 16);
-            uint16_t *dst = row_ok && x0 + px < r.w ? orow + px * (int)ostr + pi * 8 : r.junk + pc * 8;
-#if SHPL_ROWS_NTSTORE
-            __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(dst));
-#else
-            *reinterpret_cast<u32x4 *>(dst) = v;
-#endif
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {  // 32 pixels x 4 pieces of 8 channels, nontemporal
+                const int pc = lane + 64 * k, px = pc >> 2, pi = pc & 3;
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(s_o + px * REPI + pi * 16);
+                uint16_t *dst = row_ok && x0 + px < r.w ? orow + px * (int)ostr + pi * 8 : r.junk + pc * 8;
+                __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(dst));
+            }
         }
-        }
-#endif
         if constexpr (streg<Q, QA, CMP, ST>()) {
             // batch statistics of the pre-activation row (f32): the lane's channels 16h + 4 (lane / 16) + k at its
             // pixels lane % 16 and 16 + lane % 16 (tiles 2h, 2h + 1) summed, then halves exchanged across lane ^ 8
-            // (bit 3 clear keeps h = 0, set h = 1) and added to the lane's band sums s_st[lane] / s_st[64 + lane]
+            // (bit 3 clear keeps h = 0, set h = 1) and added to the lane's band sums str[0] / square sums str[1]
             if (row_ok) {
                 const int nv = r.w - x0, p = lane & 15;
                 const bool ok0 = p < nv, ok1 = 16 + p < nv, hi = (lane >> 3) & 1;
-                f32x4 ss = SHPL_ROWS_STREG == 2 ? str[0] : s_st[lane], sq = SHPL_ROWS_STREG == 2 ? str[1] : s_st[64 + lane];
-    #pragma unroll
+                f32x4 ss = str[0], sq = str[1];
+#pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float sv[2], qv[2];
-    #pragma unroll
+#pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const float v0 = ok0 ? a2[4 * (2 * h) + k] : 0.0f, v1 = ok1 ? a2[4 * (2 * h + 1) + k] : 0.0f;
                         sv[h] = __fadd_rn(v0, v1);
@@ -614,13 +567,8 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
                     ss[k] = __fadd_rn(ss[k], __fadd_rn(ks, lane_xor8(gs)));
                     sq[k] = __fadd_rn(sq[k], __fadd_rn(kq, lane_xor8(gq)));
                 }
-                if constexpr (SHPL_ROWS_STREG == 2) {
-                    str[0] = ss;
-                    str[1] = sq;
-                } else {
-                    s_st[lane] = ss;
-                    s_st[64 + lane] = sq;
-                }
+                str[0] = ss;
+                str[1] = sq;
             }
         } else if constexpr (ST) {
             // batch statistics of the pre-activation row (f32, as the tiled kernel): the accumulator through a
@@ -628,22 +576,22 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
             // bf16 transpose's reads above are done first), then lane (cp, qt) sums channels 2cp, 2cp+1 over
             // pixels 8qt .. 8qt+7 of the row into its band sums (kept in LDS: the pooled form has no VGPR to spare)
             float *s_f = reinterpret_cast<float *>(s_o);
-            if constexpr (m16<Q, ST>()) {
-    #pragma unroll
+            if constexpr (m16<Q>()) {
+#pragma unroll
                 for (int t = 0; t < 4; ++t)
                     *reinterpret_cast<f32x4 *>(s_f + (16 * (t & 1) + (lane & 15)) * SPF + 16 * (t >> 1) +
                                                4 * (lane >> 4)) = tile4(a2, t);
             } else {
-    #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<f32x4 *>(s_f + pl * SPF + 8 * g + 4 * hf) =
-                    f32x4{a2[4 * g], a2[4 * g + 1], a2[4 * g + 2], a2[4 * g + 3]};
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<f32x4 *>(s_f + pl * SPF + 8 * g + 4 * hf) =
+                        f32x4{a2[4 * g], a2[4 * g + 1], a2[4 * g + 2], a2[4 * g + 3]};
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (row_ok) {
                 const int cp = lane & 15, qt = lane >> 4, nv = r.w - x0;
                 float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    #pragma unroll
+#pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     if (k == 4) asm volatile("" ::: "memory");  // two batches of reads (transient registers)
                     const int px = 8 * qt + k;
@@ -655,7 +603,7 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
                     t[3] = __fadd_rn(t[3], __fmul_rn(v[1], v[1]));
                 }
                 f32x4 a = s_st[lane];
-    #pragma unroll
+#pragma unroll
                 for (int i = 0; i < 4; ++i) a[i] = __fadd_rn(a[i], t[i]);
                 s_st[lane] = a;
             }
@@ -665,9 +613,7 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
     for (int i = 0; i < 16; ++i) a2[i] = 0.0f;
     // stage row j + RING into the slot (the transpose's reads of it are done first)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if SHPL_ROWS_PROBE == 3
-    SHPL_STAMP(t3);
-#endif
+    SHPL_PH_STAMP(3);
     if (SHPL_ROWS_PROBE == 2) return;
     const int jn = j + RING, y = ya - 1 + jn;
     const bool live = jn < n_in;
@@ -687,30 +633,20 @@ __device__ __forceinline__ void step(const RowArgs &r, const bf16x8 (&wr)[Q][9],
         ob[i] = offsets_in_lds<Q, QA, CMP, ST>() ? (int32_t)s_offs[(L::NA + i) * 64 + lane] : offb[i];
     stage<Q, QA, CMP>(r, frame_row0 + (int64_t)y * r.w + x0 - 1, live && y >= 0 && y < r.h, occ, first, oa, ob,
                       s_ring + U * L::SLOT, lane);
-#if SHPL_ROWS_PROBE == 3
-    SHPL_STAMP(t4);
-    ph[0] += t1 - t0;
-    ph[1] += t2 - t1;
-    ph[2] += t3 - t2;
-    ph[3] += t4 - t3;
-#endif
-    (void)ph;
+    SHPL_PH_STAMP(4);
 }
 
-// Waves per SIMD: SHPL_ROWS_WPE, but the pooled 3 + 1 chunk form without ReLU on the 16x16 shape may drop to
+// Waves per SIMD: SHPL_ROWS_WPE, but the pooled 3 + 1 chunk form without ReLU (on the 16x16 shape) may drop to
 // one (it needs 257 registers at two; the allocation differs from the ReLU form's by one register).
 template <int Q, int QA, bool CMP, bool RELU, bool ST>
-constexpr int rows_wpe_min() { return (m16<Q, ST>() && CMP && Q == 4 && QA == 3 && !RELU) ? 1 : SHPL_ROWS_WPE; }
+constexpr int rows_wpe_min() { return (CMP && Q == 4 && QA == 3 && !RELU) ? 1 : SHPL_ROWS_WPE; }
 
 template <int Q, int QA, bool CMP, bool RELU, bool ST>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min<Q, QA, CMP, RELU, ST>(),
                                                                     SHPL_ROWS_WPE))) void k_conv_rows(
     const RowArgs r) {
     typedef Layout<Q, QA, ST> L;
-#if SHPL_ROWS_PROBE == 3
-    uint64_t rt0;
     SHPL_RSTAMP(rt0);
-#endif
     __shared__ __attribute__((aligned(16))) uint8_t s_ring[RING * L::SLOT];
     __shared__ __attribute__((aligned(16))) float s_par[2][NCO];
     // the halo rows' occupancy windows (entry j: input row ya - 1 + j): cells x0-1 .. x0+32 as bits 0..33, and
@@ -721,23 +657,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min
     // (frame, band, strip, output block), output blocks fastest, then strips; each XCD (blocks b, b+8, ...)
     // takes one contiguous run of them, so the blocks of a strip read its rows together, and neighbouring
     // strips share their halo columns and neighbouring bands their halo rows, in that L2
-#if SHPL_ROWS_XCD
     const int wi = (int)xcd_block(blockIdx.x, r.n_items * r.n_cob);
-#else
-    const int wi = blockIdx.x;
-#endif
     const int cob = wi % r.n_cob, item = wi / r.n_cob;
     const int strip = item % r.strips, fb = item / r.strips;
     const int band = fb % r.n_bands, f = fb / r.n_bands;
     const bool second = r.out2 && cob * NCO >= r.c_split;
     uint16_t *const obase = second ? r.out2 + (cob * NCO - r.c_split) : r.out + cob * NCO;
     const int64_t ostr = second ? r.out2_stride : r.out_stride;
-    // ST: lane (cp, qt)'s band sums of channels 2cp, 2cp+1 (sum, sum; square sum, square sum); with STREG the
-    // lane's sums (s_st[lane]) and square sums (s_st[64 + lane]) of channels 16 ((lane / 8) % 2) + 4 (lane / 16) + k
+    // ST: lane (cp, qt)'s band sums of channels 2cp, 2cp+1 (sum, sum; square sum, square sum) in s_st; the STREG
+    // forms instead keep the lane's sums (str[0]) and square sums (str[1]) of channels
+    // 16 ((lane / 8) % 2) + 4 (lane / 16) + k in registers
     constexpr bool STREG = streg<Q, QA, CMP, ST>();
-    __shared__ f32x4 s_st[ST ? (STREG ? 128 : 64) : 1];
-    if constexpr (ST) s_st[lane] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    if constexpr (STREG) s_st[64 + lane] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    __shared__ f32x4 s_st[ST && !STREG ? 64 : 1];
+    if constexpr (ST && !STREG) s_st[lane] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     const int H = r.h;
     const int x0 = strip * TW, ya = band * r.band;
     const int n_out = min(r.band, H - ya), n_in = n_out + 2;
@@ -752,6 +684,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min
     }
     uint64_t b_rows = ~0ull;
     if constexpr (CMP) {
+        // the same window computation as in k_wgrad_rows (a shared helper changed the pooled kernels' loops and
+        // k_wgrad_rows' registers; the copies stay)
         const int y = ya - 1 + lane, w0 = x0 >> 5;
         uint64_t occ_row = 0;
         int32_t first_row = 0;
@@ -793,7 +727,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min
     // the chunk weights of all taps stay in registers: A operands (32 output x 16 input channels)
     bf16x8 wr[Q][9];
     const uint16_t *wq = r.wp + (int64_t)cob * Q * W_ROWS * 16;
-    if constexpr (m16<Q, ST>()) {
+    if constexpr (m16<Q>()) {
         // wr[2c + h][t]: the A operand of K-chunk c, output half h (lane: channel 16h + lane % 16, inputs
         // 8 (lane / 16) .. of the chunk: 16-channel chunk 2c + lane / 32, its half (lane / 16) % 2)
 #pragma unroll
@@ -806,10 +740,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min
                         wq + (((2 * c + (lane >> 5)) * 9 + t) * NCO + 16 * h + (lane & 15)) * 16 + ((lane >> 4) & 1) * 8);
     } else {
 #pragma unroll
-    for (int q = 0; q < Q; ++q)
+        for (int q = 0; q < Q; ++q)
 #pragma unroll
-        for (int t = 0; t < 9; ++t)
-            wr[q][t] = *reinterpret_cast<const bf16x8 *>(wq + ((q * 9 + t) * NCO + (lane & 31)) * 16 + (lane >> 5) * 8);
+            for (int t = 0; t < 9; ++t)
+                wr[q][t] =
+                    *reinterpret_cast<const bf16x8 *>(wq + ((q * 9 + t) * NCO + (lane & 31)) * 16 + (lane >> 5) * 8);
     }
 #if !SHPL_ROWS_WLATE
     // the weights have landed before the loop, as the compiler's wait model must know: its waitcnt pass
@@ -818,7 +753,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min
     // rows and the stores) every row. The builtin clears its scoreboard (the prologue's DMAs land too)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
 #endif
-    const uint64_t m2live = m2 ? __ballot(m2row != 0u) : ~0ull;  // m2: the output rows with an occupied cell
     f32x16 acc[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -833,44 +767,42 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min
         const int g = 4 * c + (lane >> 4);
         rdq[c] = (uint32_t)(((g < 2 * QA ? g * HWD : L::RB + (g - 2 * QA) * HWD) + (lane & 15)) * 16);
     }
-    uint64_t ph[5] = {0, 0, 0, 0, 0};
-    f32x4 str[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};  // STREG == 2: the band sums
+    f32x4 str[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};  // STREG: the band sums
 #if SHPL_ROWS_PROBE == 3
-    uint64_t tk0, rt1;
-    SHPL_STAMP(tk0);
-    SHPL_RSTAMP(rt1);
+    Phases ph = {0, {0, 0, 0, 0}};
 #endif
+    SHPL_KSTAMP(tk0);
+    SHPL_RSTAMP(rt1);
     for (int j = 0; j < n_in; j += RING) {
 #define SHPL_ROWS_STEP(UU)                                                                                          \
     if (j + UU >= n_in) break;                                                                                      \
     step<Q, QA, CMP, RELU, ST, UU>(r, wr, acc, s_par, rd, s_ring, frame_row0, x0, ya, n_in, n_out, obase, ostr, s_st, \
-                                   j + UU, s_occ, s_first, b_rows, offa, offb, s_offs, rdq, lane, str, ph, m2row, m2, m2live);
+                                   j + UU, s_occ, s_first, b_rows, offa, offb, s_offs, rdq, lane, str, m2row,      \
+                                   m2 SHPL_PH_ARG);
         SHPL_ROWS_STEP(0)
         SHPL_ROWS_STEP(1)
         SHPL_ROWS_STEP(2)
 #undef SHPL_ROWS_STEP
     }
-    asm volatile("s_waitcnt vmcnt(0) expcnt(5)" ::: "memory");  // the trailing DMAs land before the wave's LDS is released (expcnt(5): the ISA guard's exit marker)
-#if SHPL_ROWS_PROBE == 3
-    uint64_t tk1, rt2;
-    SHPL_STAMP(tk1);
+    // the trailing DMAs land before the wave's LDS is released (expcnt(5): the ISA guard's exit marker)
+    asm volatile("s_waitcnt vmcnt(0) expcnt(5)" ::: "memory");
+    SHPL_KSTAMP(tk1);
     SHPL_RSTAMP(rt2);
+#if SHPL_ROWS_PROBE == 3
+    // per wave 10 words (scripts/conv_phases.py): the four phase sums, the whole loop, the input rows, the
+    // s_memrealtime stamps at the wave's start, loop start and loop end; word 9 unused
     if (lane == 0 && blockIdx.x < CPROBE_WAVES) {
         uint64_t *o = g_cprobe + 10 * (int64_t)blockIdx.x;
+        for (int i = 0; i < 4; ++i) o[i] = ph.sum[i];
+        o[4] = tk1 - tk0;
+        o[5] = (uint64_t)n_in;
         o[6] = rt0;
         o[7] = rt1;
         o[8] = rt2;
-        o[0] = ph[0];
-        o[1] = ph[1];
-        o[2] = ph[2];
-        o[3] = ph[3];
-        o[4] = tk1 - tk0;
-        o[5] = (uint64_t)n_in;
     }
 #endif
     if constexpr (STREG) {  // the band's sums over the 8 pixel lanes of each channel group, one double each
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        f32x4 ss = SHPL_ROWS_STREG == 2 ? str[0] : s_st[lane], sq = SHPL_ROWS_STREG == 2 ? str[1] : s_st[64 + lane];
+        f32x4 ss = str[0], sq = str[1];
 #pragma unroll
         for (int o = 1; o < 8; o <<= 1)
 #pragma unroll
@@ -924,10 +856,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(rows_wpe_min
 // zero products). Per wave one f32 partial of the 9 x 32 x 32 tile; two
 // fixed-order reductions (f64) give dW: deterministic.
 #ifndef SHPL_WG_PROBE
-#define SHPL_WG_PROBE 0
-#endif
-#ifndef SHPL_WG_PAIR
-#define SHPL_WG_PAIR 1
+#define SHPL_WG_PROBE 0  // Stays: a timing probe like SHPL_ROWS_PROBE. 1: no staging in the loop (wrong results)
 #endif
 
 constexpr int WX_PIECES = HWD * 4;                  // X row: 34 pixels x 4 pieces of 8 channels
@@ -981,7 +910,7 @@ __device__ __forceinline__ void wstage(const WgRowArgs &r, const uint16_t *xsrc,
 #pragma unroll
     for (int i = 0; i < WNX; ++i) {
         uint32_t o = offx[i];
-        if (cmp) {
+        if (cmp) {  // the same arithmetic as in stage (k_conv_rows), kept as a copy: see there
             const int32_t e = (int32_t)offx[i];
             const int px = (e >> 16) & 63;
             const bool hit = e >= 0 && ((occ >> px) & 1);
@@ -1097,7 +1026,7 @@ void k_wgrad_rows(const WgRowArgs r) {
                 offx[i] = ok ? (uint32_t)((px * (int)xstride + 8 * cq) * 2) : OOB;
         }
         if (pooled) {  // lane j: halo row j's window (cells x0-1 .. x0+32 as bits 0..33) and its first run
-            const int y = ya - 1 + lane, w0 = x0 >> 5;
+            const int y = ya - 1 + lane, w0 = x0 >> 5;  // as in k_conv_rows, kept as a copy: see there
             uint64_t occ_row = 0;
             int32_t first_row = 0;
             if (lane < n_in && y >= 0 && y < r.h) {
@@ -1299,8 +1228,8 @@ void wgrad_sizes(int n_items, int c_a, int c_b, int c_out, int *n_groups, size_t
 }
 
 int wgrad_launch(const WgRowArgs &r, float *dw, double *part2, hipStream_t s) {
-    // pairs of input tiles share their G rows (SHPL_WG_PAIR 0: one wave per input tile)
-    const bool pair = SHPL_WG_PAIR && r.n_cit % 2 == 0;
+    // pairs of input tiles share their G rows; an odd number of them: one wave per input tile
+    const bool pair = r.n_cit % 2 == 0;
     const int total = r.n_groups * r.n_cot * (pair ? r.n_cit / 2 : r.n_cit);
     const dim3 grid((unsigned)total), block(pair ? 128 : 64);
     if (r.cmp) {
