@@ -257,7 +257,8 @@ def test_row_keyed_pulls_noncanonical_M(c):
     """k_rows (shpl_pull over a CSR with key_range) == k_dense + k_sparse == the oracle,
     bitwise, on a non-canonical M: shuffled nnz, repeated columns (TF's per-column
     partials), negative weights, a 160-entry run, 3 / 8 / 64 channels (scalar path,
-    one chunk per lane, groups of 16 lanes), every direction / order / output mode."""
+    one chunk per lane, groups of 16 lanes), every direction / order / output mode.
+    Strides, offsets, padding and the other widths: tests/test_gpu_pulls.py."""
     from sparse_pooling_amd import _lib as L
     from sparse_pooling_amd import shpl_map as sm
     rng = np.random.default_rng(22)
