@@ -545,6 +545,17 @@ typedef enum { SHPL_ACT_NONE = 0, SHPL_ACT_RELU = 1 } shpl_act;
  *                 [a || shpl_pull(SHPL_BY_CELL, ...)] without writing it --
  *                 bitwise, when c_a is a multiple of the staging chunk (8 f32
  *                 / 16 bf16 channels; otherwise the K order differs).
+ *                 Or the pixel-keyed CSR (shpl_build_csr SHPL_BY_PIXEL,
+ *                 SHPL_ORDER_COL_ROW, with ent_col, or without it and flagged
+ *                 SHPL_CSR_IDENTITY_COLS as shpl_build_csr_buckets leaves it;
+ *                 a pool counts as pixel-keyed when either holds): the image
+ *                 side. n_keys = n_frames*h*w then counts image pixels, d_a
+ *                 is the image map, d_b the BEV map, and the result is
+ *                 bitwise the conv of [a || shpl_pull(SHPL_BY_PIXEL, ...)]:
+ *                 with ent_col a pixel's run is summed per column of M first
+ *                 and the columns' partials then added (TF's ScatterNd order,
+ *                 shpl_pull's); flagged identity columns take the plain sum,
+ *                 as the pulls do. A cell-keyed CSR leaves ent_col NULL.
  * d_weights: HWIO [3][3][c_a+c_b][c_out] in the feature dtype (slim.conv2d's
  * variable). d_center / d_scale / d_shift: optional [c_out] f32 (NULL = 0 / 1
  * / 0) -- BatchNorm inference: center = moving_mean, scale = gamma /
@@ -561,8 +572,11 @@ typedef enum { SHPL_ACT_NONE = 0, SHPL_ACT_RELU = 1 } shpl_act;
  * arithmetic) and gathered by the conv's staging.
  * Replaces: bv_fused = sparse_pool_layer(...) (sparse_pool_utils.py:61-92)
  *   followed by slim.conv2d(bv_fused, Ci, [3,3], normalizer_fn=slim.batch_norm)
- *   (avod/avod/core/models/rpn_model.py:338-346, scope pyramid_fusion_pooled_bev;
- *   the img side :347-354) and slim.conv2d(bev_fused, 256, [3,3])
+ *   (avod/avod/core/models/rpn_model.py:338-346, scope pyramid_fusion_pooled_bev);
+ *   with the pixel-keyed CSR, img_fused = [img || _sparse_pool_trans_op(M, bev)]
+ *   (sparse_pool_utils.py:79-87) followed by the conv of scope
+ *   pyramid_fusion_pooled_img (rpn_model.py:347-354); and
+ *   slim.conv2d(bev_fused, 256, [3,3])
  *   (avod/avod/core/models/retinanet_model.py:343-348). */
 int shpl_conv3x3_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b,
                                  int64_t c_out, int64_t pool_nnz_cap, int stats, size_t *bytes);
@@ -576,7 +590,8 @@ int shpl_conv3x3(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a,
 /* Whether shpl_conv3x3 with these arguments (d_ws / ws_bytes / d_center / d_scale / d_shift / stream aside;
  * stats = d_stats != NULL) runs the row-streaming form (*rows_form = 1), whose pooled call leaves the
  * occupancy maps and per-run pooled rows in its workspace that shpl_conv3x3_wgrad_reuse reads; 0 for the
- * tiled form, f32, or no pixel. The same predicate shpl_conv3x3 decides by. */
+ * tiled form, f32, or no pixel. The same predicate shpl_conv3x3 decides by; pool may be the pixel-keyed CSR
+ * of the image side, as there. */
 int shpl_conv3x3_rows_form(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
                            int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b,
                            const shpl_csr *pool, const int64_t *d_frame_off, const void *d_weights, int64_t c_out,
@@ -637,6 +652,9 @@ int shpl_conv3x3_dgrad(int dtype, int n_frames, int64_t h, int64_t w, const void
  * what this call can check of that is SHPL_ERR_ARG when false. d_dx and the written cells of d_dx_b are
  * shpl_conv3x3_dgrad's, bit for bit. When the input gradient itself does not run the row-streaming form (f32,
  * misaligned maps) or has more than 32 gradient channels (c_gy), d_dx_b is written whole.
+ * Image side (pool the pixel-keyed CSR of the forward, n_keys = n_frames*h*w image pixels): d_dx_b, the pooled
+ * BEV channels' gradient over the image, is written only at the occupied pixels -- the rows a
+ * shpl_pull(SHPL_BY_CELL, ...) over the SHPL_ORDER_COL_ENTRY CSR reads to carry it back to the BEV map.
  * Replaces: the image half of TF's conv2d backprop input in the rpn_model.py:338-354 fusion, which the
  * gradient of tf.gather_nd / tf.segment_sum (sparse_pool_utils.py:96-117) reads only at occupied cells. */
 int shpl_conv3x3_dgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, int64_t gy_stride,
@@ -652,7 +670,9 @@ int shpl_conv3x3_dgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, cons
  * partials summed in a fixed order (f64): deterministic. d_dw: f32 HWIO
  * [3][3][c_a+c_b][c_out]. Workspace: pool_nnz_cap as shpl_conv3x3's (-1: B
  * dense or absent; with a pool, its CSR's nnz_cap, which sizes the compact
- * buffer of pooled runs of the bf16 form). */
+ * buffer of pooled runs of the bf16 form). pool may be the pixel-keyed CSR of
+ * the image side, exactly as shpl_conv3x3 takes it (x = [img || the BEV map
+ * pooled with shpl_pull(SHPL_BY_PIXEL)'s per-column sums]). */
 int shpl_conv3x3_wgrad_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b,
                                        int64_t c_out, int64_t pool_nnz_cap, size_t *bytes);
 int shpl_conv3x3_wgrad(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
@@ -668,7 +688,7 @@ int shpl_conv3x3_wgrad(int dtype, int n_frames, int64_t h, int64_t w, const void
  * shpl_conv3x3_rows_form reported 1 (the caller's to establish: the forward's act and output pointer are not
  * arguments here); what this call can check of that predicate and finds false is SHPL_ERR_ARG. When the
  * weight gradient itself does not run the row-streaming form the workspace is not read. Same results as
- * shpl_conv3x3_wgrad, bit for bit. */
+ * shpl_conv3x3_wgrad, bit for bit. Cell-keyed or pixel-keyed pool alike (the forward's). */
 int shpl_conv3x3_wgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
                              int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off,
                              int64_t c_b, const shpl_csr *pool, const int64_t *d_frame_off, const void *d_gy,

@@ -74,6 +74,45 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 
+// The sum of one destination's run of CSR entries over N channels, in TF-CPU order: entries in CSR order,
+// separate multiply and add, from 0 -- walk_run's arithmetic (shpl_pull.hip), bit for bit, for the conv's
+// pooled-operand producers. GROUP (a pixel-keyed run that carries ent_col): the per-column partial Q[k]
+// first, added to the sum at every change of column -- the first change adds the zero partial (0 + 0 = +0)
+// -- and once at the end (ScatterNd's order); otherwise every product straight into the sum.
+template <bool GROUP, int N>
+struct RunSum {
+    float acc[N], q[N];
+    int32_t kprev;
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc[j] = q[j] = 0.0f;
+        kprev = -1;  // no column yet
+    }
+    __device__ __forceinline__ void add(int32_t col, float w, const float (&x)[N]) {
+        if constexpr (GROUP) {
+            if (col != kprev) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    acc[j] = __fadd_rn(acc[j], q[j]);
+                    q[j] = 0.0f;
+                }
+                kprev = col;
+            }
+#pragma unroll
+            for (int j = 0; j < N; ++j) q[j] = __fadd_rn(q[j], __fmul_rn(w, x[j]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < N; ++j) acc[j] = __fadd_rn(acc[j], __fmul_rn(w, x[j]));
+        }
+    }
+    __device__ __forceinline__ void finish() {
+        if constexpr (GROUP) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) acc[j] = __fadd_rn(acc[j], q[j]);
+        }
+    }
+};
+
 // Make this workgroup's global stores visible to its other waves: every wave
 // drains its vector-memory stores before the barrier (a workgroup-scope
 // __syncthreads does not wait for them on gfx950), then invalidates the

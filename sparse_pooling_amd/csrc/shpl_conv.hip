@@ -31,6 +31,12 @@
 // arithmetic of k_sparse (shpl_pull.hip: TF order, separate multiply and
 // add), so the conv of the fused form is bitwise the conv of
 // [bev || shpl_pull(...)] and bv_fused never reaches HBM.
+//
+// The image side (rpn_model.py:347-354 over img_fused = [img || trans(bev)])
+// is the same call with A the image map, B the BEV map and the pixel-keyed CSR
+// as the pool: nothing here reads a key's meaning, only the sum of a run
+// changes -- with ent_col it is TF's sum of per-column partials (GROUP:
+// RunSum in shpl_common.h, walk_run<GROUP>'s arithmetic in shpl_pull.hip).
 #include "shpl_conv_bn.h"
 #include "shpl_conv_rows.h"
 #include "shpl_conv_wide.h"
@@ -68,8 +74,9 @@ struct ConvArgs {
     int64_t b_stride, b_off;
     int c_b, qb;
     bool vec_a, vec_b;  // 16-byte aligned rows and offsets
-    // POOLED: B rows are image pixels read through the cell-keyed CSR
-    const int32_t *ent_dst, *ent_src, *row_ptr;
+    // POOLED: B rows are read through the pool's CSR -- image pixels through the cell-keyed one; BEV cells
+    // through the pixel-keyed one, whose ent_col (when set) groups each run by column (GROUP)
+    const int32_t *ent_dst, *ent_src, *ent_col, *row_ptr;
     const float *ent_val;
     const void *wp;  // packed weights [co_block][chunk][tap][32][CK]
     const float *center, *scale, *shift;
@@ -141,28 +148,32 @@ __device__ __forceinline__ int xcd_tile(int bid, int n) { return (int)xcd_block(
 // Pooled vector of one occupied cell for the channels [c0, c0 + CK) of the
 // chunk: sum over the cell's run of CSR entries [e0, e1) of val * img[src],
 // in entry order with separate multiply and add from 0 -- the arithmetic of
-// k_sparse (shpl_pull.hip) -- written to the cell's LDS row.
-template <typename T, bool SWZ, int PSTR>
+// k_sparse (shpl_pull.hip) -- written to the cell's LDS row. GROUP: a pixel's run of the pixel-keyed CSR with
+// ent_col, summed per column first (RunSum: walk_run<GROUP>'s order).
+template <typename T, bool SWZ, int PSTR, bool GROUP>
 __device__ __forceinline__ void pool_run(const ConvArgs &p, const T *img, int c0, int32_t e0, int32_t e1,
                                          int32_t src0, float val0, uint8_t *s_base, int pix) {
     typedef Elem<T> E;
     constexpr int HE = E::HE;
     for (int g = 0; g < E::NP; ++g) {  // one 16-byte piece (4 f32 / 8 bf16 channels) at a time
-        float sum[HE];
-#pragma unroll
-        for (int c = 0; c < HE; ++c) sum[c] = 0.0f;
+        RunSum<GROUP, HE> sum;
+        sum.init();
         for (int32_t i = e0; i < e1; ++i) {
             const T *row = img + (int64_t)(i == e0 ? src0 : p.ent_src[i]) * p.b_stride;
             const float wv = i == e0 ? val0 : p.ent_val[i];
+            const int32_t kc = GROUP ? p.ent_col[i] : 0;
             const u32x4 raw = load_piece<T>(row, c0 + g * HE, p.c_b, p.vec_b);
             T x[HE];
             __builtin_memcpy(x, &raw, sizeof(raw));
+            float xf[HE];
 #pragma unroll
-            for (int c = 0; c < HE; ++c) sum[c] = __fadd_rn(sum[c], __fmul_rn(wv, E::f(x[c])));
+            for (int c = 0; c < HE; ++c) xf[c] = E::f(x[c]);
+            sum.add(kc, wv, xf);
         }
+        sum.finish();
         T o[HE];
 #pragma unroll
-        for (int c = 0; c < HE; ++c) o[c] = E::back(sum[c]);
+        for (int c = 0; c < HE; ++c) o[c] = E::back(sum.acc[c]);
         __builtin_memcpy(s_base + piece_off<SWZ, PSTR>(pix, g), o, 16);
     }
 }
@@ -175,23 +186,24 @@ __device__ __forceinline__ void pool_run(const ConvArgs &p, const T *img, int c0
 #define SHPL_POOL_PIECES 1
 #endif
 constexpr int POOL_BATCH = 4;
-template <typename T, bool SWZ, int PSTR>
+template <typename T, bool SWZ, int PSTR, bool GROUP>
 __device__ __forceinline__ void pool_piece(const ConvArgs &p, const T *img, int c, int32_t e0, int32_t e1,
                                            int32_t src0, float val0, uint8_t *s_base, int pix, int g) {
     typedef Elem<T> E;
     constexpr int HE = E::HE;
-    float sum[HE];
-#pragma unroll
-    for (int j = 0; j < HE; ++j) sum[j] = 0.0f;
+    RunSum<GROUP, HE> sum;
+    sum.init();
     for (int32_t i0 = e0; i0 < e1; i0 += POOL_BATCH) {
         u32x4 raw[POOL_BATCH];
         float wv[POOL_BATCH];
+        int32_t kc[POOL_BATCH];
 #pragma unroll
         for (int u = 0; u < POOL_BATCH; ++u) {
             const int32_t i = i0 + u;
             if (i < e1) {
                 const int32_t sr = i == e0 ? src0 : p.ent_src[i];
                 wv[u] = i == e0 ? val0 : p.ent_val[i];
+                kc[u] = GROUP ? p.ent_col[i] : 0;
                 raw[u] = load_piece<T>(img + (int64_t)sr * p.b_stride, c, p.c_b, p.vec_b);
             }
         }
@@ -200,13 +212,16 @@ __device__ __forceinline__ void pool_piece(const ConvArgs &p, const T *img, int 
             if (i0 + u >= e1) break;
             T x[HE];
             __builtin_memcpy(x, &raw[u], sizeof(raw[u]));
+            float xf[HE];
 #pragma unroll
-            for (int j = 0; j < HE; ++j) sum[j] = __fadd_rn(sum[j], __fmul_rn(wv[u], E::f(x[j])));
+            for (int j = 0; j < HE; ++j) xf[j] = E::f(x[j]);
+            sum.add(kc[u], wv[u], xf);
         }
     }
+    sum.finish();
     T o[HE];
 #pragma unroll
-    for (int j = 0; j < HE; ++j) o[j] = E::back(sum[j]);
+    for (int j = 0; j < HE; ++j) o[j] = E::back(sum.acc[j]);
     __builtin_memcpy(s_base + piece_off<SWZ, PSTR>(pix, g), o, 16);
 }
 
@@ -313,7 +328,7 @@ __device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRun
 // outside the map. Pooled chunks: zeros where no entry lands, each run's sum
 // elsewhere (disjoint cells: no barrier between the two). The caller
 // synchronises after.
-template <typename T, bool POOLED, int PSTR, bool SWZ = false, int HHT = HH>
+template <typename T, bool POOLED, int PSTR, bool SWZ = false, int HHT = HH, bool GROUP = false>
 __device__ __forceinline__ void stage_halo(const ConvArgs &p, int q, int f, int y0, int x0, uint8_t *s_in,
                                            const HaloRuns &r, int n_run) {
     typedef Elem<T> E;
@@ -359,11 +374,11 @@ __device__ __forceinline__ void stage_halo(const ConvArgs &p, int q, int f, int 
 #if SHPL_POOL_PIECES
         // one (run, 16-byte piece) pair per thread, POOL_BATCH entries' loads in flight per round trip
         for (int t = tid; t < n_run * NP; t += CONV_BLOCK)
-            pool_piece<T, SWZ, PSTR>(p, img, (q - p.qa) * CK + (t % NP) * HE, r.e[t / NP], r.end[t / NP],
-                                     r.src[t / NP], r.val[t / NP], s_in, r.pix[t / NP], t % NP);
+            pool_piece<T, SWZ, PSTR, GROUP>(p, img, (q - p.qa) * CK + (t % NP) * HE, r.e[t / NP], r.end[t / NP],
+                                            r.src[t / NP], r.val[t / NP], s_in, r.pix[t / NP], t % NP);
 #else
         for (int k = tid; k < n_run; k += CONV_BLOCK)
-            pool_run<T, SWZ, PSTR>(p, img, (q - p.qa) * CK, r.e[k], r.end[k], r.src[k], r.val[k], s_in, r.pix[k]);
+            pool_run<T, SWZ, PSTR, GROUP>(p, img, (q - p.qa) * CK, r.e[k], r.end[k], r.src[k], r.val[k], s_in, r.pix[k]);
 #endif
     }
 }
@@ -396,7 +411,7 @@ struct ConvTile {
 // Weights and dense halo chunks are LDS-DMAs (lane k of the wave fills slot
 // k: it loads the piece the swizzle puts there); pooled chunks are computed
 // (stage_halo). The caller waits and synchronises.
-template <typename T, bool POOLED, int NCB = 1>
+template <typename T, bool POOLED, int NCB = 1, bool GROUP = false>
 __device__ __forceinline__ void conv_stage(const ConvArgs &p, int q, int f, int y0, int x0, const T *wq,
                                            int64_t wq_cb, uint8_t *s_in, uint8_t *s_w, const HaloRuns &runs,
                                            int n_run) {
@@ -437,14 +452,15 @@ __device__ __forceinline__ void conv_stage(const ConvArgs &p, int q, int f, int 
                                 s_in + base * 16, lane);
         }
     } else {
-        stage_halo<T, true, E::CB, true, HHT>(p, q, f, y0, x0, s_in, runs, n_run);
+        stage_halo<T, true, E::CB, true, HHT, GROUP>(p, q, f, y0, x0, s_in, runs, n_run);
     }
 }
 
 // NCB: output-channel blocks per workgroup (blockIdx.y covers NCB of them):
 // 2 for the input gradient's 64 output channels, so each staged input chunk
-// feeds twice the MFMAs (one halo staging per tile instead of two).
-template <typename T, bool POOLED, bool STATS, int NCB = 1>
+// feeds twice the MFMAs (one halo staging per tile instead of two). GROUP (POOLED): the pool is the pixel-keyed
+// CSR with ent_col, its runs summed per column first (pool_piece).
+template <typename T, bool POOLED, bool STATS, int NCB = 1, bool GROUP = false>
 __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const ConvArgs p) {
     typedef Elem<T> E;
     constexpr int CK = E::CK, NP = E::NP, RPW = ConvTile<T>::RPW, HHT = ConvTile<T>::HH;
@@ -501,7 +517,7 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
         // buffers with chunk q+1's LDS-DMAs in flight under chunk q's MFMAs
         // (3 workgroups per CU: f32 fused 11.3 -> 12.1 ms), and a register-staged
         // prefetch (VGPRs 62 -> 86-168: 11.8 -> 12.5 ms)
-        conv_stage<T, POOLED, NCB>(p, q, f, y0, x0, wq, wq_cb, s_in, s_w, runs, n_run);
+        conv_stage<T, POOLED, NCB, GROUP>(p, q, f, y0, x0, wq, wq_cb, s_in, s_w, runs, n_run);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMAs have landed
         __syncthreads();
         const uint8_t *si = s_in, *sw = s_w;
@@ -841,7 +857,7 @@ __device__ __forceinline__ void wg_stage(const ConvArgs &p, const WgArgs &g, int
     static_assert(G_PIECES % CONV_BLOCK == 0, "gradient pieces");
 }
 
-template <typename T, bool POOLED>
+template <typename T, bool POOLED, bool GROUP = false>
 __global__ __launch_bounds__(CONV_BLOCK, POOLED ? 1 : 2) void k_conv3x3_wgrad(const ConvArgs p, const WgArgs g) {
     typedef Elem<T> E;
     constexpr int CK = E::CK, CB = E::CB, NQ = WG_CI / CK;
@@ -876,7 +892,8 @@ __global__ __launch_bounds__(CONV_BLOCK, POOLED ? 1 : 2) void k_conv3x3_wgrad(co
 #pragma unroll
             for (int j = 0; j < NQ; ++j) {
                 const int q = cib * NQ + j;
-                if (q < Q) stage_halo<T, POOLED, CB>(p, q, f, y0, x0, s_x + j * NPIX * CB, runs, n_run);
+                if (q < Q)
+                    stage_halo<T, POOLED, CB, false, HH, GROUP>(p, q, f, y0, x0, s_x + j * NPIX * CB, runs, n_run);
             }
         }
         wg_stage<T, !POOLED>(p, g, f, y0, x0, cib, cob, s_x, s_g);
@@ -1284,7 +1301,15 @@ ConvArgs conv_args(int dtype, int n_frames, int64_t h, int64_t w, const ConvPlan
     a.ent_dst = pool ? pool->ent_dst : nullptr;
     a.ent_src = pool ? pool->ent_src : nullptr;
     a.ent_val = pool ? pool->ent_val : nullptr;
+    a.ent_col = pool ? pool->ent_col : nullptr;
     return a;
+}
+
+// A pool counts as pixel-keyed (shpl_build_csr SHPL_BY_PIXEL, SHPL_ORDER_COL_ROW: the keys are image pixels, the
+// sources BEV cells) when it carries ent_col or is flagged as one column per entry; only the former needs the
+// per-column partials, as in the pulls (grouped() in shpl_pull.hip).
+bool pixel_keyed(const shpl_csr *pool) {
+    return pool->ent_col != nullptr || (pool->flags & SHPL_CSR_IDENTITY_COLS) != 0;
 }
 
 // The checks on the sources and the pool that the forward and the weight gradient share, in their order.
@@ -1339,9 +1364,9 @@ int conv_rows_launch(const ConvPlan &pl, const ConvArgs &a, void *ws, bool poole
     r.junk = region<uint16_t>(ws, pl.junk);
     if (pooled) {
         const Pooled po = pooled_in(ws, pl.pooled);
-        const int rc = rows::prep_pooled(a.n_frames, a.h, a.w, pl.g.wpr, a.ent_dst, a.ent_src, a.ent_val, pl.pool_cap,
-                                         frame_off, reinterpret_cast<const uint16_t *>(a.b), a.b_stride, a.b_off,
-                                         a.c_b, po.occ, po.occ_base, po.cmp, s);
+        const int rc = rows::prep_pooled(a.n_frames, a.h, a.w, pl.g.wpr, a.ent_dst, a.ent_src, a.ent_val, a.ent_col,
+                                         pl.pool_cap, frame_off, reinterpret_cast<const uint16_t *>(a.b), a.b_stride,
+                                         a.b_off, a.c_b, po.occ, po.occ_base, po.cmp, s);
         if (rc) return rc;
         r.occ = po.occ;
         r.occ_base = po.occ_base;
@@ -1377,8 +1402,8 @@ int conv_wide_launch(const ConvPlan &pl, const ConvArgs &a, void *ws, const shpl
     if (pool && pl.wide_cmp) {
         const Pooled po = pooled_in(ws, pl.pooled);
         const int rc = wide::prep(a.n_frames, a.h, a.w, pl.g.wpr, pool->ent_dst, pool->ent_src, pool->ent_val,
-                                  pool->nnz_cap, frame_off, reinterpret_cast<const uint16_t *>(a.b), a.b_stride, a.b_off,
-                                  a.c_b, po.occ, po.occ_base, po.cmp, s);
+                                  pool->ent_col, pool->nnz_cap, frame_off, reinterpret_cast<const uint16_t *>(a.b),
+                                  a.b_stride, a.b_off, a.c_b, po.occ, po.occ_base, po.cmp, s);
         if (rc) return rc;
         r.occ = po.occ;
         r.occ_base = po.occ_base;
@@ -1387,8 +1412,8 @@ int conv_wide_launch(const ConvPlan &pl, const ConvArgs &a, void *ws, const shpl
         r.wpr = pl.g.wpr;
     } else if (pool) {
         uint16_t *map = region<uint16_t>(ws, pl.map);
-        const int rc = shpl_pull(SHPL_BY_CELL, SHPL_BF16, pool, a.b, a.b_stride, a.b_off, a.c_b, nullptr, 0, 0, 0,
-                                 SHPL_OUT_POOL, map, a.c_b, s);
+        const int rc = shpl_pull(pixel_keyed(pool) ? SHPL_BY_PIXEL : SHPL_BY_CELL, SHPL_BF16, pool, a.b, a.b_stride,
+                                 a.b_off, a.c_b, nullptr, 0, 0, 0, SHPL_OUT_POOL, map, a.c_b, s);
         if (rc) return rc;
         r.b = map;
         r.b_stride = a.c_b;
@@ -1442,7 +1467,9 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, void *ws, bool pooled, bool sta
     // nothing (2.73 / 2.77 ms: 3 waves per SIMD instead of 6 for a
     // memory-pipeline-bound kernel) and keeps one.
     const bool pair = sizeof(T) == 4 && !pooled && !stats && pl.n_cob % 2 == 0;
-    const auto kernel = pooled  ? (stats ? k_conv3x3<T, true, true> : k_conv3x3<T, true, false>)
+    const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
+    const auto kernel = group   ? (stats ? k_conv3x3<T, true, true, 1, true> : k_conv3x3<T, true, false, 1, true>)
+                        : pooled ? (stats ? k_conv3x3<T, true, true> : k_conv3x3<T, true, false>)
                         : stats ? k_conv3x3<T, false, true>
                         : pair  ? k_conv3x3<T, false, false, 2>
                                 : k_conv3x3<T, false, false>;
@@ -1646,7 +1673,7 @@ int wgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, cons
                     return SHPL_ERR_ARG;
             } else {
                 rc = rows::prep_pooled(n_frames, (int)h, (int)w, wp.g.wpr, pool->ent_dst, pool->ent_src,
-                                       pool->ent_val, pool->nnz_cap, d_frame_off,
+                                       pool->ent_val, pool->ent_col, pool->nnz_cap, d_frame_off,
                                        reinterpret_cast<const uint16_t *>(B.p), B.stride, B.off, (int)B.c, po.occ,
                                        po.occ_base, po.cmp, s);
                 if (rc) return rc;
@@ -1680,7 +1707,11 @@ int wgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, cons
         SHPL_LAUNCH_CHECK();
     }
     const dim3 grid((unsigned)wp.n_groups, (unsigned)wp.n_cib, (unsigned)pl.n_cob);
-    const auto kernel = dtype == SHPL_F32 ? (pooled ? k_conv3x3_wgrad<float, true> : k_conv3x3_wgrad<float, false>)
+    const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
+    const auto kernel = dtype == SHPL_F32 ? (group    ? k_conv3x3_wgrad<float, true, true>
+                                             : pooled ? k_conv3x3_wgrad<float, true>
+                                                      : k_conv3x3_wgrad<float, false>)
+                        : group           ? k_conv3x3_wgrad<uint16_t, true, true>
                         : pooled          ? k_conv3x3_wgrad<uint16_t, true>
                                           : k_wgrad_bf16;
     hipLaunchKernelGGL(kernel, grid, dim3(CONV_BLOCK), 0, s, a, g);

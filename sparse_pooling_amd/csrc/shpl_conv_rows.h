@@ -37,12 +37,13 @@ struct RowArgs {
 bool supported(int q, int qa);
 bool supported_st(int q, int qa, bool cmp);
 
-// Occupancy words + prefix counts of the cell-keyed CSR per frame, then the
-// pooled vector of every run into its compact row (shpl_pull's arithmetic).
+// Occupancy words + prefix counts of the pool's CSR per frame (cell-keyed, or pixel-keyed: the keys are then
+// the image's pixels), then the pooled vector of every run into its compact row (shpl_pull's arithmetic;
+// ent_col set: the pixel-keyed CSR's per-column partials, NULL: the plain sum in entry order).
 int prep_pooled(int n_frames, int h, int w, int wpr, const int32_t *ent_dst, const int32_t *ent_src,
-                const float *ent_val, int64_t nnz_cap, const int64_t *frame_off, const uint16_t *img,
-                int64_t img_stride, int64_t img_off, int c_b, uint32_t *occ, int32_t *occ_base, uint16_t *cmp,
-                hipStream_t s);
+                const float *ent_val, const int32_t *ent_col, int64_t nnz_cap, const int64_t *frame_off,
+                const uint16_t *img, int64_t img_stride, int64_t img_off, int c_b, uint32_t *occ, int32_t *occ_base,
+                uint16_t *cmp, hipStream_t s);
 
 // The conv: n_items * n_cob one-wave workgroups (ST: also the per-item
 // channel sums of the pre-activation output, for k_stats_reduce).

@@ -241,10 +241,12 @@ __global__ __launch_bounds__(1024) void k_occ_frame(const int32_t *ent_dst, cons
 // frame_off[f] + (run rank in frame f): one thread per entry; the thread on a
 // run's first entry sums the run in entry order with separate multiply and add
 // from 0 and rounds once per channel -- shpl_pull's (k_sparse's) arithmetic,
-// bit for bit -- all NP 16-byte pieces of each entry's row in flight together.
-template <int NP>
+// bit for bit -- all NP 16-byte pieces of each entry's row in flight together. GROUP: the run is a pixel's
+// of the pixel-keyed CSR (ent_col set) and sums per column first (RunSum: walk_run<GROUP>'s order).
+template <int NP, bool GROUP>
 __global__ __launch_bounds__(SHPL_BLOCK) void k_pool_runs(const int32_t *ent_dst, const int32_t *ent_src,
-                                                          const float *ent_val, int64_t nnz_cap, const uint16_t *img,
+                                                          const float *ent_val, const int32_t *ent_col,
+                                                          int64_t nnz_cap, const uint16_t *img,
                                                           int64_t img_stride, int64_t img_off, int c_b, int H, int W,
                                                           int wpr, const uint32_t *occ, const int32_t *occ_base,
                                                           const int64_t *frame_off, uint16_t *cmp) {
@@ -256,17 +258,15 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_pool_runs(const int32_t *ent_dst
     int32_t dn = e + 1 < nnz_cap ? ent_dst[e + 1] : -1;
     float wv = ent_val[e];
     int32_t src = ent_src[e];
+    int32_t kc = GROUP ? ent_col[e] : 0;
     if (d < 0 || prev == d) return;
     const int64_t cells = (int64_t)H * W;
     const int f = (int)(d / cells);
     const int c = (int)(d - f * cells), y = c / W, x = c - y * W;
     const int64_t wi = ((int64_t)f * H + y) * wpr + (x >> 5);
     const int32_t rid = occ_base[wi] + __popc(occ[wi] & ((1u << (x & 31)) - 1u));
-    float sum[NP][8];
-#pragma unroll
-    for (int g = 0; g < NP; ++g)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sum[g][j] = 0.0f;
+    RunSum<GROUP, NP * 8> sum;
+    sum.init();
     // entry i's row loads go out with entry i+1's index words (one round trip per entry, not two)
     for (int64_t i = e;; ++i) {
         const uint16_t *row = img + (int64_t)src * img_stride + img_off;
@@ -275,30 +275,35 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_pool_runs(const int32_t *ent_dst
         for (int g = 0; g < NP; ++g) raw[g] = *reinterpret_cast<const u32x4 *>(row + g * 8);
         const bool more = dn == d;  // entry i+1 is in the run (dn is -1 past the capacity)
         float wn = 0.0f;
-        int32_t sn = 0, dnn = -1;
+        int32_t sn = 0, dnn = -1, kn = 0;
         if (more) {
             wn = ent_val[i + 1];
             sn = ent_src[i + 1];
+            if (GROUP) kn = ent_col[i + 1];
             dnn = i + 2 < nnz_cap ? ent_dst[i + 2] : -1;
         }
+        float xf[NP * 8];
 #pragma unroll
         for (int g = 0; g < NP; ++g) {
             uint16_t xv[8];
             __builtin_memcpy(xv, &raw[g], 16);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) sum[g][j] = __fadd_rn(sum[g][j], __fmul_rn(wv, bf16_to_f32(xv[j])));
+            for (int j = 0; j < 8; ++j) xf[g * 8 + j] = bf16_to_f32(xv[j]);
         }
+        sum.add(kc, wv, xf);
         if (!more) break;
         wv = wn;
         src = sn;
+        kc = kn;
         dn = dnn;
     }
+    sum.finish();
     uint16_t *o = cmp + (frame_off[f] + rid) * (int64_t)c_b;
 #pragma unroll
     for (int g = 0; g < NP; ++g) {
         uint16_t v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(sum[g][j]);
+        for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(sum.acc[g * 8 + j]);
         *reinterpret_cast<u32x4 *>(o + g * 8) = *reinterpret_cast<u32x4 *>(v);
     }
 }
@@ -1135,9 +1140,9 @@ bool supported_st(int q, int qa, bool cmp) {
 }
 
 int prep_pooled(int n_frames, int h, int w, int wpr, const int32_t *ent_dst, const int32_t *ent_src,
-                const float *ent_val, int64_t nnz_cap, const int64_t *frame_off, const uint16_t *img,
-                int64_t img_stride, int64_t img_off, int c_b, uint32_t *occ, int32_t *occ_base, uint16_t *cmp,
-                hipStream_t s) {
+                const float *ent_val, const int32_t *ent_col, int64_t nnz_cap, const int64_t *frame_off,
+                const uint16_t *img, int64_t img_stride, int64_t img_off, int c_b, uint32_t *occ, int32_t *occ_base,
+                uint16_t *cmp, hipStream_t s) {
     hipLaunchKernelGGL(k_occ_frame, dim3(n_frames), dim3(1024), 0, s, ent_dst, frame_off, h, w, wpr, occ, occ_base);
     SHPL_LAUNCH_CHECK();
     const int np = c_b / 8;
@@ -1145,10 +1150,12 @@ int prep_pooled(int n_frames, int h, int w, int wpr, const int32_t *ent_dst, con
         const dim3 grid((unsigned)((nnz_cap + SHPL_BLOCK - 1) / SHPL_BLOCK));
         switch (np) {
 #define SHPL_POOL_RUNS(NP)                                                                                       \
-    case NP:                                                                                                     \
-        hipLaunchKernelGGL(k_pool_runs<NP>, grid, dim3(SHPL_BLOCK), 0, s, ent_dst, ent_src, ent_val, nnz_cap, img, \
+    case NP: {                                                                                                   \
+        const auto kernel = ent_col ? k_pool_runs<NP, true> : k_pool_runs<NP, false>;                             \
+        hipLaunchKernelGGL(kernel, grid, dim3(SHPL_BLOCK), 0, s, ent_dst, ent_src, ent_val, ent_col, nnz_cap, img, \
                            img_stride, img_off, c_b, h, w, wpr, occ, occ_base, frame_off, cmp);                   \
-        break;
+        break;                                                                                                   \
+    }
             SHPL_POOL_RUNS(1)
             SHPL_POOL_RUNS(2)
             SHPL_POOL_RUNS(3)

@@ -274,11 +274,25 @@ __global__ __launch_bounds__(BLOCK, 2) void k_conv_wide(const WideArgs p) {
     }
 }
 
+// The 8 bf16 channels of a 16-byte piece as f32.
+struct Piece8 { float x[8]; };
+__device__ __forceinline__ Piece8 piece_f32(const u32x4 &raw) {
+    uint16_t xv[8];
+    __builtin_memcpy(xv, &raw, 16);
+    Piece8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r.x[j] = bf16_to_f32(xv[j]);
+    return r;
+}
+
 // The pooled vector of every run of the cell-keyed CSR, piece g, into its compact row frame_off[f] + (run rank
 // in frame f): one thread per (entry, 16-byte piece); the thread on a run's first entry sums the run in entry
-// order with separate multiply and add from 0 and rounds once -- k_sparse's arithmetic, bit for bit.
+// order with separate multiply and add from 0 and rounds once -- k_sparse's arithmetic, bit for bit. GROUP: a
+// pixel-keyed CSR with ent_col, summed per column first (RunSum: walk_run<GROUP>'s order).
+template <bool GROUP>
 __global__ __launch_bounds__(256) void k_pool_runs_wide(const int32_t *ent_dst, const int32_t *ent_src,
-                                                        const float *ent_val, int64_t nnz_cap, const uint16_t *img,
+                                                        const float *ent_val, const int32_t *ent_col,
+                                                        int64_t nnz_cap, const uint16_t *img,
                                                         int64_t img_stride, int64_t img_off, int c_b, int np, int H,
                                                         int W, int wpr, const uint32_t *occ, const int32_t *occ_base,
                                                         const int64_t *frame_off, uint16_t *cmp) {
@@ -291,38 +305,38 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide(const int32_t *ent_dst, 
     int32_t dn = e + 1 < nnz_cap ? ent_dst[e + 1] : -1;
     float wv = ent_val[e];
     int32_t src = ent_src[e];
+    int32_t kc = GROUP ? ent_col[e] : 0;
     if (d < 0 || prev == d) return;
     const int64_t cells = (int64_t)H * W;
     const int f = (int)(d / cells);
     const int c = (int)(d - f * cells), y = c / W, x = c - y * W;
     const int64_t wi = ((int64_t)f * H + y) * wpr + (x >> 5);
     const int32_t rid = occ_base[wi] + __popc(occ[wi] & ((1u << (x & 31)) - 1u));
-    float sum[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum[j] = 0.0f;
+    RunSum<GROUP, 8> sum;
+    sum.init();
     // entry i's row piece goes out with entry i+1's index words (one round trip per entry)
     for (int64_t i = e;; ++i) {
         const u32x4 raw = *reinterpret_cast<const u32x4 *>(img + (int64_t)src * img_stride + img_off + g * 8);
         const bool more = dn == d;
         float wn = 0.0f;
-        int32_t sn = 0, dnn = -1;
+        int32_t sn = 0, dnn = -1, kn = 0;
         if (more) {
             wn = ent_val[i + 1];
             sn = ent_src[i + 1];
+            if (GROUP) kn = ent_col[i + 1];
             dnn = i + 2 < nnz_cap ? ent_dst[i + 2] : -1;
         }
-        uint16_t xv[8];
-        __builtin_memcpy(xv, &raw, 16);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sum[j] = __fadd_rn(sum[j], __fmul_rn(wv, bf16_to_f32(xv[j])));
+        sum.add(kc, wv, piece_f32(raw).x);
         if (!more) break;
         wv = wn;
         src = sn;
+        kc = kn;
         dn = dnn;
     }
+    sum.finish();
     uint16_t v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(sum[j]);
+    for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(sum.acc[j]);
     *reinterpret_cast<u32x4 *>(cmp + (frame_off[f] + rid) * (int64_t)c_b + g * 8) = *reinterpret_cast<u32x4 *>(v);
 }
 
@@ -330,13 +344,14 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide(const int32_t *ent_dst, 
 // their K row pieces in flight together (the runs of a cell are mostly one entry long, so a thread per entry
 // spent a round trip per index word and per row with little else in flight); each run head sums its run in
 // entry order from 0 with separate multiply and add, as k_pool_runs_wide does -- bit for bit -- walking on past
-// the group when the run does.
+// the group when the run does. GROUP: as k_pool_runs_wide's.
 #ifndef SHPL_WIDE_RUNS_K
 #define SHPL_WIDE_RUNS_K 4  // 1: k_pool_runs_wide (a thread per entry and piece)
 #endif
-template <int K>
+template <int K, bool GROUP>
 __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst, const int32_t *ent_src,
-                                                          const float *ent_val, int64_t nnz_cap, const uint16_t *img,
+                                                          const float *ent_val, const int32_t *ent_col,
+                                                          int64_t nnz_cap, const uint16_t *img,
                                                           int64_t img_stride, int64_t img_off, int c_b, int np, int H,
                                                           int W, int wpr, const uint32_t *occ,
                                                           const int32_t *occ_base, const int64_t *frame_off,
@@ -346,7 +361,7 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst
     const int g = (int)(t - grp * np);
     const int64_t e0 = grp * K;
     if (e0 >= nnz_cap) return;
-    int32_t d[K + 1], src[K];
+    int32_t d[K + 1], src[K], kc[K];
     float wv[K];
     const int32_t prev0 = e0 > 0 ? ent_dst[e0 - 1] : -1;
 #pragma unroll
@@ -356,6 +371,7 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst
         const bool in = e0 + k < nnz_cap;
         wv[k] = in ? ent_val[e0 + k] : 0.0f;
         src[k] = in ? ent_src[e0 + k] : 0;
+        kc[k] = GROUP && in ? ent_col[e0 + k] : 0;
     }
     u32x4 raw[K];
 #pragma unroll
@@ -366,9 +382,8 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (d[k] < 0 || d[k] == (k ? d[k - 1] : prev0)) continue;  // not a run head
-        float sum[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sum[j] = 0.0f;
+        RunSum<GROUP, 8> sum;
+        sum.init();
         bool tail = true;  // the run reaches past the group
 #pragma unroll
         for (int m = k; m < K; ++m) {
@@ -376,33 +391,30 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst
                 tail = false;
                 break;
             }
-            uint16_t xv[8];
-            __builtin_memcpy(xv, &raw[m], 16);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sum[j] = __fadd_rn(sum[j], __fmul_rn(wv[m], bf16_to_f32(xv[j])));
+            sum.add(kc[m], wv[m], piece_f32(raw[m]).x);
         }
         if (tail && d[K] == d[k]) {  // entries e0 + K, ... of the same cell, one round trip each
             int64_t i = e0 + K;
             float w = ent_val[i];
             int32_t sr = ent_src[i];
+            int32_t kt = GROUP ? ent_col[i] : 0;
             int32_t dn = i + 1 < nnz_cap ? ent_dst[i + 1] : -1;
             for (;; ++i) {
                 const u32x4 r = *reinterpret_cast<const u32x4 *>(img + (int64_t)sr * img_stride + img_off + g * 8);
                 const bool more = dn == d[k];
                 float wn = 0.0f;
-                int32_t sn = 0, dnn = -1;
+                int32_t sn = 0, dnn = -1, kn = 0;
                 if (more) {
                     wn = ent_val[i + 1];
                     sn = ent_src[i + 1];
+                    if (GROUP) kn = ent_col[i + 1];
                     dnn = i + 2 < nnz_cap ? ent_dst[i + 2] : -1;
                 }
-                uint16_t xv[8];
-                __builtin_memcpy(xv, &r, 16);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sum[j] = __fadd_rn(sum[j], __fmul_rn(w, bf16_to_f32(xv[j])));
+                sum.add(kt, w, piece_f32(r).x);
                 if (!more) break;
                 w = wn;
                 sr = sn;
+                kt = kn;
                 dn = dnn;
             }
         }
@@ -410,9 +422,10 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst
         const int c = (int)(d[k] - f * cells), y = c / W, x = c - y * W;
         const int64_t wi = ((int64_t)f * H + y) * wpr + (x >> 5);
         const int32_t rid = occ_base[wi] + __popc(occ[wi] & ((1u << (x & 31)) - 1u));
+        sum.finish();
         uint16_t v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(sum[j]);
+        for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(sum.acc[j]);
         *reinterpret_cast<u32x4 *>(cmp + (frame_off[f] + rid) * (int64_t)c_b + g * 8) = *reinterpret_cast<u32x4 *>(v);
     }
 }
@@ -420,24 +433,25 @@ __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst
 }  // namespace
 
 int prep(int n_frames, int h, int w, int wpr, const int32_t *ent_dst, const int32_t *ent_src, const float *ent_val,
-         int64_t nnz_cap, const int64_t *frame_off, const uint16_t *img, int64_t img_stride, int64_t img_off, int c_b,
-         uint32_t *occ, int32_t *occ_base, uint16_t *cmp, hipStream_t s) {
+         const int32_t *ent_col, int64_t nnz_cap, const int64_t *frame_off, const uint16_t *img, int64_t img_stride,
+         int64_t img_off, int c_b, uint32_t *occ, int32_t *occ_base, uint16_t *cmp, hipStream_t s) {
     // the occupancy words alone (no pooled channels: rows::prep_pooled's k_occ_frame)
-    int rc = rows::prep_pooled(n_frames, h, w, wpr, ent_dst, ent_src, ent_val, nnz_cap, frame_off, img, img_stride,
-                               img_off, 0, occ, occ_base, cmp, s);
+    int rc = rows::prep_pooled(n_frames, h, w, wpr, ent_dst, ent_src, ent_val, ent_col, nnz_cap, frame_off, img,
+                               img_stride, img_off, 0, occ, occ_base, cmp, s);
     if (rc) return rc;
     const int np = c_b / 8;
     if (nnz_cap > 0 && np > 0 && SHPL_WIDE_RUNS_K > 1) {
         const int64_t threads = (nnz_cap + SHPL_WIDE_RUNS_K - 1) / SHPL_WIDE_RUNS_K * np;
-        hipLaunchKernelGGL(k_pool_runs_wide_k<SHPL_WIDE_RUNS_K>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                           s, ent_dst, ent_src, ent_val, nnz_cap, img, img_stride, img_off, c_b, np, h, w, wpr, occ,
-                           occ_base, frame_off, cmp);
+        const auto kernel = ent_col ? k_pool_runs_wide_k<SHPL_WIDE_RUNS_K, true>
+                                    : k_pool_runs_wide_k<SHPL_WIDE_RUNS_K, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ent_dst, ent_src, ent_val,
+                           ent_col, nnz_cap, img, img_stride, img_off, c_b, np, h, w, wpr, occ, occ_base, frame_off, cmp);
         SHPL_LAUNCH_CHECK();
     } else if (nnz_cap > 0 && np > 0) {
         const int64_t threads = nnz_cap * np;
-        hipLaunchKernelGGL(k_pool_runs_wide, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ent_dst,
-                           ent_src, ent_val, nnz_cap, img, img_stride, img_off, c_b, np, h, w, wpr, occ, occ_base,
-                           frame_off, cmp);
+        const auto kernel = ent_col ? k_pool_runs_wide<true> : k_pool_runs_wide<false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ent_dst, ent_src, ent_val,
+                           ent_col, nnz_cap, img, img_stride, img_off, c_b, np, h, w, wpr, occ, occ_base, frame_off, cmp);
         SHPL_LAUNCH_CHECK();
     }
     return SHPL_OK;

@@ -25,9 +25,18 @@ the device too: BatchNorm/ReLU backward, the input gradient (the same conv
 kernel on transposed weights) and the weight gradient (an MFMA reduction over
 pixels that recomputes the pooled channels from the CSR), then the SHPL pull
 that carries the pooled channels' gradient back to the image map.
+
+``FusionConv.fused_img(img, bev, smap)`` is the image side's conv of
+[img || _sparse_pool_trans_op(M, bev)] (the dual path of sparse_pool_layer,
+sparse_pool_utils.py:79-87) the same way, from the BEV->img (pixel-keyed) CSR:
+the same kernels with the sides swapped, the pooled sums taken per column of M
+first (TF's ScatterNd order, as shpl_pull SHPL_BY_PIXEL), and the pooled
+channels' gradient pulled back to the BEV map. ``PostFusion`` holds both
+scopes of rpn_model.py:338-354 and issues the two convs side by side.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
@@ -35,6 +44,17 @@ import torch
 
 from . import _lib as L
 from . import shpl_map as sm
+
+
+# The directions of a fused conv: the CSR (direction, order) its forward pools through, the pull that carries the
+# pooled channels' gradient back to the pooled source (the TF gradient of the forward's op), and the pull that
+# materialises the pooled channels (f32 weight gradient).
+_Side = collections.namedtuple("_Side", "fwd grad pool")
+# pyramid_fusion_pooled_bev: [bev || _sparse_pool_op(M, img)]; the gradient returns to the image (a8's TF gradient)
+SIDE_BEV = _Side((L.BY_CELL, L.ORDER_ENTRY), (L.BY_PIXEL, L.ORDER_COL_ENTRY), sm.pool_img_to_bev)
+# pyramid_fusion_pooled_img: [img || _sparse_pool_trans_op(M, bev)]; the gradient returns to the BEV map (the pull
+# of _DualFn.backward)
+SIDE_IMG = _Side((L.BY_PIXEL, L.ORDER_COL_ROW), (L.BY_CELL, L.ORDER_COL_ENTRY), sm.pool_bev_to_img)
 
 
 def conv_ws_bytes(dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap, stats):
@@ -71,7 +91,9 @@ def conv3x3(a, weights, b=None, pool=None, frame_off=None, center=None, scale=No
     a: [B,H,W,Ca] NHWC (f32 or bf16); weights: HWIO [3,3,Ca+Cb,Cout] of the
     same dtype; b: a second dense map [B,H,W,Cb], or -- with ``pool`` (the
     cell-keyed ``_lib.Csr`` of an img->BEV map) and ``frame_off`` -- the image
-    map [Bi,Hi,Wi,Cb] that is pooled on the fly; stats: optional [2,Cout]
+    map [Bi,Hi,Wi,Cb] that is pooled on the fly (a the BEV map); with the
+    pixel-keyed CSR (BY_PIXEL, ORDER_COL_ROW) a is the image map and b the BEV
+    map [Bb,Hb,Wb,Cb] pooled to the image; stats: optional [2,Cout]
     float64 tensor receiving per-channel sum / sum of squares of the
     pre-epilogue output."""
     dt = L.dtype_code(a)
@@ -149,8 +171,9 @@ def conv3x3_dgrad(gy, weights, c_dx, split=None, pool=None, fwd_ws=None, fwd_sta
     with ``split`` = c, the pair (channels [0, c), channels [c, c_dx)) as two
     dense maps written by the kernel's epilogue (no slicing copies). ``fwd_ws`` (with ``pool``, the pooled bf16
     forward's CSR, and ``split``): the workspace of that forward conv3x3 (taken with statistics: fwd_stats),
-    whose occupancy words limit the second map to the occupied cells -- the only rows the pixel-keyed pull
-    back to the image reads; its other cells are left unwritten (shpl_conv3x3_dgrad_reuse)."""
+    whose occupancy words limit the second map to the occupied cells (pixels, for a pixel-keyed pool) -- the
+    only rows the pull back to the pooled source reads; its other rows are left unwritten
+    (shpl_conv3x3_dgrad_reuse)."""
     gy = gy.contiguous()
     B, H, W, Cg = (int(s) for s in gy.shape)
     weights = weights.to(gy.dtype).contiguous()
@@ -200,26 +223,27 @@ def conv3x3_wgrad(a, gy, b=None, pool=None, frame_off=None, fwd_ws=None, fwd_sta
 
 class _FusionConvFn(torch.autograd.Function):
     """FusionConv forward + its TF-autodiff backward, all on the device.
-    Inputs: a [B,H,W,Ca]; b: a dense [B,H,W,Cb], or the image map pooled
-    through smap (pooled=True), or None; the conv weights; beta / bias."""
+    Inputs: a [B,H,W,Ca]; b: a dense [B,H,W,Cb], or None, or -- with side (SIDE_BEV: a the BEV map, SIDE_IMG:
+    a the image map) -- the other map, pooled through smap; the conv weights; beta / bias."""
 
     @staticmethod
-    def forward(ctx, a, b, weights, beta, bias, conv, smap, pooled, is_training, out):
+    def forward(ctx, a, b, weights, beta, bias, conv, smap, side, is_training, out):
+        pooled = side is not None
         a = a.contiguous()
         b = None if b is None else b.contiguous()
         B, H, W, Ca = (int(s) for s in a.shape)
         Cb = 0 if b is None else int(b.shape[-1])
         dt = L.dtype_code(a)
-        pool = smap.csr(L.BY_CELL, L.ORDER_ENTRY) if pooled else None
+        pool = smap.csr(*side.fwd) if pooled else None
         frame_off = smap.frame_off if pooled else None
         train_bn = conv.batch_norm and is_training
-        if pooled and ctx.needs_input_grad[1]:  # the image gradient's pixel-keyed CSR sorts beside the forward
-            smap.prefetch_csr(L.BY_PIXEL, L.ORDER_COL_ENTRY)
+        if pooled and ctx.needs_input_grad[1]:  # the pooled source's gradient's CSR sorts beside the forward
+            smap.prefetch_csr(*side.grad)
         xb, b_img = None, b
         if pooled and train_bn and ctx.needs_input_grad[2] and a.dtype != torch.bfloat16:
             # f32: the weight gradient needs the pooled channels in HBM (see backward): pooled here, once, the
             # forward is the dense two-source conv (bf16 pools inside both convs: k_conv_rows / k_wgrad_rows)
-            xb = sm.pool_img_to_bev(smap, b, (B, H, W, Cb))
+            xb = side.pool(smap, b, (B, H, W, Cb))
             b, pool, frame_off = xb, None, None
         cap = pool.nnz_cap if pool is not None else None
         # bf16 pooled with a weight gradient to come: a workspace of this call's own, kept for the backward,
@@ -252,7 +276,7 @@ class _FusionConvFn(torch.autograd.Function):
                              ws=bn_ws)
             conv._refresh_scale()  # the moving statistics were updated through their device pointers
             mean, scale = bn_ws[:conv.c_out], bn_ws[conv.c_out:]
-        ctx.conv, ctx.smap, ctx.pooled, ctx.train_bn = conv, smap, pooled, train_bn
+        ctx.conv, ctx.smap, ctx.pooled, ctx.side, ctx.train_bn = conv, smap, pooled, side, train_bn
         ctx.shapes = (Ca, Cb)
         ctx.xb = xb
         b = b_img
@@ -264,7 +288,7 @@ class _FusionConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         a, b, weights, y, raw, mean, scale, beta = ctx.saved_tensors
-        conv, smap, pooled = ctx.conv, ctx.smap, ctx.pooled
+        conv, smap, pooled, dirs = ctx.conv, ctx.smap, ctx.pooled, ctx.side
         Ca, Cb = ctx.shapes
         gy = gy.contiguous().to(a.dtype)
         if conv.batch_norm or conv.bias is not None or conv.relu:
@@ -295,7 +319,7 @@ class _FusionConvFn(torch.autograd.Function):
             with torch.cuda.stream(side):
                 if zero_side:
                     # (the dense half reads no source rows: any aligned map stands in for dx_b, not written yet)
-                    sm.pull(smap, L.BY_PIXEL, L.ORDER_COL_ENTRY, d_b, Cb, 0, Cb, d_b, Cb, part="dense")
+                    sm.pull(smap, *dirs.grad, d_b, Cb, 0, Cb, d_b, Cb, part="dense")
                     zeros_done = torch.cuda.Event()
                     zeros_done.record(side)
                 if wgrad_side:
@@ -309,7 +333,7 @@ class _FusionConvFn(torch.autograd.Function):
             else:  # the epilogue writes the two sources' gradients as separate dense maps
                 occ = pooled and ctx.fwd_ws is not None and conv.DGRAD_OCC and ctx.needs_input_grad[1]
                 d_a, dx_b = conv3x3_dgrad(g_raw, weights, Ca + Cb, split=Ca,
-                                          pool=smap.csr(L.BY_CELL, L.ORDER_ENTRY) if occ else None,
+                                          pool=smap.csr(*dirs.fwd) if occ else None,
                                           fwd_ws=ctx.fwd_ws if occ else None, fwd_stats=ctx.train_bn)
                 if ctx.needs_input_grad[1]:
                     if late_zero:
@@ -318,16 +342,16 @@ class _FusionConvFn(torch.autograd.Function):
                         side.wait_stream(cur)
                         d_b = torch.empty(b.shape, dtype=a.dtype, device=a.device)
                         with torch.cuda.stream(side):
-                            sm.pull(smap, L.BY_PIXEL, L.ORDER_COL_ENTRY, d_b, Cb, 0, Cb, d_b, Cb, part="dense")
-                            sm.pull(smap, L.BY_PIXEL, L.ORDER_COL_ENTRY, dx_b, Cb, 0, Cb, d_b, Cb, part="sparse")
+                            sm.pull(smap, *dirs.grad, d_b, Cb, 0, Cb, d_b, Cb, part="dense")
+                            sm.pull(smap, *dirs.grad, dx_b, Cb, 0, Cb, d_b, Cb, part="sparse")
                         for t in (dx_b, d_b):
                             t.record_stream(side)
                     elif pooled and zeros_done is not None:  # its zero rows are on the side stream already
                         cur.wait_event(zeros_done)
-                        sm.pull(smap, L.BY_PIXEL, L.ORDER_COL_ENTRY, dx_b, Cb, 0, Cb, d_b, Cb, part="sparse")
-                    elif pooled:  # the pooled channels' gradient back to the image (a8's TF gradient)
+                        sm.pull(smap, *dirs.grad, dx_b, Cb, 0, Cb, d_b, Cb, part="sparse")
+                    elif pooled:  # the pooled channels' gradient back to the pooled source (_Side.grad)
                         d_b = torch.empty(b.shape, dtype=dx_b.dtype, device=dx_b.device)
-                        sm.pull(smap, L.BY_PIXEL, L.ORDER_COL_ENTRY, dx_b, Cb, 0, Cb, d_b, Cb)
+                        sm.pull(smap, *dirs.grad, dx_b, Cb, 0, Cb, d_b, Cb)
                     else:
                         d_b = dx_b
             if not ctx.needs_input_grad[0]:
@@ -349,13 +373,13 @@ class _FusionConvFn(torch.autograd.Function):
         smap, pooled = ctx.smap, ctx.pooled
         if pooled and a.dtype == torch.bfloat16:
             # k_wgrad_rows gathers the pooled rows from a compact per-run buffer: bv_fused never stored
-            dw = conv3x3_wgrad(a, g_raw, b=b, pool=smap.csr(L.BY_CELL, L.ORDER_ENTRY), frame_off=smap.frame_off,
+            dw = conv3x3_wgrad(a, g_raw, b=b, pool=smap.csr(*ctx.side.fwd), frame_off=smap.frame_off,
                                fwd_ws=ctx.fwd_ws, fwd_stats=ctx.train_bn)
         elif pooled:
             # f32: the pooled channels once into HBM (shpl_pull): the dense two-source weight gradient
             # runs at twice the waves per SIMD of the one that recomputes them per tile (257 vs
             # 214 registers); conv3x3_wgrad(..., pool=...) stays the memory-lean form
-            xb = ctx.xb if ctx.xb is not None else sm.pool_img_to_bev(smap, b, tuple(a.shape[:3]) + (ctx.shapes[1],))
+            xb = ctx.xb if ctx.xb is not None else ctx.side.pool(smap, b, tuple(a.shape[:3]) + (ctx.shapes[1],))
             dw = conv3x3_wgrad(a, g_raw, b=xb)
         else:
             dw = conv3x3_wgrad(a, g_raw, b=b)
@@ -463,7 +487,7 @@ class FusionConv:
     def __call__(self, x, is_training=False, out=None):
         """The conv of a materialised map (bv_fused, img_fused, or img)."""
         if self._grad_wanted(x):
-            return _FusionConvFn.apply(x, None, self.weights, self.beta, self.bias, self, None, False, is_training,
+            return _FusionConvFn.apply(x, None, self.weights, self.beta, self.bias, self, None, None, is_training,
                                        out)
         return self._run(x, None, None, None, is_training, out)
 
@@ -472,12 +496,73 @@ class FusionConv:
         concat: ``smap`` is the ShplMap of the frames of ``bev``. Differentiable
         in bev, img, the weights and beta / bias."""
         if self._grad_wanted(bev, img):
-            return _FusionConvFn.apply(bev, img, self.weights, self.beta, self.bias, self, smap, True, is_training,
-                                       out)
-        return self.fused_csr(bev, img, smap.csr(L.BY_CELL, L.ORDER_ENTRY), smap.frame_off, is_training, out)
+            return _FusionConvFn.apply(bev, img, self.weights, self.beta, self.bias, self, smap, SIDE_BEV,
+                                       is_training, out)
+        return self.fused_csr(bev, img, smap.csr(*SIDE_BEV.fwd), smap.frame_off, is_training, out)
 
     def fused_csr(self, bev, img, csr, frame_off, is_training=False, out=None):
         """fused() over an already built cell-keyed CSR (``_lib.Csr``) and the
         per-frame entry slots ``frame_off`` (FusedPipeline.csr / .frame_off);
         forward only."""
         return self._run(bev, img, csr, frame_off, is_training, out)
+
+    def fused_img(self, img, bev, smap, is_training=False, out=None):
+        """The conv of [img || _sparse_pool_trans_op(M, bev)] (img_fused of the dual
+        sparse_pool_layer) without writing the concat: ``smap`` is the ShplMap of the
+        frames of ``img``. Differentiable in img, bev, the weights and beta / bias."""
+        if int(bev.numel()) // max(int(bev.shape[-1]), 1) != smap.n_cells:
+            raise ValueError(f"BEV map {tuple(bev.shape)} has {int(bev.numel()) // max(int(bev.shape[-1]), 1)} rows, "
+                             f"the map {smap.n_cells} cells")
+        if self._grad_wanted(img, bev):
+            return _FusionConvFn.apply(img, bev, self.weights, self.beta, self.bias, self, smap, SIDE_IMG,
+                                       is_training, out)
+        return self.fused_img_csr(img, bev, smap.csr(*SIDE_IMG.fwd), smap.frame_off, is_training, out)
+
+    def fused_img_csr(self, img, bev, csr, frame_off, is_training=False, out=None):
+        """fused_img() over an already built pixel-keyed CSR (``_lib.Csr``: BY_PIXEL, ORDER_COL_ROW, with ent_col
+        or flagged identity columns) and the per-frame entry slots ``frame_off`` (FusedPipeline.pcsr /
+        .frame_off); forward only."""
+        return self._run(img, bev, csr, frame_off, is_training, out)
+
+
+class PostFusion:
+    """Both convs that follow the SHPL under rpn_sparse_pooling_conv_after_fusion (rpn_model.py:338-354):
+    ``pyramid_fusion_pooled_bev`` over bv_fused = [bev || pool(img)] and ``pyramid_fusion_pooled_img`` over
+    img_fused -- [img || trans(bev)] for a dual layer, img itself otherwise (bv_index=None, the RPN's own call).
+    ``dual`` fixes the image conv's input channels, as it fixes the graph in the reference. depths: the output
+    channels (bev conv, img conv); default the reference's feature_depths = (c_img, c_bev)."""
+
+    def __init__(self, c_bev, c_img, depths=None, dual=True, dtype=torch.float32, device="cuda", seed=0, **kw):
+        d_bev, d_img = (c_img, c_bev) if depths is None else depths
+        self.c_bev, self.c_img, self.dual = int(c_bev), int(c_img), bool(dual)
+        self.bev = FusionConv(c_bev + c_img, d_bev, dtype=dtype, device=device, seed=seed, **kw)
+        self.img = FusionConv(c_img + (c_bev if dual else 0), d_img, dtype=dtype, device=device, seed=seed + 1, **kw)
+        self._side = None
+
+    def __call__(self, bev, img, smap, dual=None, is_training=False):
+        """(bev_out, img_out): the BEV conv on the current stream, the image conv on the module's side stream,
+        which the current stream then waits for. Gradients into bev and img from the two convs add in autograd."""
+        dual = self.dual if dual is None else bool(dual)
+        if dual != self.dual:
+            raise ValueError(f"this PostFusion's image conv was built for dual={self.dual}")
+        cur = torch.cuda.current_stream(bev.device)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=bev.device)
+        side = self._side
+        if dual:  # both CSRs on the current stream, before the fork: the map builds each once, stream-ordered
+            smap.csr(*SIDE_IMG.fwd)
+        smap.csr(*SIDE_BEV.fwd)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            img_out = self._img_conv(img, bev, smap, is_training)
+        bev_out = self.bev.fused(bev, img, smap, is_training)
+        for t in (bev, img, self.img.weights):
+            t.record_stream(side)
+        cur.wait_stream(side)
+        img_out.record_stream(cur)
+        return bev_out, img_out
+
+    def _img_conv(self, img, bev, smap, is_training):
+        if not self.dual:
+            return self.img(img, is_training)
+        return self.img.fused_img(img, bev, smap, is_training)
