@@ -1,8 +1,8 @@
 """Per-kernel diff of two `hipcc -S --cuda-device-only` outputs: device_asm_diff.py PARENT.s NEW.s
 
 For a refactor of a kernel source that must leave the device code alone. Each file is split at the
-`Begin function` / `End function` markers; the function index in local labels is normalised and whitespace
-collapsed. Per kernel: identical, or differing with the four resource fields of its descriptor and whether the
+`Begin function` / `End function` markers; the function index in local labels (and in the comments that name
+them: it moves with the order of instantiation) is normalised and whitespace collapsed. Per kernel: identical, or differing with the four resource fields of its descriptor and whether the
 row kernels' loop -- from the first marked ring wait (`s_waitcnt vmcnt(K) expcnt(6)`) to the exit marker
 (`... expcnt(5)`), register numbers masked -- is the same line for line. Exit status 1 when a kernel differs
 or exists on one side only.
@@ -23,6 +23,7 @@ def kernels(path):
         if name is None:
             continue
         line = re.sub(r"\.L(BB|func_begin|func_end|tmp)\d+", r".L\1N", " ".join(line.split()))
+        line = re.sub(r"\bBB\d+_", "BBN_", line)  # the same index in the loop comments (Header=BB12_3)
         if line:
             out[name].append(line)
         if ".end_amdhsa_kernel" in line:

@@ -1,6 +1,7 @@
 """Tuning sweep of the pull kernel on the GPU box: times compile-time variants
 of libshpl (built by `python scripts/pull_sweep.py --build`) on the bench
-workload (64 config-2 frames). Also calibrates the box's copy bandwidth."""
+workload (64 config-2 frames). Also calibrates the box's copy bandwidth.
+Its variants predate the current shpl_pull.hip (the switches are gone; result: profiles/r01_pull_sweep.log)."""
 import argparse
 import ctypes
 import glob

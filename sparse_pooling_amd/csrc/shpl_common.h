@@ -21,6 +21,10 @@
 
 namespace shpl {
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // one 16-byte piece
+
+inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
+
 // Number of set bits of `mask` in lanes below this lane (wave64).
 // Wave-wide integer sum and inclusive scan (the device library's DPP / swizzle forms: a chain of ds_bpermute
 // shuffles per value was most of the aggregate reads' time in k_index1). Integer sums: any order, same result.
@@ -236,9 +240,8 @@ namespace {
 // shape measured 6.7 TB/s, scripts/calib.hip). Sizes in 8-byte words.
 __global__ __launch_bounds__(SHPL_BLOCK) void k_zero_fill(uint64_t *p, uint64_t n8) {
     const uint64_t i = (uint64_t)blockIdx.x * SHPL_BLOCK + threadIdx.x;
-    typedef uint32_t u32x4z __attribute__((ext_vector_type(4)));
     if (2 * i + 1 < n8) {
-        __builtin_nontemporal_store(u32x4z{0u, 0u, 0u, 0u}, reinterpret_cast<u32x4z *>(p) + i);
+        __builtin_nontemporal_store(u32x4{0u, 0u, 0u, 0u}, reinterpret_cast<u32x4 *>(p) + i);
     } else if (2 * i < n8) {
         p[2 * i] = 0;  // an odd word count's last word
     }

@@ -1,16 +1,12 @@
 // shpl_conv_bn.h -- the few pieces the conv (shpl_conv.hip) and BatchNorm (shpl_bn.hip) share: the element
-// conversions, the deterministic sums of their f64 partials, the 16-byte alignment test.
+// conversions, the deterministic sums of their f64 partials.
 #pragma once
 
 #include "shpl_common.h"
 
 namespace shpl {
 
-inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
-
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // One chunk = the input channels staged per LDS round, 32 B per pixel: 8
 // f32 channels (4 f32 MFMAs of K=2 per tap) or 16 bf16 channels (one bf16

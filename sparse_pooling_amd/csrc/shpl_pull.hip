@@ -19,25 +19,20 @@
 // The zeros k_dense writes into occupied rows are rewritten by k_sparse:
 // nnz*16 B per chunk column (about 1 % of the stream at config 2), against a
 // read-before-write occupancy test that cost ~17 % of the stream (measured,
-// scripts/pull_sweep.py).
+// profiles/r01_pull_sweep.log).
 //
 // Work unit: one 16-byte chunk (4 f32 / 8 bf16); a 64-lane wave stores 1 KiB
 // contiguous. k_dense is a full grid, one chunk per thread (no grid-stride
 // loop): the fastest streaming shape measured on MI355X for this traffic
 // (read 1 : write 2) -- see DESIGN.md.
-#include "shpl_common.h"
+#include <algorithm>
+#include <type_traits>
 
-#ifndef SHPL_NT_LOAD
-#define SHPL_NT_LOAD 1
-#endif
-#ifndef SHPL_NT_STORE
-#define SHPL_NT_STORE 1
-#endif
+#include "shpl_common.h"
 
 namespace shpl {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 
@@ -66,18 +61,10 @@ struct Chunk {
 
     static __device__ __forceinline__ raw_t load(const T *p) { return *reinterpret_cast<const raw_t *>(p); }
     static __device__ __forceinline__ raw_t load_nt(const T *p) {
-#if SHPL_NT_LOAD
         return __builtin_nontemporal_load(reinterpret_cast<const raw_t *>(p));
-#else
-        return *reinterpret_cast<const raw_t *>(p);
-#endif
     }
     static __device__ __forceinline__ void store_nt(T *p, raw_t v) {
-#if SHPL_NT_STORE
         __builtin_nontemporal_store(v, reinterpret_cast<raw_t *>(p));
-#else
-        *reinterpret_cast<raw_t *>(p) = v;
-#endif
     }
     static __device__ __forceinline__ void to_f32(raw_t r, float (&x)[VEC]) {
         T e[VEC];
@@ -214,10 +201,7 @@ __device__ __forceinline__ void fma_free_accumulate(float (&acc)[VEC], float w, 
     for (int j = 0; j < VEC; ++j) acc[j] = __fadd_rn(acc[j], __fmul_rn(w, x[j]));
 }
 
-#ifndef SHPL_WALK
-#define SHPL_WALK 2
-#endif
-constexpr int WALK = SHPL_WALK;
+constexpr int WALK = 2;  // entries per step of k_sparse's walk
 // Runs longer than LONG_RUN entries (config 3: up to 54 image points on one
 // pixel) are left to k_sparse_long, which batches LONG_WALK entries per
 // feature round trip with the index words staged in LDS; k_sparse then never walks more than LONG_RUN / WALK
@@ -225,28 +209,36 @@ constexpr int WALK = SHPL_WALK;
 constexpr int LONG_RUN = 8;
 constexpr int LONG_WALK = 16;
 
-// Sum of one destination's run starting at sorted entry s, chunk c (VEC
-// elements of the pooled part), in TF-CPU order: entries in CSR order with
-// separate multiply and add; GROUP (BY_PIXEL): per column partial Q[k] first
-// (ScatterNd's order). W entries per step: their index loads, then their
-// feature loads, are each in flight together.
-// Index words of W consecutive entries from i (past nnz: dst -1).
+// Index words of sorted entry i: destination, source row, weight, column (GROUP; else 0). Past the capacity:
+// destination -1, the rest 0.
+template <bool GROUP>
+__device__ __forceinline__ void idx_at(const Ents &e, int64_t i, int32_t &d, int32_t &sr, float &w, int32_t &kc) {
+    const bool ok = i < e.n;
+    d = ok ? e.dst[i] : -1;
+    sr = ok ? e.src[i] : 0;
+    w = ok ? e.val[i] : 0.0f;
+    kc = (GROUP && ok) ? e.col[i] : 0;
+}
+
+// Index words of W consecutive entries from i.
 template <bool GROUP, int W>
 struct IdxBatch {
     int32_t d[W], sr[W], kc[W];
     float w[W];
     __device__ __forceinline__ void load(const Ents &e, int64_t i) {
 #pragma unroll
-        for (int u = 0; u < W; ++u) {
-            const bool ok = i + u < e.n;
-            d[u] = ok ? e.dst[i + u] : -1;
-            sr[u] = ok ? e.src[i + u] : 0;
-            w[u] = ok ? e.val[i + u] : 0.0f;
-            kc[u] = (GROUP && ok) ? e.col[i + u] : 0;
-        }
+        for (int u = 0; u < W; ++u) idx_at<GROUP>(e, i + u, d[u], sr[u], w[u], kc[u]);
     }
 };
 
+// Sum of one destination's run starting at sorted entry s, chunk c (VEC
+// elements of the pooled part), in TF-CPU order: entries in CSR order with
+// separate multiply and add; GROUP (BY_PIXEL): per column partial Q[k] first
+// (ScatterNd's order). W entries per step: their index loads, then their
+// feature loads, are each in flight together.
+// The accumulate step is written out here, in k_sparse_long and in row_walk (RunSum of shpl_common.h is the
+// same arithmetic): through RunSum or a shared function each site's registers moved across an occupancy
+// step (docs/HISTORY.md, the pull refactor).
 template <typename T, int VEC, bool GROUP, int W>
 __device__ __forceinline__ void walk_run(const Feat &f, const Ents &e, int64_t s, int32_t key, uint32_t c,
                                          float (&acc)[VEC], const IdxBatch<GROUP, W> *first = nullptr) {
@@ -260,8 +252,6 @@ __device__ __forceinline__ void walk_run(const Feat &f, const Ents &e, int64_t s
     int32_t kprev = -1;  // no column yet: the first flush adds a zero partial (0 + 0 = +0)
     for (int64_t i = s;; i += W) {
         bool in[W];
-        int32_t d[W], sr[W], kc[W];
-        float w[W];
         // index loads of the batch do not wait for each other (dst need not match yet);
         // the first batch may come preloaded (issued with the caller's head test)
         IdxBatch<GROUP, W> b;
@@ -270,18 +260,11 @@ __device__ __forceinline__ void walk_run(const Feat &f, const Ents &e, int64_t s
         else
             b.load(e, i);
 #pragma unroll
-        for (int u = 0; u < W; ++u) {
-            d[u] = b.d[u];
-            sr[u] = b.sr[u];
-            w[u] = b.w[u];
-            kc[u] = b.kc[u];
-        }
-#pragma unroll
-        for (int u = 0; u < W; ++u) in[u] = d[u] == key && (u == 0 || in[u - 1]);
+        for (int u = 0; u < W; ++u) in[u] = b.d[u] == key && (u == 0 || in[u - 1]);
         typename C::raw_t raw[W];
 #pragma unroll
         for (int u = 0; u < W; ++u)
-            if (in[u]) raw[u] = C::load(sc + (int64_t)sr[u] * f.src_stride);
+            if (in[u]) raw[u] = C::load(sc + (int64_t)b.sr[u] * f.src_stride);
 #pragma unroll
         for (int u = 0; u < W; ++u) {
             if (!in[u]) break;
@@ -289,17 +272,17 @@ __device__ __forceinline__ void walk_run(const Feat &f, const Ents &e, int64_t s
             C::to_f32(raw[u], x);
             if (GROUP) {
                 // TF: Q[k] = sum of column k's entries; out = 0 + Q[k1] + Q[k2] ... (ScatterNd order)
-                if (kc[u] != kprev) {
+                if (b.kc[u] != kprev) {
 #pragma unroll
                     for (int j = 0; j < VEC; ++j) {
                         acc[j] = __fadd_rn(acc[j], q[j]);
                         q[j] = 0.0f;
                     }
-                    kprev = kc[u];
+                    kprev = b.kc[u];
                 }
-                fma_free_accumulate<VEC>(q, w[u], x);
+                fma_free_accumulate<VEC>(q, b.w[u], x);
             } else {
-                fma_free_accumulate<VEC>(acc, w[u], x);
+                fma_free_accumulate<VEC>(acc, b.w[u], x);
             }
         }
         if (!in[W - 1]) break;
@@ -371,35 +354,19 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_sparse(const Feat f, const Ents 
 // sorted entries for wide cell-keyed rows (once_seg), else k_sparse's (entry, chunk) walk over every run; the
 // rest zero the rows whose key_range is empty: a wave per ONCE_ROWS rows, one key_range load for all of them,
 // then their zero chunks stored with nothing to wait for. Rows and stores are disjoint between the two parts.
-#ifndef SHPL_ONCE_ROWS
-#define SHPL_ONCE_ROWS 16
-#endif
-#ifndef SHPL_ONCE_XCD
-#define SHPL_ONCE_XCD 1
-#endif
-#ifndef SHPL_ONCE_ZERO_FIRST
-#define SHPL_ONCE_ZERO_FIRST 1  // the zeroing blocks first: 1.401-1.404 vs 1.408-1.410 ms at config 6 (profiles/r05_once_ab.log)
-#endif
-constexpr int ONCE_ROWS = SHPL_ONCE_ROWS;
-#ifndef SHPL_ONCE_SEG
-#define SHPL_ONCE_SEG 1
-#endif
-#ifndef SHPL_SEG_BATCH
-#define SHPL_SEG_BATCH 8
-#endif
-constexpr int SEG_BATCH = SHPL_SEG_BATCH;
-#ifndef SHPL_SEG_CONT
-#define SHPL_SEG_CONT 2
-#endif
+// The zeroing blocks come first in the grid: 1.401-1.404 vs 1.408-1.410 ms at config 6 with the run-walking
+// blocks first (profiles/r05_once_ab.log).
+constexpr int ONCE_ROWS = 16;
+constexpr int SEG_BATCH = 8;  // gathered rows in flight per step of the window walk
 // entries per step past the window (a run crossing it: rare, short); 2 keeps k_once at 84 VGPRs without spills
 // under its 5-waves bound (8: 136 VGPRs, 3 waves per SIMD, 0.578 vs 0.513-0.520 ms at config 6;
 // profiles/r05_c6c2_ab.log)
-constexpr int SEG_CONT = SHPL_SEG_CONT;
+constexpr int SEG_CONT = 2;
 // the window walk for cell-keyed rows of at least half a wave of chunks (RetinaNet's 256 channels: 64 f32 /
 // 32 bf16 chunks); narrower rows would leave most lanes idle through the window's serial walk (measured as
 // shpl_pull_sparse's form at config 2's 32 channels: 205 vs 80 us)
 __host__ __device__ constexpr bool once_seg(bool group, uint32_t cpool) {
-    return SHPL_ONCE_SEG && !group && cpool >= 32;
+    return !group && cpool >= 32;
 }
 
 template <typename T, int VEC>
@@ -469,16 +436,11 @@ __device__ __forceinline__ void seg_window(const Feat &f, const Ents &e, int64_t
         if (key < 0) continue;
         // the window's last run: on past the window while the destination stays
         for (int64_t t = s0 + SHPL_WAVE;; t += SEG_CONT) {
-            int32_t dd[SEG_CONT], ss[SEG_CONT];
+            int32_t dd[SEG_CONT], ss[SEG_CONT], no_col;
             float ww[SEG_CONT];
             bool in[SEG_CONT];
 #pragma unroll
-            for (int u = 0; u < SEG_CONT; ++u) {
-                const bool okk = t + u < e.n;
-                dd[u] = okk ? e.dst[t + u] : -1;
-                ss[u] = okk ? e.src[t + u] : 0;
-                ww[u] = okk ? e.val[t + u] : 0.0f;
-            }
+            for (int u = 0; u < SEG_CONT; ++u) idx_at<false>(e, t + u, dd[u], ss[u], ww[u], no_col);
 #pragma unroll
             for (int u = 0; u < SEG_CONT; ++u) in[u] = dd[u] == key && (u == 0 || in[u - 1]);
             typename C::raw_t raw[SEG_CONT];
@@ -498,26 +460,18 @@ __device__ __forceinline__ void seg_window(const Feat &f, const Ents &e, int64_t
     }
 }
 
-#ifndef SHPL_ONCE_WPE
-#define SHPL_ONCE_WPE 5  // k_once at 5 waves per SIMD: the zero rows' write-only stream and the window walks
-#endif
+// k_once at 5 waves per SIMD: the zero rows' write-only stream and the window walks
 template <typename T, int VEC, bool GROUP, bool POW2>
-__global__ __launch_bounds__(SHPL_BLOCK)
-#if SHPL_ONCE_WPE
-__attribute__((amdgpu_waves_per_eu(SHPL_ONCE_WPE, SHPL_ONCE_WPE)))
-#endif
-void k_once(const Feat f, const Ents e, int cpool_shift,
-                                                     const int32_t *key_range, int64_t n_rows, int64_t sblocks) {
+__global__ __launch_bounds__(SHPL_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5)))
+void k_once(const Feat f, const Ents e, int cpool_shift, const int32_t *key_range, int64_t n_rows, int64_t sblocks) {
     const int64_t zblocks = (int64_t)gridDim.x - sblocks;
-    const int64_t zb = SHPL_ONCE_ZERO_FIRST ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - sblocks;
-    if (zb < 0 || zb >= zblocks) {
-        int64_t sb = SHPL_ONCE_ZERO_FIRST ? zb - zblocks : (int64_t)blockIdx.x;
-#if SHPL_ONCE_XCD
+    const int64_t zb = blockIdx.x;
+    if (zb >= zblocks) {
+        int64_t sb = zb - zblocks;
         // workgroups go to the 8 XCDs round-robin by id: sb % 8 picks the XCD, so each XCD walks a contiguous
         // eighth of the entries in order and the image rows its neighbouring destinations share stay in its
         // own L2 (the launcher makes sblocks a multiple of 8)
         sb = (sb & 7) * (sblocks >> 3) + (sb >> 3);
-#endif
         if (once_seg(GROUP, f.cpool)) {
             const int64_t wpb = SHPL_BLOCK / SHPL_WAVE;
             for (int64_t win = sb * wpb + (threadIdx.x >> 6); win * SHPL_WAVE < e.n; win += sblocks * wpb)
@@ -593,12 +547,13 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_sparse_long(const Feat f, const 
         if (n_run == 0) continue;  // uniform
         const int64_t base = blk + s_first;
         for (int j = threadIdx.x; j < LONG_IDX; j += SHPL_BLOCK) {
-            const int64_t i = base + j;
-            const bool ok = i < nnz;
-            s_dst[j] = ok ? e.dst[i] : -1;
-            s_src[j] = ok ? e.src[i] : 0;
-            s_val[j] = ok ? e.val[i] : 0.0f;
-            if (GROUP) s_col[j] = ok ? e.col[i] : 0;
+            int32_t d, sr, kc;
+            float w;
+            idx_at<GROUP>(e, base + j, d, sr, w, kc);
+            s_dst[j] = d;
+            s_src[j] = sr;
+            s_val[j] = w;
+            if (GROUP) s_col[j] = kc;
         }
         __syncthreads();
         for (int p = threadIdx.x; p < n_run * (int)f.cpool; p += SHPL_BLOCK) {
@@ -625,11 +580,7 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_sparse_long(const Feat f, const 
                         w[u] = s_val[j];
                         kc[u] = GROUP ? s_col[j] : 0;
                     } else {
-                        const bool ok = x < nnz;
-                        d = ok ? e.dst[x] : -1;
-                        sr[u] = ok ? e.src[x] : 0;
-                        w[u] = ok ? e.val[x] : 0.0f;
-                        kc[u] = (GROUP && ok) ? e.col[x] : 0;
+                        idx_at<GROUP>(e, x, d, sr[u], w[u], kc[u]);
                     }
                     in[u] = d == key && (u == 0 || in[u - 1]);
                 }
@@ -682,13 +633,10 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_sparse_long(const Feat f, const 
 // their latency overlaps the index loads. Trip counts are wave-uniform (the
 // longest run of the wave's rows), so the shuffles always see every lane.
 // Arithmetic is k_sparse's: bitwise the same output as k_dense + k_sparse.
-#ifndef SHPL_ROWS_WALK
-#define SHPL_ROWS_WALK 8
-#endif
-constexpr int ROWS_WALK = SHPL_ROWS_WALK;
+constexpr int ROWS_WALK = 8;
 #ifndef SHPL_RPROBE
-// timing probes of the row walk: 1 every gather from the first 64 rows, 2 no stores (wrong results); 3 each
-// k_rows2 wave's start / end s_memrealtime stamps into g_probe (read by shpl_probe_stamps)
+// the one timing probe left (scripts/stamps_rows2.py): 3 each k_rows2 wave's start / end s_memrealtime stamps
+// into g_probe (read by shpl_probe_stamps). 1 and 2 sat inside the row walk; their results: docs/HISTORY.md
 #define SHPL_RPROBE 0
 #endif
 #if SHPL_RPROBE == 3
@@ -743,7 +691,7 @@ __device__ __forceinline__ void row_walk(const Feat &f, const Ents &e, int64_t r
                 for (int u = 0; u < ROWS_WALK; ++u) {
                     const int32_t sr = __shfl(my_src, gbase + ((u0 + u) & (G - 1)), 64);
                     if (mine && j0 + u0 + u < len && u0 + u < G)
-                        raw[u] = C::load(src + ((int64_t)(SHPL_RPROBE == 1 ? (sr & 63) : sr) * f.src_stride + (int64_t)pc * VEC));
+                        raw[u] = C::load(src + ((int64_t)sr * f.src_stride + (int64_t)pc * VEC));
                 }
 #pragma unroll
                 for (int u = 0; u < ROWS_WALK; ++u) {
@@ -783,10 +731,6 @@ __device__ __forceinline__ void row_walk(const Feat &f, const Ents &e, int64_t r
             for (int j = 0; j < VEC; ++j) acc[j] = __fadd_rn(a[j], acc[j]);
         } else if (len == 0) {
             C::store_nt(out + (row * f.out_stride + (int64_t)(oc0 + pc) * VEC), C::zero());
-            continue;
-        }
-        if (SHPL_RPROBE == 2) {  // timing probe: no pooled stores (wrong results)
-            if (acc[0] == 1234.5f) C::store_nt(out, C::from_f32(acc));
             continue;
         }
         C::store_nt(out + (row * f.out_stride + (int64_t)(oc0 + pc) * VEC), C::from_f32(acc));
@@ -841,15 +785,8 @@ struct RowsSide {
 // The pixel-keyed pull's blocks come first: its longer runs (6.7 entries on average at config 3, up to 54 at
 // the horizon) then start early instead of forming the launch's tail (k_rows2 31.1 -> 24.0 us per pair,
 // profiles/r03_pixel_first_ab.log; reversing the order inside either side measured within noise).
-#ifndef SHPL_ROWS2_WPE
-#define SHPL_ROWS2_WPE 0
-#endif
 template <typename T, int VEC, int G, bool GR1, int MODE>
-__global__ __launch_bounds__(SHPL_BLOCK)
-#if SHPL_ROWS2_WPE
-__attribute__((amdgpu_waves_per_eu(SHPL_ROWS2_WPE, SHPL_ROWS2_WPE)))
-#endif
-void k_rows2(const RowsSide s0, const RowsSide s1) {
+__global__ __launch_bounds__(SHPL_BLOCK) void k_rows2(const RowsSide s0, const RowsSide s1) {
 #if SHPL_RPROBE == 3
     uint64_t t0;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
@@ -869,7 +806,12 @@ void k_rows2(const RowsSide s0, const RowsSide s1) {
 #endif
 }
 
-bool aligned(const void *ptr, int64_t a) { return ((uintptr_t)ptr) % (uintptr_t)a == 0; }
+// log2(c) when c is a power of two, else -1: the kernels then shift instead of dividing
+int pow2_shift(uint32_t c) {
+    for (int k = 0; k < 31; ++k)
+        if (c == (1u << k)) return k;
+    return -1;
+}
 
 struct Plan {
     Feat f = {};
@@ -904,10 +846,10 @@ int plan(int direction, int dtype, const shpl_csr *csr, const void *d_src, int64
     const int64_t esz = dtype == SHPL_F32 ? 4 : 2;
     const int64_t vec = 16 / esz;
     // 16-byte chunks need every row start and every channel split on a 16-byte boundary
-    bool v16 = c_pool % vec == 0 && out_stride % vec == 0 && aligned(d_out, 16);
-    if (c_pool > 0) v16 = v16 && src_stride % vec == 0 && src_off % vec == 0 && aligned(d_src, 16);
+    bool v16 = c_pool % vec == 0 && out_stride % vec == 0 && aligned16(d_out);
+    if (c_pool > 0) v16 = v16 && src_stride % vec == 0 && src_off % vec == 0 && aligned16(d_src);
     if (mode != SHPL_OUT_POOL)
-        v16 = v16 && c_pass % vec == 0 && pass_stride % vec == 0 && pass_off % vec == 0 && aligned(d_pass, 16);
+        v16 = v16 && c_pass % vec == 0 && pass_stride % vec == 0 && pass_off % vec == 0 && aligned16(d_pass);
     const int64_t v = v16 ? vec : 1;
     Feat &f = pl->f;
     f.src = d_src;
@@ -922,122 +864,93 @@ int plan(int direction, int dtype, const shpl_csr *csr, const void *d_src, int64
     f.cpr = (uint32_t)(width / v);
     f.cpass = mode == SHPL_OUT_CONCAT ? (uint32_t)(c_pass / v) : 0u;
     f.cpool = (uint32_t)(c_pool / v);
-    f.cpr_shift = -1;
-    for (int k = 0; k < 31; ++k)
-        if (f.cpr == (1u << k)) f.cpr_shift = k;
+    f.cpr_shift = pow2_shift(f.cpr);
     pl->n_dst = n_dst;
     pl->v16 = v16;
     pl->dtype = dtype;
     return SHPL_OK;
 }
 
-template <typename T, int VEC>
-int dense_t(const Plan &pl, hipStream_t s) {
-    if (pl.f.cpr == 0) return SHPL_OK;
+// Run-time values to template arguments: each dispatcher calls a generic lambda with a tag that carries the
+// compile-time form (shpl_batch_norm's style, shpl_bn.hip).
+template <typename T_, int VEC_>
+struct Elems {  // the element type and the elements per chunk
+    typedef T_ T;
+    static constexpr int VEC = VEC_;
+};
+
+template <typename F>
+auto by_elems(int dtype, bool v16, F &&fn) {
+    if (dtype == SHPL_F32) return v16 ? fn(Elems<float, 4>()) : fn(Elems<float, 1>());
+    return v16 ? fn(Elems<uint16_t, 8>()) : fn(Elems<uint16_t, 1>());
+}
+
+// fn(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...) for run-time switches b0, b1, ...
+template <bool... Bs, typename F>
+auto by_bools(F &&fn) {
+    return fn(std::bool_constant<Bs>{}...);
+}
+template <bool... Bs, typename F, typename... R>
+auto by_bools(F &&fn, bool b, R... rest) {
+    return b ? by_bools<Bs..., true>(fn, rest...) : by_bools<Bs..., false>(fn, rest...);
+}
+
+// fn(std::integral_constant<int, V>{}) for the listed V that v equals, the last one when none does
+template <int V, int... Rest, typename F>
+auto by_int(int v, F &&fn) {
+    if constexpr (sizeof...(Rest) == 0)
+        return fn(std::integral_constant<int, V>{});
+    else
+        return v == V ? fn(std::integral_constant<int, V>{}) : by_int<Rest...>(v, fn);
+}
+
+// Lanes per row of the row-keyed kernels: the pooled chunks of a row, at least 8 (index words come G at a
+// time), at most a wave.
+int lanes_per_row(uint32_t cpool) {
+    int G = 8;
+    while (G < 64 && (uint32_t)G < cpool) G <<= 1;
+    return G;
+}
+template <typename F>
+auto by_lanes(int G, F &&fn) {
+    return by_int<8, 16, 32, 64>(G, fn);
+}
+
+// The CSR's sorted entries as the kernels take them; live: with its frame layout; heads: with its run heads.
+Ents ents_of(const shpl_csr *csr, bool live, bool heads) {
+    Ents e{csr->nnz_cap, csr->ent_dst, csr->ent_src, csr->ent_col, csr->ent_val};
+    if (live) {
+        e.frame_off = csr->frame_off;
+        e.frame_nnz = csr->frame_nnz;
+        e.n_frames = (int)csr->n_frames;
+    }
+    if (heads) {
+        e.heads = (const int2 *)csr->heads;
+        e.head_k = (int)csr->head_k;
+    }
+    return e;
+}
+
+int dense(const Plan &pl, hipStream_t s) {
+    if (pl.n_dst == 0 || pl.f.cpr == 0) return SHPL_OK;
     // u32 chunk index per launch: at most 2^31 chunks each
     const int64_t rows_per_launch = ((int64_t)1 << 31) / (int64_t)pl.f.cpr;
     for (int64_t r0 = 0; r0 < pl.n_dst; r0 += rows_per_launch) {
         const int64_t nr = (pl.n_dst - r0) < rows_per_launch ? (pl.n_dst - r0) : rows_per_launch;
         const int64_t blocks = (nr * pl.f.cpr + SHPL_BLOCK - 1) / SHPL_BLOCK;
-        if (pl.f.cpr_shift >= 0)
-            hipLaunchKernelGGL((k_dense<T, VEC, true>), dim3((unsigned)blocks), dim3(SHPL_BLOCK), 0, s, pl.f,
-                               (uint32_t)r0, (uint32_t)nr);
-        else
-            hipLaunchKernelGGL((k_dense<T, VEC, false>), dim3((unsigned)blocks), dim3(SHPL_BLOCK), 0, s, pl.f,
-                               (uint32_t)r0, (uint32_t)nr);
+        by_elems(pl.dtype, pl.v16, [&](auto el) {
+            typedef decltype(el) E;
+            by_bools([&](auto POW2) {
+                hipLaunchKernelGGL((k_dense<typename E::T, E::VEC, POW2.value>), dim3((unsigned)blocks),
+                                   dim3(SHPL_BLOCK), 0, s, pl.f, (uint32_t)r0, (uint32_t)nr);
+            }, pl.f.cpr_shift >= 0);
+        });
         SHPL_LAUNCH_CHECK();
     }
     return SHPL_OK;
 }
 
-int dense(const Plan &pl, hipStream_t s) {
-    if (pl.n_dst == 0) return SHPL_OK;
-    if (pl.dtype == SHPL_F32) return pl.v16 ? dense_t<float, 4>(pl, s) : dense_t<float, 1>(pl, s);
-    return pl.v16 ? dense_t<uint16_t, 8>(pl, s) : dense_t<uint16_t, 1>(pl, s);
-}
-
-#ifndef SHPL_LIVE_GRID
-#define SHPL_LIVE_GRID 4096  // workgroups of the live-entry k_sparse at most (a grid-stride loop)
-#endif
-
-template <typename T, int VEC, bool GROUP, bool LIVE>
-void sparse_launch(const Plan &pl, const Ents &e, int grid, int shift, bool split, hipStream_t s) {
-#define SHPL_SPARSE(SPLIT, POW2)                                                                                   \
-    hipLaunchKernelGGL((k_sparse<T, VEC, GROUP, SPLIT, POW2, LIVE>), dim3(grid), dim3(SHPL_BLOCK), 0, s, pl.f, e, \
-                       shift)
-    if (split) {
-        if (shift >= 0) SHPL_SPARSE(true, true); else SHPL_SPARSE(true, false);
-    } else {
-        if (shift >= 0) SHPL_SPARSE(false, true); else SHPL_SPARSE(false, false);
-    }
-#undef SHPL_SPARSE
-}
-
-template <typename T, int VEC, bool GROUP>
-int sparse_tg(const Plan &pl, const Ents &e, int64_t nnz_cap, hipStream_t s) {
-    // one thread per (entry, chunk) of the capacity (the live count is read on the device), or, with a
-    // frame layout, a bounded grid walking the live entries' (entry, chunk) pairs
-    const bool live = e.n_frames > 0;
-    int grid = grid_for(nnz_cap * (int64_t)pl.f.cpool, SHPL_BLOCK, 1 << 20);
-    if (live && grid > SHPL_LIVE_GRID) grid = SHPL_LIVE_GRID;
-    int shift = -1;
-    for (int k = 0; k < 31; ++k)
-        if (pl.f.cpool == (1u << k)) shift = k;
-    // without a run longer than LONG_RUN possible, k_sparse takes every run (the short part); so it does
-    // over live entries (raw scans: runs of at most a few voxel points per cell -- k_sparse_long would only
-    // scan the capacity)
-    const bool split = !live && nnz_cap > LONG_RUN;
-    if (live)
-        sparse_launch<T, VEC, GROUP, true>(pl, e, grid, shift, split, s);
-    else
-        sparse_launch<T, VEC, GROUP, false>(pl, e, grid, shift, split, s);
-    SHPL_LAUNCH_CHECK();
-    if (!split) return SHPL_OK;
-    // a bounded grid: each workgroup scans per_block slots, LONG_SLOTS at a time
-    int64_t lgrid = (nnz_cap + LONG_SLOTS - 1) / LONG_SLOTS;
-    if (lgrid > LONG_GRID) lgrid = LONG_GRID;
-    const int64_t per_block = (nnz_cap + lgrid - 1) / lgrid;
-    hipLaunchKernelGGL((k_sparse_long<T, VEC, GROUP>), dim3((unsigned)lgrid), dim3(SHPL_BLOCK), 0, s, pl.f, e,
-                       per_block);
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
-}
-
-template <typename T, int VEC, bool GROUP>
-int once_tg(const Plan &pl, const shpl_csr *csr, hipStream_t s) {
-    Ents e{csr->nnz_cap, csr->ent_dst, csr->ent_src, csr->ent_col, csr->ent_val};
-    // the run-walking blocks: a thread per (entry, chunk), or (cell-keyed) a wave per 64 entries
-    const int64_t swork = once_seg(GROUP, pl.f.cpool) ? csr->nnz_cap : csr->nnz_cap * (int64_t)pl.f.cpool;
-    int64_t sblocks = csr->nnz_cap > 0 ? grid_for(swork, SHPL_BLOCK, 1 << 20) : 0;
-    if (SHPL_ONCE_XCD) sblocks = (sblocks + 7) & ~(int64_t)7;  // k_once's XCD-contiguous block order
-    const int64_t zblocks = (pl.n_dst + ONCE_ROWS * (SHPL_BLOCK / SHPL_WAVE) - 1) / (ONCE_ROWS * (SHPL_BLOCK / SHPL_WAVE));
-    if (sblocks + zblocks > 0x7fffffffLL) return SHPL_ERR_BAD_SHAPE;
-    int shift = -1;
-    for (int k = 0; k < 31; ++k)
-        if (pl.f.cpool == (1u << k)) shift = k;
-    if (shift >= 0)
-        hipLaunchKernelGGL((k_once<T, VEC, GROUP, true>), dim3((unsigned)(sblocks + zblocks)), dim3(SHPL_BLOCK), 0, s,
-                           pl.f, e, shift, (const int32_t *)csr->key_range, pl.n_dst, sblocks);
-    else
-        hipLaunchKernelGGL((k_once<T, VEC, GROUP, false>), dim3((unsigned)(sblocks + zblocks)), dim3(SHPL_BLOCK), 0,
-                           s, pl.f, e, shift, (const int32_t *)csr->key_range, pl.n_dst, sblocks);
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
-}
-
-template <typename T, int VEC>
-int once_t(const Plan &pl, const shpl_csr *csr, bool group, hipStream_t s) {
-    return group ? once_tg<T, VEC, true>(pl, csr, s) : once_tg<T, VEC, false>(pl, csr, s);
-}
-
-template <typename T, int VEC>
-int sparse_t(const Plan &pl, const shpl_csr *csr, bool group, hipStream_t s) {
-    const bool live = csr->n_frames > 0 && csr->frame_off && csr->frame_nnz;
-    Ents e{csr->nnz_cap, csr->ent_dst, csr->ent_src, csr->ent_col, csr->ent_val,
-           live ? csr->frame_off : nullptr, live ? csr->frame_nnz : nullptr, live ? (int)csr->n_frames : 0};
-    return group ? sparse_tg<T, VEC, true>(pl, e, csr->nnz_cap, s)
-                 : sparse_tg<T, VEC, false>(pl, e, csr->nnz_cap, s);
-}
+constexpr int LIVE_GRID = 4096;  // workgroups of the live-entry k_sparse at most (a grid-stride loop)
 
 // Per-column partials (TF's Q[k]) only where columns can repeat: a pixel-keyed CSR without ent_col has every
 // entry in a column of its own (the index builder's maps), where Q[k] is one product and the plain sum is
@@ -1046,50 +959,108 @@ int sparse_t(const Plan &pl, const shpl_csr *csr, bool group, hipStream_t s) {
 bool grouped(const shpl_csr *csr, int direction) { return direction == SHPL_BY_PIXEL && csr->ent_col != nullptr; }
 
 int sparse(const Plan &pl, const shpl_csr *csr, int direction, hipStream_t s) {
-    if (pl.n_dst == 0 || pl.f.cpool == 0 || csr->nnz_cap == 0) return SHPL_OK;
+    const int64_t nnz_cap = csr->nnz_cap;
+    if (pl.n_dst == 0 || pl.f.cpool == 0 || nnz_cap == 0) return SHPL_OK;
     if (csr->n_frames < 0 || csr->n_frames > LIVE_MAX_FRAMES) return SHPL_ERR_ARG;
-    const bool group = grouped(csr, direction);
-    if (pl.dtype == SHPL_F32)
-        return pl.v16 ? sparse_t<float, 4>(pl, csr, group, s) : sparse_t<float, 1>(pl, csr, group, s);
-    return pl.v16 ? sparse_t<uint16_t, 8>(pl, csr, group, s) : sparse_t<uint16_t, 1>(pl, csr, group, s);
-}
-
-template <typename T, int VEC, bool GROUP>
-int rows_t(const Plan &pl, const shpl_csr *csr, hipStream_t s) {
-    Ents e{csr->nnz_cap, csr->ent_dst, csr->ent_src, csr->ent_col, csr->ent_val};
-    e.heads = (const int2 *)csr->heads;
-    e.head_k = (int)csr->head_k;
-    // lanes per row: the pooled chunks of a row, at least 8 (index words come G at a time), at most a wave
-    int G = 8;
-    while (G < 64 && (uint32_t)G < pl.f.cpool) G <<= 1;
-    const int64_t rows_per_block = (int64_t)(SHPL_BLOCK / G);
-    const int64_t blocks = (pl.n_dst + rows_per_block - 1) / rows_per_block;
-    if (blocks > 0x7fffffffLL) return SHPL_ERR_BAD_SHAPE;
-#define SHPL_ROWS(GG) \
-    hipLaunchKernelGGL((k_rows<T, VEC, GROUP, GG>), dim3((unsigned)blocks), dim3(SHPL_BLOCK), 0, s, pl.f, e, \
-                       (const int32_t *)csr->key_range, pl.n_dst)
-    switch (G) {
-        case 8: SHPL_ROWS(8); break;
-        case 16: SHPL_ROWS(16); break;
-        case 32: SHPL_ROWS(32); break;
-        default: SHPL_ROWS(64); break;
-    }
-#undef SHPL_ROWS
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
-}
-
-template <typename T, int VEC>
-int rows_tv(const Plan &pl, const shpl_csr *csr, bool group, hipStream_t s) {
-    return group ? rows_t<T, VEC, true>(pl, csr, s) : rows_t<T, VEC, false>(pl, csr, s);
+    // one thread per (entry, chunk) of the capacity (the live count is read on the device), or, with a
+    // frame layout, a bounded grid walking the live entries' (entry, chunk) pairs
+    const bool live = csr->n_frames > 0 && csr->frame_off && csr->frame_nnz;
+    const Ents e = ents_of(csr, live, false);
+    int grid = grid_for(nnz_cap * (int64_t)pl.f.cpool, SHPL_BLOCK, 1 << 20);
+    if (live && grid > LIVE_GRID) grid = LIVE_GRID;
+    const int shift = pow2_shift(pl.f.cpool);
+    // without a run longer than LONG_RUN possible, k_sparse takes every run (the short part); so it does
+    // over live entries (raw scans: runs of at most a few voxel points per cell -- k_sparse_long would only
+    // scan the capacity). So SPLIT with LIVE is instantiated and never launched.
+    const bool split = !live && nnz_cap > LONG_RUN;
+    // k_sparse_long's bounded grid: each workgroup scans per_block slots, LONG_SLOTS at a time
+    int64_t lgrid = (nnz_cap + LONG_SLOTS - 1) / LONG_SLOTS;
+    if (lgrid > LONG_GRID) lgrid = LONG_GRID;
+    const int64_t per_block = (nnz_cap + lgrid - 1) / lgrid;
+    return by_elems(pl.dtype, pl.v16, [&](auto el) {
+        typedef decltype(el) E;
+        return by_bools([&](auto GROUP, auto SPLIT, auto POW2, auto LIVE) {
+            hipLaunchKernelGGL((k_sparse<typename E::T, E::VEC, GROUP.value, SPLIT.value, POW2.value, LIVE.value>),
+                               dim3(grid), dim3(SHPL_BLOCK), 0, s, pl.f, e, shift);
+            SHPL_LAUNCH_CHECK();
+            if (!SPLIT.value) return SHPL_OK;
+            hipLaunchKernelGGL((k_sparse_long<typename E::T, E::VEC, GROUP.value>), dim3((unsigned)lgrid),
+                               dim3(SHPL_BLOCK), 0, s, pl.f, e, per_block);
+            SHPL_LAUNCH_CHECK();
+            return SHPL_OK;
+        }, grouped(csr, direction), split, shift >= 0, live);
+    });
 }
 
 int rows(const Plan &pl, const shpl_csr *csr, int direction, hipStream_t s) {
     if (pl.n_dst == 0) return SHPL_OK;
+    const Ents e = ents_of(csr, false, true);
+    const int G = lanes_per_row(pl.f.cpool);
+    const int64_t rows_per_block = (int64_t)(SHPL_BLOCK / G);
+    const int64_t blocks = (pl.n_dst + rows_per_block - 1) / rows_per_block;
+    if (blocks > 0x7fffffffLL) return SHPL_ERR_BAD_SHAPE;
+    by_elems(pl.dtype, pl.v16, [&](auto el) {
+        typedef decltype(el) E;
+        by_bools([&](auto GROUP) {
+            by_lanes(G, [&](auto GG) {
+                hipLaunchKernelGGL((k_rows<typename E::T, E::VEC, GROUP.value, GG.value>), dim3((unsigned)blocks),
+                                   dim3(SHPL_BLOCK), 0, s, pl.f, e, (const int32_t *)csr->key_range, pl.n_dst);
+            });
+        }, grouped(csr, direction));
+    });
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
+
+int once(const Plan &pl, const shpl_csr *csr, int direction, hipStream_t s) {
     const bool group = grouped(csr, direction);
-    if (pl.dtype == SHPL_F32)
-        return pl.v16 ? rows_tv<float, 4>(pl, csr, group, s) : rows_tv<float, 1>(pl, csr, group, s);
-    return pl.v16 ? rows_tv<uint16_t, 8>(pl, csr, group, s) : rows_tv<uint16_t, 1>(pl, csr, group, s);
+    const Ents e = ents_of(csr, false, false);
+    // the run-walking blocks: a thread per (entry, chunk), or (cell-keyed) a wave per 64 entries
+    const int64_t swork = once_seg(group, pl.f.cpool) ? csr->nnz_cap : csr->nnz_cap * (int64_t)pl.f.cpool;
+    int64_t sblocks = csr->nnz_cap > 0 ? grid_for(swork, SHPL_BLOCK, 1 << 20) : 0;
+    sblocks = (sblocks + 7) & ~(int64_t)7;  // k_once's XCD-contiguous block order
+    const int64_t zblocks = (pl.n_dst + ONCE_ROWS * (SHPL_BLOCK / SHPL_WAVE) - 1) / (ONCE_ROWS * (SHPL_BLOCK / SHPL_WAVE));
+    if (sblocks + zblocks > 0x7fffffffLL) return SHPL_ERR_BAD_SHAPE;
+    const int shift = pow2_shift(pl.f.cpool);
+    by_elems(pl.dtype, pl.v16, [&](auto el) {
+        typedef decltype(el) E;
+        by_bools([&](auto GROUP, auto POW2) {
+            hipLaunchKernelGGL((k_once<typename E::T, E::VEC, GROUP.value, POW2.value>),
+                               dim3((unsigned)(sblocks + zblocks)), dim3(SHPL_BLOCK), 0, s, pl.f, e, shift,
+                               (const int32_t *)csr->key_range, pl.n_dst, sblocks);
+        }, group, shift >= 0);
+    });
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
+
+// The two sides of shpl_pull_pair in one k_rows2 launch, G lanes per row.
+int pair(RowsSide s[2], int dtype, bool v16, int G, hipStream_t st) {
+    const int rpb = SHPL_BLOCK / G;
+    for (int k = 0; k < 2; ++k)
+        if (s[k].n_rows > 0) s[k].blocks = (s[k].n_rows + rpb - 1) / rpb;
+    const int64_t blocks = s[0].blocks + s[1].blocks;
+    if (blocks == 0) return SHPL_OK;
+    if (blocks > 0x7fffffffLL) return SHPL_ERR_BAD_SHAPE;
+    const bool gr1 = s[1].e.col != nullptr;  // the pixel-keyed side's per-column partials (grouped())
+    // the output mode at compile time when both pulls share it (the forward pair's pooled halves, the gradient
+    // pair's add): the other modes' preloaded operands leave the registers (config 3: 78 -> VGPRs below)
+    int mode = -1;
+    if (s[0].n_rows == 0 || s[1].n_rows == 0 || s[0].f.mode == s[1].f.mode)
+        mode = s[0].n_rows ? s[0].f.mode : s[1].f.mode;
+    by_elems(dtype, v16, [&](auto el) {
+        typedef decltype(el) E;
+        by_lanes(G, [&](auto GG) {
+            by_bools([&](auto GR1) {
+                by_int<SHPL_OUT_POOL, SHPL_OUT_ADD, SHPL_OUT_CONCAT, -1>(mode, [&](auto MODE) {
+                    hipLaunchKernelGGL((k_rows2<typename E::T, E::VEC, GG.value, GR1.value, MODE.value>),
+                                       dim3((unsigned)blocks), dim3(SHPL_BLOCK), 0, st, s[0], s[1]);
+                });
+            }, gr1);
+        });
+    });
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
 }
 
 }  // namespace
@@ -1131,59 +1102,8 @@ extern "C" int shpl_pull_once(SHPL_PULL_ARGS) {
     SHPL_PLAN();
     if (mode != SHPL_OUT_POOL || !csr->key_range) return SHPL_ERR_ARG;
     if (pl.n_dst == 0 || pl.f.cpool == 0) return SHPL_OK;
-    const bool group = grouped(csr, direction);
-    hipStream_t s = (hipStream_t)stream;
-    if (pl.dtype == SHPL_F32)
-        return pl.v16 ? once_t<float, 4>(pl, csr, group, s) : once_t<float, 1>(pl, csr, group, s);
-    return pl.v16 ? once_t<uint16_t, 8>(pl, csr, group, s) : once_t<uint16_t, 1>(pl, csr, group, s);
+    return once(pl, csr, direction, (hipStream_t)stream);
 }
-
-// ---------------------------------------------------------------- paired pulls
-namespace shpl {
-namespace {
-
-template <typename T, int VEC>
-int pair_t(RowsSide s[2], int G, hipStream_t st) {
-    const int rpb = SHPL_BLOCK / G;
-    for (int k = 0; k < 2; ++k)
-        if (s[k].n_rows > 0) s[k].blocks = (s[k].n_rows + rpb - 1) / rpb;
-    const int64_t blocks = s[0].blocks + s[1].blocks;
-    if (blocks == 0) return SHPL_OK;
-    if (blocks > 0x7fffffffLL) return SHPL_ERR_BAD_SHAPE;
-    const bool gr1 = s[1].e.col != nullptr;  // the pixel-keyed side's per-column partials (grouped())
-    // the output mode at compile time when both pulls share it (the forward pair's pooled halves, the gradient
-    // pair's add): the other modes' preloaded operands leave the registers (config 3: 78 -> VGPRs below)
-    int mode = -1;
-    if (s[0].n_rows == 0 || s[1].n_rows == 0 || s[0].f.mode == s[1].f.mode)
-        mode = s[0].n_rows ? s[0].f.mode : s[1].f.mode;
-#define SHPL_ROWS2_M(GG, GR, M) \
-    hipLaunchKernelGGL((k_rows2<T, VEC, GG, GR, M>), dim3((unsigned)blocks), dim3(SHPL_BLOCK), 0, st, s[0], s[1])
-#define SHPL_ROWS2_G(GG, GR)                                                  \
-    if (mode == SHPL_OUT_POOL) SHPL_ROWS2_M(GG, GR, SHPL_OUT_POOL);          \
-    else if (mode == SHPL_OUT_ADD) SHPL_ROWS2_M(GG, GR, SHPL_OUT_ADD);       \
-    else if (mode == SHPL_OUT_CONCAT) SHPL_ROWS2_M(GG, GR, SHPL_OUT_CONCAT); \
-    else SHPL_ROWS2_M(GG, GR, -1);
-#define SHPL_ROWS2(GG)              \
-    if (gr1) {                      \
-        SHPL_ROWS2_G(GG, true)      \
-    } else {                        \
-        SHPL_ROWS2_G(GG, false)     \
-    }
-    switch (G) {
-        case 8: SHPL_ROWS2(8); break;
-        case 16: SHPL_ROWS2(16); break;
-        case 32: SHPL_ROWS2(32); break;
-        default: SHPL_ROWS2(64); break;
-    }
-#undef SHPL_ROWS2
-#undef SHPL_ROWS2_G
-#undef SHPL_ROWS2_M
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
-}
-
-}  // namespace
-}  // namespace shpl
 
 extern "C" int shpl_pull_pair(const shpl_csr *by_cell, const shpl_pull_desc *d_cell, const shpl_csr *by_pixel,
                               const shpl_pull_desc *d_pixel, void *stream) {
@@ -1218,21 +1138,17 @@ extern "C" int shpl_pull_pair(const shpl_csr *by_cell, const shpl_pull_desc *d_c
         return SHPL_OK;
     }
     RowsSide s[2] = {};
-    int dtype = -1, v16 = 0, G = 8;
+    int dtype = -1, G = 8;
+    bool v16 = false;
     for (int k = 0; k < 2; ++k) {
         if (!on[k]) continue;
-        const shpl_csr *c = cs[k];
         dtype = pl[k].dtype;
         v16 = pl[k].v16;
-        while (G < 64 && (uint32_t)G < pl[k].f.cpool) G <<= 1;  // lanes per row: the widest pooled row
-        s[k] = RowsSide{pl[k].f, Ents{c->nnz_cap, c->ent_dst, c->ent_src, c->ent_col, c->ent_val}, c->key_range,
-                        pl[k].n_dst, 0};
-        s[k].e.heads = (const int2 *)c->heads;
-        s[k].e.head_k = (int)c->head_k;
+        G = std::max(G, lanes_per_row(pl[k].f.cpool));  // the widest pooled row's
+        s[k] = RowsSide{pl[k].f, ents_of(cs[k], false, true), cs[k]->key_range, pl[k].n_dst, 0};
     }
     if (dtype < 0) return SHPL_OK;
-    if (dtype == SHPL_F32) return v16 ? pair_t<float, 4>(s, G, st) : pair_t<float, 1>(s, G, st);
-    return v16 ? pair_t<uint16_t, 8>(s, G, st) : pair_t<uint16_t, 1>(s, G, st);
+    return pair(s, dtype, v16, G, st);
 }
 
 #if SHPL_RPROBE == 3

@@ -41,7 +41,7 @@ Dispatch table: template instance -> the tests that launch it (T = float / uint1
                                    test_chunk_counts[*-flat-k1/k8-*]); scalar: test_chunk_counts[*-flat-c3/c12-*]
       !SPLIT, LIVE                 test_entry_points[*-live-*]
       !SPLIT, !LIVE                test_tiny_capacity (nnz_cap <= LONG_RUN)
-      SPLIT, LIVE                  unreachable: sparse_tg() sets split = !live
+      SPLIT, LIVE                  unreachable: sparse() sets split = !live
   k_sparse_long<T, VEC, GROUP>     every flat / split case (runs of 9 .. 600); its second round per workgroup:
                                    test_capacity_second_round
   k_once<T, VEC, GROUP, POW2>      test_entry_points[*-once-*], test_chunk_counts[*-once-*] (POW2: k1, k8;
