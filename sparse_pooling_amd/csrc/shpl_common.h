@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/shpl.h"
 
 #define SHPL_WAVE 64
@@ -36,6 +38,33 @@ __device__ __forceinline__ int32_t wave_incl_scan(int32_t v) { return __ockl_wfs
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The calling lanes (ok) of this wave that name the same LDS word, as a lane mask, this lane included: each ORs
+// its bit into the word (zero between uses), reads the word back, and zeroes it again. One wave's LDS
+// operations run in order, so the reads follow every OR of the wave and the zeroing every read; lane_rank of
+// the mask is the lane's rank among its peers. Every lane of the wave calls; !ok lanes get 0. (Measured in the
+// index build at config 3: a multisplit of ballots over the word's index bits spent ~2.4 us of VALU.)
+__device__ __forceinline__ uint64_t wave_peers(uint64_t *word, bool ok) {
+    uint64_t peers = 0;
+    if (ok) atomicOr(reinterpret_cast<unsigned long long *>(word), 1ull << (threadIdx.x & 63));
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (ok) peers = *word;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (ok) *word = 0;
+    return peers;
+}
+
+// Exclusive prefix of v over the block's threads, any block of whole waves: wsum needs one int per wave and
+// keeps the waves' sums (their total is the block's); one block barrier inside, none after.
+__device__ __forceinline__ int32_t block_excl_scan(int32_t v, int32_t *wsum) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int32_t x = wave_incl_scan(v);
+    if (lane == 63) wsum[wid] = x;
+    __syncthreads();
+    int32_t run = x - v;
+    for (int w = 0; w < wid; ++w) run += wsum[w];
+    return run;
 }
 
 // Exclusive scan of one int per thread across a 256-thread block.
@@ -195,6 +224,12 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 constexpr int BK_KEYS = 128;        // destinations per range
 constexpr int BK_MAX_RANGES = 512;  // ranges per frame (65536 destinations)
 constexpr int BK_RBITS = 9;         // range bits matched by the placement's multisplit
+constexpr int IDX_CHUNK = 1024;     // points per index chunk: hist's n_chunks (shpl_compact.h, one workgroup each)
+
+inline int n_chunks_for(int64_t max_points) {
+    const int64_t c = (max_points + IDX_CHUNK - 1) / IDX_CHUNK;
+    return (int)(c < 1 ? 1 : c);
+}
 
 struct BkLayout {
     int n_frames, n_chunks, nr[2], nrmax;
@@ -232,6 +267,38 @@ inline int grid_for(int64_t work, int64_t per_block, int cap) {
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     return (int)g;
+}
+
+// Run-time values to template arguments: each dispatcher calls a generic lambda with a tag that carries the
+// compile-time form (shpl_batch_norm's style, shpl_bn.hip).
+// fn(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...) for run-time switches b0, b1, ...
+template <bool... Bs, typename F>
+auto by_bools(F &&fn) {
+    return fn(std::bool_constant<Bs>{}...);
+}
+template <bool... Bs, typename F, typename... R>
+auto by_bools(F &&fn, bool b, R... rest) {
+    return b ? by_bools<Bs..., true>(fn, rest...) : by_bools<Bs..., false>(fn, rest...);
+}
+
+template <typename T_>
+struct TypeOf {  // a type as a value
+    typedef T_ T;
+};
+
+// fn(TypeOf<int64_t / int32_t>) for an index type code (SHPL_I64 / SHPL_I32), fn(point type, index type) for a
+// point dtype (SHPL_F64 / SHPL_F32) with one: fn's status, SHPL_ERR_ARG for any other code.
+template <typename F>
+int by_itype(int itype, F &&fn) {
+    if (itype == SHPL_I64) return fn(TypeOf<int64_t>());
+    if (itype == SHPL_I32) return fn(TypeOf<int32_t>());
+    return SHPL_ERR_ARG;
+}
+template <typename F>
+int by_point_types(int dtype, int itype, F &&fn) {
+    if (dtype == SHPL_F64) return by_itype(itype, [&](auto vt) { return fn(TypeOf<double>(), vt); });
+    if (dtype == SHPL_F32) return by_itype(itype, [&](auto vt) { return fn(TypeOf<float>(), vt); });
+    return SHPL_ERR_ARG;
 }
 
 namespace {

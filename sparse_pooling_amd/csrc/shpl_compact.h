@@ -1,6 +1,6 @@
 // shpl_compact.h -- batched, stable per-frame compaction used by the point
 // stages (index builder, KITTI velodyne loader): every frame's points are cut
-// into chunks of IDX_CHUNK points, one 1024-thread workgroup per chunk.
+// into chunks of IDX_CHUNK points, one workgroup per chunk and one point per thread.
 //   k_count   -- kept points per chunk (Stage::load + Stage::eval)
 //   k_compact -- the chunk's kept points land after those of the frame's
 //                earlier chunks, in point order; each chunk also writes the
@@ -28,12 +28,7 @@
 namespace shpl {
 namespace {
 
-constexpr int IDX_BLOCK = 1024;
-#ifndef SHPL_IDX_BATCH
-#define SHPL_IDX_BATCH 1
-#endif
-constexpr int IDX_BATCH = SHPL_IDX_BATCH;         // point rows per thread whose loads are in flight together
-constexpr int IDX_CHUNK = IDX_BLOCK * IDX_BATCH;  // points per workgroup: one round
+constexpr int IDX_BLOCK = IDX_CHUNK;  // threads per workgroup: one per point of its chunk (shpl_common.h)
 
 constexpr uint32_t KEEP_MULTI = 1u, KEEP_ONE = 2u, AUX = 4u;
 
@@ -77,16 +72,12 @@ struct Bkt {
     int32_t *hist;    // [2][F][n_chunks][nrmax]
     int32_t *ext;     // [2][F][nrmax][2]
     uint32_t *words;  // [2][nnz_cap]
-    PassCopy cp[2];
-    int cp_at[2];     // the launch each copy rides: 0 = k_count, 1 = k_compact
+    PassCopy cp[2];   // the riders: cp[0] (the cell copy) rides k_count, cp[1] (the pixel copy) k_compact
     int cp_blocks;    // rider workgroups per frame in each launch (0: none)
     int32_t *bar;     // [2][F] k_index1's frame barrier words (arrivals, departures): zero between calls
 };
 
-#ifndef SHPL_CP_BATCH
-#define SHPL_CP_BATCH 8
-#endif
-constexpr int CP_BATCH = SHPL_CP_BATCH;  // 16-byte pieces per thread in flight
+constexpr int CP_BATCH = 8;  // 16-byte pieces per thread in flight
 
 // 32-bit piece arithmetic (a frame's pieces < 2^31, checked on the host; a shift when a row holds a power of
 // two of pieces): the 64-bit divisions of an earlier form held the rider path at 111 / 122 VGPRs, and with it
@@ -187,11 +178,10 @@ __device__ __forceinline__ int32_t load_agent(const int32_t *p) {
 }
 
 // Pass 1 of chunk j of frame f: KEEP_MULTI / KEEP_ONE / AUX points, and (BKT) the chunk's histograms over
-// the destination ranges; leaves the chunk's points in `in`.
+// the destination ranges; leaves this thread's point in `in`, its flags in `m` and its payload in `pl`.
 template <typename Stage, bool BKT>
 __device__ __forceinline__ void count_phase(const Stage &st, const Frames &fr, const Bkt &bk, int f, int j,
-                                            typename Stage::In (&in)[IDX_BATCH], uint32_t (&m_out)[IDX_BATCH],
-                                            typename Stage::Payload (&pl_out)[IDX_BATCH]) {
+                                            typename Stage::In &in, uint32_t &m, typename Stage::Payload &pl) {
     __shared__ int32_t wsum[3][IDX_BLOCK / 64];
     __shared__ int32_t hist[BKT ? 2 * BK_MAX_RANGES : 1];
     if constexpr (BKT) {
@@ -203,33 +193,21 @@ __device__ __forceinline__ void count_phase(const Stage &st, const Frames &fr, c
     if (j == fr.n_chunks - 1 && p1 > base + IDX_CHUNK && threadIdx.x == 0 && fr.err)
         atomicOr(fr.err, SHPL_EBIT_CAPACITY);  // frame larger than max_points_per_frame
     const Ctx ctx{p1 - p0, -1};
-#pragma unroll
-    for (int u = 0; u < IDX_BATCH; ++u) {
-        const int64_t i = base + (int64_t)u * IDX_BLOCK + threadIdx.x;
-        if (i < p1) st.load(i, in[u]);
-    }
-    int32_t n[3] = {0, 0, 0};
+    const int64_t i = base + threadIdx.x;
+    if (i < p1) st.load(i, in);
     if constexpr (BKT) __syncthreads();  // hist cleared
-#pragma unroll
-    for (int u = 0; u < IDX_BATCH; ++u) {
-        const int64_t i = base + (int64_t)u * IDX_BLOCK + threadIdx.x;
-        typename Stage::Payload &pl = pl_out[u];
-        const uint32_t m = i < p1 ? st.eval(ctx, f, i, in[u], pl) : 0u;
-        m_out[u] = m;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) n[k] += (m >> k) & 1u;
-        if constexpr (BKT) {
-            int32_t kc, kp;
-            if ((m & KEEP_MULTI) && st.bucket_keys(pl, kc, kp)) {
-                atomicAdd(&hist[kc / BK_KEYS], 1);
-                atomicAdd(&hist[BK_MAX_RANGES + kp / BK_KEYS], 1);
-            }
+    m = i < p1 ? st.eval(ctx, f, i, in, pl) : 0u;
+    if constexpr (BKT) {
+        int32_t kc, kp;
+        if ((m & KEEP_MULTI) && st.bucket_keys(pl, kc, kp)) {
+            atomicAdd(&hist[kc / BK_KEYS], 1);
+            atomicAdd(&hist[BK_MAX_RANGES + kp / BK_KEYS], 1);
         }
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        n[k] = wave_sum(n[k]);
-        if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = n[k];
+        const int32_t n = wave_sum((m >> k) & 1u);
+        if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = n;
     }
     __syncthreads();
     // the chunk's counts and histograms: write-through stores (sc1), which k_index1's frame barrier hands to
@@ -255,15 +233,13 @@ __global__ __launch_bounds__(IDX_BLOCK) void k_count(Stage st, Frames fr, Bkt bk
     const int f = blockIdx.y, j = (int)blockIdx.x;
     if constexpr (BKT) {
         if (j >= fr.n_chunks) {  // a rider workgroup (uniform)
-            const int rj = j - fr.n_chunks;
-            for (int c = 0; c < 2; ++c)
-                if (bk.cp_at[c] == 0) pass_copy(bk.cp[c], f, rj, bk.cp_blocks);
+            pass_copy(bk.cp[0], f, j - fr.n_chunks, bk.cp_blocks);
             return;
         }
     }
-    typename Stage::In in[IDX_BATCH];
-    uint32_t m[IDX_BATCH];
-    typename Stage::Payload pl[IDX_BATCH];
+    typename Stage::In in;
+    uint32_t m;
+    typename Stage::Payload pl;
     count_phase<Stage, BKT>(st, fr, bk, f, j, in, m, pl);
 }
 
@@ -294,23 +270,15 @@ __device__ __forceinline__ void bucket_place(const Stage &st, const Frames &fr, 
             x2[1] = b_tot;
         }
     }
-    // 2. stable multisplit of the chunk's entries by range, per key: each lane ORs its bit into its wave's word
-    // of its range (s_peer, zero between uses), reads the word back -- the wave's lanes of the same range, its
-    // rank among them = the lanes below it -- and the lanes zero it again. One wave's LDS operations run in
-    // order, so the reads follow every OR of the wave and the zeroing every read. (Measured: a multisplit of
-    // ballots over the range bits spent ~2.4 us of VALU here at config 3.)
+    // 2. stable multisplit of the chunk's entries by range, per key: an entry's rank among its wave's entries
+    // of the same range (wave_peers on the wave's word of the range)
     int32_t kk[2] = {0, 0};
     const bool ok = total >= 2 && keep && pos >= 0 && st.bucket_keys(pl, kk[0], kk[1]);
     int32_t rank[2];
 #pragma unroll
     for (int K = 0; K < 2; ++K) {
         const int r = ok ? kk[K] / BK_KEYS : 0;
-        uint64_t peers = 0;
-        if (ok) atomicOr(reinterpret_cast<unsigned long long *>(&s_peer[wid][r]), 1ull << lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (ok) peers = s_peer[wid][r];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (ok) s_peer[wid][r] = 0;
+        const uint64_t peers = wave_peers(&s_peer[wid][r], ok);
         rank[K] = (int32_t)lane_rank(peers);
         if (ok && rank[K] == 0) s_w[K][wid][r] = (int16_t)__popcll(peers);
     }
@@ -346,16 +314,14 @@ __device__ __forceinline__ void bucket_place(const Stage &st, const Frames &fr, 
 // chunk are ranked in order by wave ballots + an LDS prefix. Each chunk also
 // writes the sentinels of the unused capacity that falls in its stretch of
 // slots, and the frame's last chunk the frame's entry count.
-// Pass 2 of chunk j of frame f (`loaded`: its points already in `in`, and pass 1's flags and payloads in
+// Pass 2 of chunk j of frame f (`loaded`: this thread's point already in `in`, and pass 1's flags and payload in
 // flags1 / pay1, from count_phase in the same launch: they are pass 2's own unless the frame has exactly one AUX point --
-// the stage's second product in the other order -- so only then is a point evaluated again).
+// the stage's second product in the other order -- so only then is the point evaluated again).
 template <typename Stage, bool BKT>
 __device__ __forceinline__ void compact_phase(const Stage &st, const Frames &fr, const Bkt &bk, int f, int j,
-                                              typename Stage::In (&in)[IDX_BATCH], bool loaded,
-                                              const uint32_t (&flags1)[IDX_BATCH],
-                                              const typename Stage::Payload (&pay1)[IDX_BATCH]) {
-    static_assert(!BKT || IDX_BATCH == 1, "bucket placement ranks one point per thread");
-    __shared__ int32_t wsum[IDX_BATCH][IDX_BLOCK / 64];
+                                              typename Stage::In &in, bool loaded, uint32_t flags1,
+                                              const typename Stage::Payload &pay1) {
+    __shared__ int32_t wsum[IDX_BLOCK / 64];
     __shared__ int32_t pre[2][IDX_BLOCK / 64], all[2][IDX_BLOCK / 64], naux[IDX_BLOCK / 64];
     __shared__ int32_t s_off[BKT ? 2 * BK_MAX_RANGES : 1], s_scan[IDX_BLOCK / 64];
     // per-wave range counts, then their prefixes over the waves (at most IDX_BLOCK: 16 bits). LDS of the
@@ -443,61 +409,42 @@ __device__ __forceinline__ void compact_phase(const Stage &st, const Frames &fr,
     const int variant = n_aux == 1 ? 1 : 0;
     const uint32_t keep_bit = variant ? KEEP_ONE : KEEP_MULTI;
     const int64_t base = p0 + (int64_t)j * IDX_CHUNK;
-    typename Stage::Payload pl[IDX_BATCH];
-    bool keep[IDX_BATCH];
-    if (!loaded) {
-#pragma unroll
-        for (int u = 0; u < IDX_BATCH; ++u) {
-            const int64_t i = base + (int64_t)u * IDX_BLOCK + threadIdx.x;
-            if (i < p1) st.load(i, in[u]);
+    const int64_t i = base + threadIdx.x;
+    typename Stage::Payload pl;
+    bool keep = false;
+    if (!loaded && i < p1) st.load(i, in);
+    if (i < p1) {
+        if (loaded && n_aux != 1) {
+            keep = (flags1 & keep_bit) != 0;
+            pl = pay1;
+        } else {
+            keep = (st.eval(ctx, f, i, in, pl) & keep_bit) != 0;
         }
+        st.touch(f, i, pl, keep);
     }
-    uint64_t m[IDX_BATCH];
-    int64_t b_pos = 0;  // BKT: this point's entry slot in the frame
-#pragma unroll
-    for (int u = 0; u < IDX_BATCH; ++u) {
-        const int64_t i = base + (int64_t)u * IDX_BLOCK + threadIdx.x;
-        keep[u] = false;
-        if (i < p1) {
-            if (loaded && n_aux != 1) {
-                keep[u] = (flags1[u] & keep_bit) != 0;
-                pl[u] = pay1[u];
-            } else {
-                keep[u] = (st.eval(ctx, f, i, in[u], pl[u]) & keep_bit) != 0;
-            }
-            st.touch(f, i, pl[u], keep[u]);
-        }
-        m[u] = __ballot(keep[u]);
-        if ((threadIdx.x & 63) == 0) wsum[u][wid] = (int32_t)__popcll(m[u]);
-    }
+    const uint64_t m = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) wsum[wid] = (int32_t)__popcll(m);
     lds_barrier();
-    int64_t kept = 0;
+    int64_t kept = 0;  // the frame's entries in earlier chunks
     for (int w = 0; w < IDX_BLOCK / 64; ++w) kept += pre[variant][w];
-#pragma unroll
-    for (int u = 0; u < IDX_BATCH; ++u) {
-        int32_t before = 0, tot = 0;
-        for (int w = 0; w < IDX_BLOCK / 64; ++w) {
-            const int32_t c = wsum[u][w];
-            before += w < wid ? c : 0;
-            tot += c;
-        }
-        const int64_t i = base + (int64_t)u * IDX_BLOCK + threadIdx.x;
-        const int64_t slot = kept + before + lane_rank(m[u]);  // (entries of the frame before this one)
-        // every write the frame's aggregates address stays inside the frame's capacity: aggregates a failed
-        // barrier left half-written (SHPL_EBIT_BARRIER is set then) can make a wrong map, never a stray write
-        const bool in_cap = slot >= 0 && slot < cap_end - p0;
-        if (keep[u] && !in_cap && fr.err) atomicOr(fr.err, SHPL_EBIT_BARRIER);
-        if (keep[u] && in_cap) st.emit(f, i, p0 + slot, p0, pl[u]);
-        if constexpr (BKT) b_pos = in_cap ? slot : -1;
-        kept += tot;
+    int32_t before = 0;  // the chunk's in earlier waves
+    for (int w = 0; w < IDX_BLOCK / 64; ++w) {
+        const int32_t c = wsum[w];
+        before += w < wid ? c : 0;
     }
+    const int64_t slot = kept + before + lane_rank(m);  // (entries of the frame before this one)
+    // every write the frame's aggregates address stays inside the frame's capacity: aggregates a failed
+    // barrier left half-written (SHPL_EBIT_BARRIER is set then) can make a wrong map, never a stray write
+    const bool in_cap = slot >= 0 && slot < cap_end - p0;
+    if (keep && !in_cap && fr.err) atomicOr(fr.err, SHPL_EBIT_BARRIER);
+    if (keep && in_cap) st.emit(f, i, p0 + slot, p0, pl);
     // sentinels of the unused capacity [p0 + total, cap_end), each chunk its own stretch
     int64_t total = 0;
     for (int w = 0; w < IDX_BLOCK / 64; ++w) total += all[variant][w];
     SHPL_IDX1_STAMP(4);
     if constexpr (BKT) {  // (s_tb written before k_compact's first barrier; entries past nr[K] never)
         const bool live = (int)(threadIdx.x % BK_MAX_RANGES) < bk.nr[threadIdx.x / BK_MAX_RANGES];
-        bucket_place(st, fr, bk, f, j, p0, cap_end - p0, total, keep[0], pl[0], b_pos,
+        bucket_place(st, fr, bk, f, j, p0, cap_end - p0, total, keep, pl, in_cap ? slot : -1,
                      live ? s_tb[threadIdx.x] : 0,
                      live ? s_tb[2 * BK_MAX_RANGES + threadIdx.x] : 0, s_off, s_scan, s_w, s_peer);
     }
@@ -520,16 +467,13 @@ __global__ __launch_bounds__(IDX_BLOCK) void k_compact(Stage st, Frames fr, Bkt 
     const int f = blockIdx.y, j = (int)blockIdx.x;
     if constexpr (BKT) {
         if (j >= fr.n_chunks) {  // a rider workgroup (uniform)
-            const int rj = j - fr.n_chunks;
-            for (int c = 0; c < 2; ++c)
-                if (bk.cp_at[c] == 1) pass_copy(bk.cp[c], f, rj, bk.cp_blocks);
+            pass_copy(bk.cp[1], f, j - fr.n_chunks, bk.cp_blocks);
             return;
         }
     }
-    typename Stage::In in[IDX_BATCH];
-    uint32_t m[IDX_BATCH] = {};
-    typename Stage::Payload pl[IDX_BATCH];
-    compact_phase<Stage, BKT>(st, fr, bk, f, j, in, false, m, pl);
+    typename Stage::In in;
+    typename Stage::Payload pl;
+    compact_phase<Stage, BKT>(st, fr, bk, f, j, in, false, 0u, pl);
 }
 
 // Both passes of the bucketed index in ONE launch (k_index1, small batches): a 1-D grid, every frame's chunk
@@ -552,6 +496,7 @@ __global__ __launch_bounds__(IDX_BLOCK) void k_compact(Stage st, Frames fr, Bkt 
 // a chunk of the launch is undispatched at most (chunks - 1) slots are held by waiting chunks and one is free
 // for it. (A GPU shared with other processes can still starve a frame: then the give-up below.)
 constexpr int IDX1_MAX_CHUNKS = 32;
+constexpr int IDX1_RIDERS = 240;  // rider workgroups per copy over the batch
 constexpr uint64_t IDX1_SPIN_TICKS = 2000000;  // 20 ms of s_memrealtime (100 MHz): the barrier's give-up
 #ifndef SHPL_IDX1_FAULT
 #define SHPL_IDX1_FAULT 0  // test builds only (libshpl_fault.so): chunk 0 of frame 0 never arrives -> the give-up
@@ -577,15 +522,8 @@ __device__ __forceinline__ void frame_barrier(const Frames &fr, const Bkt &bk, i
     __syncthreads();  // (every later load of the frame's aggregates is an sc1 load: no acquire fence)
 }
 
-#ifndef SHPL_IDX1_WPE
-#define SHPL_IDX1_WPE 0  // waves per SIMD asked of the register allocator (8: two workgroups per CU); 0 = its own
-#endif
 template <typename Stage>
-__global__ __launch_bounds__(IDX_BLOCK)
-#if SHPL_IDX1_WPE
-__attribute__((amdgpu_waves_per_eu(SHPL_IDX1_WPE, SHPL_IDX1_WPE)))
-#endif
-void k_index1(Stage st, Frames fr, Bkt bk) {
+__global__ __launch_bounds__(IDX_BLOCK) void k_index1(Stage st, Frames fr, Bkt bk) {
     const int64_t b = blockIdx.x, n_ch = (int64_t)fr.n_frames * fr.n_chunks;
     if (b >= n_ch) {  // a rider workgroup (uniform): copy c's workgroup r of frame f
         const int64_t rj = b - n_ch;
@@ -602,9 +540,9 @@ void k_index1(Stage st, Frames fr, Bkt bk) {
     if (threadIdx.x < 12) s_P[threadIdx.x] = st.P[12 * (int64_t)f + threadIdx.x];
     Stage sf = st;
     sf.P_frame = s_P;
-    typename Stage::In in[IDX_BATCH];
-    uint32_t m[IDX_BATCH];
-    typename Stage::Payload pl[IDX_BATCH];
+    typename Stage::In in;
+    uint32_t m;
+    typename Stage::Payload pl;
     count_phase<Stage, true>(sf, fr, bk, f, j, in, m, pl);
     SHPL_IDX1_STAMP(1);
     frame_barrier(fr, bk, f, j);
@@ -637,11 +575,6 @@ int64_t index1_resident() {
     return (int64_t)cus * per_cu;
 }
 
-int n_chunks_for(int64_t max_points) {
-    const int64_t c = (max_points + IDX_CHUNK - 1) / IDX_CHUNK;
-    return (int)(c < 1 ? 1 : c);
-}
-
 constexpr size_t IDX_WS_HEAD = 256;  // single-frame [0, n] offsets
 
 size_t index_ws_bytes(int n_frames, int64_t max_points) {
@@ -658,18 +591,12 @@ int run_compaction(const Stage &st, int n_frames, int64_t max_points, const int6
     const dim3 grid(fr.n_chunks, n_frames);
     if constexpr (Stage::HAS_BUCKETS) {
         if (bk) {
-#ifndef SHPL_INDEX1
-#define SHPL_INDEX1 1
-#endif
-#ifndef SHPL_IDX1_RIDERS
-#define SHPL_IDX1_RIDERS 240
-#endif
             // (an error word is needed to report a failed barrier: without one, the two launches)
-            if (SHPL_INDEX1 && bk->bar && err && fr.n_chunks <= IDX1_MAX_CHUNKS &&
+            if (bk->bar && err && fr.n_chunks <= IDX1_MAX_CHUNKS &&
                 (int64_t)n_frames * fr.n_chunks <= index1_resident<Stage>()) {
-                // rider workgroups per copy and frame: SHPL_IDX1_RIDERS per copy over the batch, at most one per
+                // rider workgroups per copy and frame: IDX1_RIDERS per copy over the batch, at most one per
                 // 64 KiB of a frame's copy (the two-launch form's cp_blocks bound)
-                int per = SHPL_IDX1_RIDERS / n_frames;
+                int per = IDX1_RIDERS / n_frames;
                 if (per > bk->cp_blocks) per = bk->cp_blocks;
                 if (per < 1) per = 1;
                 Bkt b1 = *bk;
@@ -680,11 +607,8 @@ int run_compaction(const Stage &st, int n_frames, int64_t max_points, const int6
                 SHPL_LAUNCH_CHECK();
                 return SHPL_OK;
             }
-            bool rides[2] = {false, false};
-            for (int c = 0; c < 2; ++c)
-                if (bk->cp[c].row_bytes > 0) rides[bk->cp_at[c]] = true;
-            const dim3 grid0(fr.n_chunks + (rides[0] ? bk->cp_blocks : 0), n_frames);
-            const dim3 grid1(fr.n_chunks + (rides[1] ? bk->cp_blocks : 0), n_frames);
+            const dim3 grid0(fr.n_chunks + (bk->cp[0].row_bytes > 0 ? bk->cp_blocks : 0), n_frames);
+            const dim3 grid1(fr.n_chunks + (bk->cp[1].row_bytes > 0 ? bk->cp_blocks : 0), n_frames);
             hipLaunchKernelGGL((k_count<Stage, true>), grid0, dim3(IDX_BLOCK), 0, stream, st, fr, *bk);
             SHPL_LAUNCH_CHECK();
             hipLaunchKernelGGL((k_compact<Stage, true>), grid1, dim3(IDX_BLOCK), 0, stream, st, fr, *bk);

@@ -53,9 +53,6 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_pack(int64_t nnz, const int64_t 
 // ------------------------------------------------------------------ CSR
 constexpr int CSR_BLOCK = 1024;           // one workgroup per frame
 constexpr int CSR_TILES = 16384;          // LDS tile counters (64 KiB)
-#ifndef SHPL_CSR_PROBE
-#define SHPL_CSR_PROBE 0  // timing probes of k_csr_frame (wrong results): 1 return after the scan, 2 after placement
-#endif
 
 struct CsrIn {
     int direction, order, n_frames;
@@ -93,14 +90,15 @@ __device__ __forceinline__ uint64_t order_key(const CsrIn &c, int32_t e) {
 constexpr int CSR_BATCH = 8;     // entries per thread whose loads are in flight together
 constexpr int CSR_WIN = 10240;   // packed words staged in LDS for the rank fix-up (80 KiB)
 
-// Destinations of entries first + u*CSR_BLOCK (u < U), -1 for invalid or past e1.
+// Destinations of entries first + u * stride (u < U), -1 for invalid or past e1.
 // All loads of the batch are issued before any is used.
 template <bool HAS_COL, int U>
-__device__ __forceinline__ void keys_batch(const CsrIn &c, int64_t first, int64_t e1, int32_t (&key)[U]) {
+__device__ __forceinline__ void keys_batch(const CsrIn &c, int64_t first, int64_t stride, int64_t e1,
+                                           int32_t (&key)[U]) {
     int32_t r[U], k[U], p[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const int64_t e = first + (int64_t)u * CSR_BLOCK;
+        const int64_t e = first + u * stride;
         const bool ok = e < e1;
         r[u] = ok ? c.cell[e] : -1;
         k[u] = ok ? (HAS_COL ? c.col[e] : (int32_t)e) : -1;
@@ -175,21 +173,39 @@ __device__ __forceinline__ void tile_scan(int32_t *cnt, int32_t *wsum) {
         v[q] = cnt[threadIdx.x * CSR_PER_THREAD + q];
         sum += v[q];
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int32_t x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    int32_t run = x - sum;
-    for (int w = 0; w < wid; ++w) run += wsum[w];
+    int32_t run = block_excl_scan(sum, wsum);
 #pragma unroll
     for (int q = 0; q < CSR_PER_THREAD; ++q) {
         cnt[threadIdx.x * CSR_PER_THREAD + q] = run;
         run += v[q];
+    }
+}
+
+// The tail of a batched emission: entry ee[u] with destination key[u] goes to slot out_base + d[u] (d[u] < 0:
+// none) with its source row, value and column -- the columns' loads, then the sources' and values', then the
+// stores, each batch in flight together.
+template <bool HAS_COL>
+__device__ __forceinline__ void emit_batch(const CsrIn &c, int64_t out_base, const int32_t (&d)[CSR_BATCH],
+                                           const int32_t (&ee)[CSR_BATCH], const int32_t (&key)[CSR_BATCH],
+                                           int32_t *ent_dst, int32_t *ent_src, float *ent_val, int32_t *ent_col) {
+    int32_t kk[CSR_BATCH], src[CSR_BATCH];
+    float val[CSR_BATCH];
+#pragma unroll
+    for (int u = 0; u < CSR_BATCH; ++u) kk[u] = d[u] >= 0 ? (HAS_COL ? c.col[ee[u]] : ee[u]) : 0;
+#pragma unroll
+    for (int u = 0; u < CSR_BATCH; ++u) {
+        if (d[u] < 0) continue;
+        src[u] = c.direction == SHPL_BY_CELL ? c.pix[kk[u]] : c.cell[ee[u]];
+        val[u] = c.val[ee[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < CSR_BATCH; ++u) {
+        if (d[u] < 0) continue;
+        const int64_t o = out_base + d[u];
+        ent_dst[o] = key[u];
+        ent_src[o] = src[u];
+        ent_val[o] = val[u];
+        if (ent_col) ent_col[o] = kk[u];
     }
 }
 
@@ -213,7 +229,7 @@ __device__ void emit_sorted(const CsrIn &c, const uint64_t *words, int32_t n_val
             for (int32_t s = w0 + threadIdx.x; s < w1; s += CSR_BLOCK) win[s - w0] = words[s];
             __syncthreads();
             for (int32_t s0 = w0 + threadIdx.x; s0 < w1; s0 += CSR_BLOCK * CSR_BATCH) {
-                int32_t d[CSR_BATCH], ee[CSR_BATCH], kk[CSR_BATCH], key[CSR_BATCH];
+                int32_t d[CSR_BATCH], ee[CSR_BATCH], key[CSR_BATCH];
 #pragma unroll
                 for (int u = 0; u < CSR_BATCH; ++u) {
                     const int32_t s = s0 + u * CSR_BLOCK;
@@ -234,25 +250,7 @@ __device__ void emit_sorted(const CsrIn &c, const uint64_t *words, int32_t n_val
                     }
                     d[u] = a + rank;
                 }
-#pragma unroll
-                for (int u = 0; u < CSR_BATCH; ++u) kk[u] = d[u] >= 0 ? (HAS_COL ? c.col[ee[u]] : ee[u]) : 0;
-                int32_t src[CSR_BATCH];
-                float val[CSR_BATCH];
-#pragma unroll
-                for (int u = 0; u < CSR_BATCH; ++u) {
-                    if (d[u] < 0) continue;
-                    src[u] = c.direction == SHPL_BY_CELL ? c.pix[kk[u]] : c.cell[ee[u]];
-                    val[u] = c.val[ee[u]];
-                }
-#pragma unroll
-                for (int u = 0; u < CSR_BATCH; ++u) {
-                    if (d[u] < 0) continue;
-                    const int64_t o = out_base + d[u];
-                    ent_dst[o] = key[u];
-                    ent_src[o] = src[u];
-                    ent_val[o] = val[u];
-                    if (ent_col) ent_col[o] = kk[u];
-                }
+                emit_batch<HAS_COL>(c, out_base, d, ee, key, ent_dst, ent_src, ent_val, ent_col);
             }
             __syncthreads();  // the next window overwrites win
         }
@@ -306,6 +304,21 @@ __device__ __forceinline__ void clear_holes(const CsrIn &c, int f, int64_t from,
     for (int64_t d = from + threadIdx.x; d < hole_end; d += CSR_BLOCK) ent_dst[d] = -1;
 }
 
+// What the workgroup of a frame's last range clears (the range builder, k_bsort2; CSR_BLOCK threads): the
+// frame's slots from `from` (the end of its valid entries) to its capacity's end and, after the last frame, the
+// slots up to nnz_cap and the key ranges of the destinations from kend on (empty runs).
+__device__ __forceinline__ void clear_after(bool last_frame, int64_t from, int64_t cap_end, int64_t nnz_cap,
+                                            int64_t kend, int64_t n_keys, int32_t *ent_dst, int32_t *key_range) {
+    for (int64_t h = from + threadIdx.x; h < cap_end; h += CSR_BLOCK) ent_dst[h] = -1;
+    if (!last_frame) return;
+    for (int64_t h = cap_end + threadIdx.x; h < nnz_cap; h += CSR_BLOCK) ent_dst[h] = -1;
+    if (key_range)
+        for (int64_t k = kend + threadIdx.x; k < n_keys; k += CSR_BLOCK) {
+            key_range[2 * k] = 0;
+            key_range[2 * k + 1] = 0;
+        }
+}
+
 template <bool HAS_COL>
 __global__ __launch_bounds__(CSR_BLOCK) void k_csr_frame(CsrIn c, uint64_t *tmp, int64_t nnz_cap, int32_t *ent_dst,
                                                          int32_t *ent_src, float *ent_val, int32_t *ent_col) {
@@ -326,7 +339,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_frame(CsrIn c, uint64_t *tmp,
     // 1. histogram
     for (int64_t b = e0 + threadIdx.x; b < e1; b += (int64_t)CSR_BLOCK * CSR_BATCH) {
         int32_t key[CSR_BATCH];
-        keys_batch<HAS_COL>(c, b, e1, key);
+        keys_batch<HAS_COL>(c, b, CSR_BLOCK, e1, key);
 #pragma unroll
         for (int u = 0; u < CSR_BATCH; ++u) {
             const int64_t k = (int64_t)key[u] - kbase;
@@ -337,11 +350,10 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_frame(CsrIn c, uint64_t *tmp,
     // 2. exclusive scan
     tile_scan<CSR_TILES>(cnt, wsum);
     __syncthreads();
-    if (SHPL_CSR_PROBE == 1) return;
     // 3. placement of (destination << 32 | entry): cnt[t] advances from start(t) to end(t) = start(t+1)
     for (int64_t b = e0 + threadIdx.x; b < e1; b += (int64_t)CSR_BLOCK * CSR_BATCH) {
         int32_t key[CSR_BATCH];
-        keys_batch<HAS_COL>(c, b, e1, key);
+        keys_batch<HAS_COL>(c, b, CSR_BLOCK, e1, key);
 #pragma unroll
         for (int u = 0; u < CSR_BATCH; ++u) {
             const int64_t k = (int64_t)key[u] - kbase;
@@ -351,7 +363,6 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_frame(CsrIn c, uint64_t *tmp,
         }
     }
     block_publish();  // tmp was written by other waves of this workgroup through memory
-    if (SHPL_CSR_PROBE == 2) return;
     const int32_t n_valid = cnt[n_tiles - 1];
     // 4. rank fix-up
     emit_sorted<HAS_COL, CSR_WIN>(c, tmp + e0, n_valid, e0, kbase, c.log_tile, cnt, win, ent_dst, ent_src, ent_val, ent_col);
@@ -419,21 +430,13 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_csr_count(CsrIn c, SegIn g) {
     __syncthreads();
     const int64_t step = (int64_t)gridDim.x * SEG_BLOCK;
     for (int64_t b = e0 + (int64_t)blockIdx.x * SEG_BLOCK + threadIdx.x; b < e1; b += step * SEG_BATCH) {
-        int32_t r[SEG_BATCH], k[SEG_BATCH], p[SEG_BATCH];
-#pragma unroll
-        for (int u = 0; u < SEG_BATCH; ++u) {
-            const int64_t e = b + u * step;
-            const bool ok = e < e1;
-            r[u] = ok ? c.cell[e] : -1;
-            k[u] = ok ? (HAS_COL ? c.col[e] : (int32_t)e) : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < SEG_BATCH; ++u) p[u] = k[u] >= 0 ? c.pix[k[u]] : -1;
+        int32_t keys[SEG_BATCH];
+        keys_batch<HAS_COL>(c, b, step, e1, keys);
 #pragma unroll
         for (int u = 0; u < SEG_BATCH; ++u) {
             const int64_t e = b + u * step;
             if (e >= e1) continue;
-            int32_t key = (r[u] < 0 || k[u] < 0 || p[u] < 0) ? -1 : (c.direction == SHPL_BY_CELL ? r[u] : p[u]);
+            int32_t key = keys[u];
             const int64_t kk = (int64_t)key - kbase;
             if (key >= 0 && (kk < 0 || kk >= c.keys_per_frame)) key = -1;  // outside the frame: left out
             g.kbuf[e] = key;
@@ -467,20 +470,8 @@ __device__ int32_t seg_map(const SegIn &g, int f, int32_t *seg_of, int32_t *seg_
         seg_start[s] = 0;
         seg_lo[s] = 0;
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int32_t x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    int32_t run = x - sum, total = 0;
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w < wid) run += wsum[w];
-        total += wsum[w];
-    }
+    int32_t run = block_excl_scan(sum, wsum), total = 0;
+    for (int w = 0; w < BLOCK / 64; ++w) total += wsum[w];
     const int64_t S = g.S;
     auto seg_at = [&](int32_t excl) { return total ? (int)min(S - 1, (int64_t)excl * S / total) : 0; };
 #pragma unroll
@@ -595,10 +586,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_segment(CsrIn c, SegIn g, int
 // A range holding more than RANGE_LIST entries (a pathological frame) reads
 // its frame a second time and places 64-bit words in its own stretch of the
 // workspace instead.
-#ifndef SHPL_RANGE_KEYS
-#define SHPL_RANGE_KEYS 128
-#endif
-constexpr int RANGE_KEYS = SHPL_RANGE_KEYS;
+constexpr int RANGE_KEYS = 128;    // destinations per range
 constexpr int RANGE_LIST = 10240;  // words of one range in LDS (2 arrays, 80 KiB)
 constexpr int RANGE_BATCH = 16;    // entries per thread whose loads are in flight together
 
@@ -611,8 +599,7 @@ __device__ __forceinline__ void range_emit(const CsrIn &c, int32_t total, const 
                                            float *ent_val, int32_t *ent_col) {
     const bool entry_order = c.order == SHPL_ORDER_ENTRY || !HAS_COL;
     for (int32_t s0 = threadIdx.x; s0 < total; s0 += CSR_BLOCK * CSR_BATCH) {
-        int32_t d[CSR_BATCH], ee[CSR_BATCH], key[CSR_BATCH], kk[CSR_BATCH], src[CSR_BATCH];
-        float val[CSR_BATCH];
+        int32_t d[CSR_BATCH], ee[CSR_BATCH], key[CSR_BATCH];
 #pragma unroll
         for (int u = 0; u < CSR_BATCH; ++u) {
             const int32_t sl = s0 + u * CSR_BLOCK;
@@ -639,23 +626,7 @@ __device__ __forceinline__ void range_emit(const CsrIn &c, int32_t total, const 
             }
             d[u] = a + rank;
         }
-#pragma unroll
-        for (int u = 0; u < CSR_BATCH; ++u) kk[u] = d[u] >= 0 ? (HAS_COL ? c.col[ee[u]] : ee[u]) : 0;
-#pragma unroll
-        for (int u = 0; u < CSR_BATCH; ++u) {
-            if (d[u] < 0) continue;
-            src[u] = c.direction == SHPL_BY_CELL ? c.pix[kk[u]] : c.cell[ee[u]];
-            val[u] = c.val[ee[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < CSR_BATCH; ++u) {
-            if (d[u] < 0) continue;
-            const int64_t o = out0 + d[u];
-            ent_dst[o] = key[u];
-            ent_src[o] = src[u];
-            ent_val[o] = val[u];
-            if (ent_col) ent_col[o] = kk[u];
-        }
+        emit_batch<HAS_COL>(c, out0, d, ee, key, ent_dst, ent_src, ent_val, ent_col);
     }
 }
 
@@ -705,7 +676,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_range(CsrIn c, uint64_t *tmp,
     int32_t below = 0;
     for (int64_t b = e0 + threadIdx.x; b < e1; b += (int64_t)CSR_BLOCK * RANGE_BATCH) {
         int32_t key[RANGE_BATCH];
-        keys_batch<HAS_COL>(c, b, e1, key);
+        keys_batch<HAS_COL>(c, b, CSR_BLOCK, e1, key);
 #pragma unroll
         for (int u = 0; u < RANGE_BATCH; ++u) {
             const int64_t k = key[u];
@@ -732,17 +703,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_range(CsrIn c, uint64_t *tmp,
     const int32_t total = n_list;
     __syncthreads();  // wsum is reused by the scan
     // 2. exclusive scan: beg[t] = start of destination k0 + t; cnt becomes the fill cursor
-    const int32_t v = threadIdx.x < RANGE_KEYS ? cnt[threadIdx.x] : 0;
-    int32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    int32_t run = x - v;
-    for (int w = 0; w < wid; ++w) run += wsum[w];
+    const int32_t run = block_excl_scan(threadIdx.x < RANGE_KEYS ? cnt[threadIdx.x] : 0, wsum);
     if (threadIdx.x < RANGE_KEYS) {
         beg[threadIdx.x] = run;
         cnt[threadIdx.x] = run;
@@ -761,7 +722,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_range(CsrIn c, uint64_t *tmp,
         uint64_t *words = tmp + out0;  // this range's stretch of the frame's slots
         for (int64_t b = e0 + threadIdx.x; b < e1; b += (int64_t)CSR_BLOCK * RANGE_BATCH) {
             int32_t key[RANGE_BATCH];
-            keys_batch<HAS_COL>(c, b, e1, key);
+            keys_batch<HAS_COL>(c, b, CSR_BLOCK, e1, key);
 #pragma unroll
             for (int u = 0; u < RANGE_BATCH; ++u) {
                 const int64_t k = key[u];
@@ -781,15 +742,8 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_csr_range(CsrIn c, uint64_t *tmp,
             key_range[2 * (k0 + t) + 1] = (int32_t)(out0 + cnt[t]);
         }
     }
-    if (r != n_ranges - 1) return;
-    for (int64_t h = out0 + total + threadIdx.x; h < cap_end; h += CSR_BLOCK) ent_dst[h] = -1;
-    if (f != c.n_frames - 1) return;
-    for (int64_t h = cap_end + threadIdx.x; h < nnz_cap; h += CSR_BLOCK) ent_dst[h] = -1;
-    if (key_range)
-        for (int64_t k = kend + threadIdx.x; k < n_keys; k += CSR_BLOCK) {
-            key_range[2 * k] = 0;
-            key_range[2 * k + 1] = 0;
-        }
+    if (r == n_ranges - 1)
+        clear_after(f == c.n_frames - 1, out0 + total, cap_end, nnz_cap, kend, n_keys, ent_dst, key_range);
 }
 
 static_assert(RANGE_KEYS == 128, "the sort multisplit matches 7 destination bits");
@@ -798,26 +752,27 @@ static_assert(BK_KEYS == RANGE_KEYS, "the index builder's buckets are the sort's
 // A bucket's counting sort (k_bsort2): words[0, n) = the bucket of destinations
 // [k0, k0 + nk) (global ids, word = local destination << 24 | entry - e0) in entry order, placed stably
 // by destination at out0.. with source row, value and column; key_range of its destinations. BY_CELL:
-// source = pix[e]; BY_PIXEL: source = cell[e] and column e (the builder's identity columns). All threads
+// source = pix[e]; BY_PIXEL: source = cell[e]; the column is e (the index builder's identity columns). All threads
 // call it. The bucket is cut into one contiguous slice per wave: the slices' per-destination counts
 // (LDS atomics), one exclusive scan over (destination, slice) gives every (slice, destination) its first
 // slot, and each wave then places its own slice in order, 64 words at a time (ballots over the 7
 // destination bits rank a word among its batch's equals, one lane per destination moves the slice's
 // cursor) -- three block barriers whatever the bucket's size. Buckets of at most LCAP words are read
 // into LDS first together with their entries' source rows and values (every load in flight at once).
-template <int BLOCK, int LCAP>
+constexpr int BS_BLOCK = CSR_BLOCK;  // threads of a k_bsort2 workgroup (the horizon's 2 k-entry pixel buckets: 3 rounds)
+constexpr int BS_LCAP = 4096;   // bucket words staged in LDS with their source rows and values (48 KiB)
+
 __device__ __forceinline__ void bucket_sort_emit(const uint32_t *words, int32_t n, int64_t e0, int64_t out0,
-                                                 int64_t k0, int nk, int direction, const int32_t *col,
-                                                 const int32_t *cell, const int32_t *pix, const float *vals,
-                                                 int32_t *ent_dst, int32_t *ent_src, float *ent_val,
-                                                 int32_t *ent_col, int32_t *key_range, int2 *heads = nullptr,
-                                                 int head_k = 0) {
-    constexpr int NW = BLOCK / 64;
+                                                 int64_t k0, int nk, int direction, const int32_t *cell,
+                                                 const int32_t *pix, const float *vals, int32_t *ent_dst,
+                                                 int32_t *ent_src, float *ent_val, int32_t *ent_col,
+                                                 int32_t *key_range, int2 *heads, int head_k) {
+    constexpr int BLOCK = BS_BLOCK, LCAP = BS_LCAP, NW = BLOCK / 64;
     __shared__ int32_t cnt[NW][RANGE_KEYS], s_tot[RANGE_KEYS], s_beg[RANGE_KEYS];
     __shared__ uint64_t s_peer[NW][RANGE_KEYS];  // per wave and destination: its batch's lanes (zero between uses)
-    __shared__ uint32_t l_w[LCAP > 0 ? LCAP : 1];
-    __shared__ int32_t l_s[LCAP > 0 ? LCAP : 1];
-    __shared__ float l_v[LCAP > 0 ? LCAP : 1];
+    __shared__ uint32_t l_w[LCAP];
+    __shared__ int32_t l_s[LCAP];
+    __shared__ float l_v[LCAP];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const bool staged = n <= LCAP;
     const int32_t L = (n + NW - 1) / NW;  // words per wave slice
@@ -838,7 +793,7 @@ __device__ __forceinline__ void bucket_sort_emit(const uint32_t *words, int32_t 
             for (int u = 0; u < 4; ++u) {
                 if (i0 + u * BLOCK >= n) continue;
                 const int64_t e = e0 + (w[u] & 0xffffffu);
-                const int32_t kk = col ? col[e] : (int32_t)e;
+                const int32_t kk = (int32_t)e;  // the entry's column: itself
                 vl[u] = vals[e];
                 sr[u] = direction == SHPL_BY_CELL ? pix[kk] : cell[e];
             }
@@ -893,25 +848,17 @@ __device__ __forceinline__ void bucket_sort_emit(const uint32_t *words, int32_t 
                 w = l_w[i];
                 src = l_s[i];
                 val = l_v[i];
-                if (ent_col) kk = col ? col[e0 + (w & 0xffffffu)] : (int32_t)(e0 + (w & 0xffffffu));
+                if (ent_col) kk = (int32_t)(e0 + (w & 0xffffffu));
             } else {
                 w = words[i];
                 const int64_t e = e0 + (w & 0xffffffu);
-                kk = col ? col[e] : (int32_t)e;
+                kk = (int32_t)e;
                 val = vals[e];
                 src = direction == SHPL_BY_CELL ? pix[kk] : cell[e];
             }
         }
         const int t = (int)(w >> 24);
-        // the batch's lanes of destination t: each ORs its bit into the wave's word of t, reads it back, and the
-        // lanes zero it again (one wave's LDS operations run in order; 7 ballots over the destination bits cost
-        // more VALU)
-        uint64_t peers = 0;
-        if (ok) atomicOr(reinterpret_cast<unsigned long long *>(&s_peer[wid][t]), 1ull << lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (ok) peers = s_peer[wid][t];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (ok) s_peer[wid][t] = 0;
+        const uint64_t peers = wave_peers(&s_peer[wid][t], ok);  // the batch's lanes of destination t
         const int32_t rank = (int32_t)lane_rank(peers);
         const int32_t base = ok ? cnt[wid][t] : 0;
         // the batch's last lane of each destination moves the slice's cursor (after every lane's read: one
@@ -956,8 +903,6 @@ struct BsIn {
     int64_t nnz_cap;
 };
 
-constexpr int BS_BLOCK = 1024;  // threads of a k_bsort2 workgroup (the horizon's 2 k-entry pixel buckets: 3 rounds)
-constexpr int BS_LCAP = 4096;   // bucket words staged in LDS with their source rows and values (48 KiB)
 
 __global__ __launch_bounds__(BS_BLOCK) void k_bsort2(BsIn in, BsSide s0, BsSide s1) {
     __shared__ uint32_t one[1];
@@ -1001,18 +946,11 @@ __global__ __launch_bounds__(BS_BLOCK) void k_bsort2(BsIn in, BsSide s0, BsSide 
         __syncthreads();
     }
     const int64_t out0 = p0 + start;
-    bucket_sort_emit<BS_BLOCK, BS_LCAP>(W, n, p0, out0, k0, nk, direction, nullptr, in.cell, in.pix, in.val, sd.ent_dst,
-                                        sd.ent_src, sd.ent_val, sd.ent_col, sd.key_range, sd.heads, sd.head_k);
+    bucket_sort_emit(W, n, p0, out0, k0, nk, direction, in.cell, in.pix, in.val, sd.ent_dst, sd.ent_src, sd.ent_val,
+                     sd.ent_col, sd.key_range, sd.heads, sd.head_k);
     // the frame's unused capacity (its last range), the slots and key ranges after the last frame
-    if (q != sd.nr - 1) return;
-    for (int64_t h = p0 + valid + threadIdx.x; h < cap_end; h += BS_BLOCK) sd.ent_dst[h] = -1;
-    if (f != in.n_frames - 1) return;
-    for (int64_t h = cap_end + threadIdx.x; h < sd.nnz_cap; h += BS_BLOCK) sd.ent_dst[h] = -1;
-    if (sd.key_range)
-        for (int64_t kk = kend + threadIdx.x; kk < sd.n_keys; kk += BS_BLOCK) {
-            sd.key_range[2 * kk] = 0;
-            sd.key_range[2 * kk + 1] = 0;
-        }
+    if (q == sd.nr - 1)
+        clear_after(f == in.n_frames - 1, p0 + valid, cap_end, sd.nnz_cap, kend, sd.n_keys, sd.ent_dst, sd.key_range);
 }
 
 }  // namespace
@@ -1035,18 +973,14 @@ extern "C" int shpl_pack_map(int64_t nnz, const int64_t *d_mij, const float *d_v
     const int64_t n = nnz > n_cols ? nnz : n_cols;
     const int grid = grid_for(n > 0 ? n : 1, SHPL_BLOCK, 4096);
     hipStream_t s = (hipStream_t)stream;
-    if (idx_itype == SHPL_I32)
-        hipLaunchKernelGGL(k_pack<int32_t>, dim3(grid), dim3(SHPL_BLOCK), 0, s, nnz, d_mij, d_values, n_values,
-                           n_rows, n_cols, (const int32_t *)d_idx, img_b, img_h, img_w, row_base, col_base,
-                           pix_base, d_cell, d_col, d_val, d_pix, d_err);
-    else if (idx_itype == SHPL_I64)
-        hipLaunchKernelGGL(k_pack<int64_t>, dim3(grid), dim3(SHPL_BLOCK), 0, s, nnz, d_mij, d_values, n_values,
-                           n_rows, n_cols, (const int64_t *)d_idx, img_b, img_h, img_w, row_base, col_base,
-                           pix_base, d_cell, d_col, d_val, d_pix, d_err);
-    else
-        return SHPL_ERR_ARG;
-    SHPL_LAUNCH_CHECK();
-    return SHPL_OK;
+    return by_itype(idx_itype, [&](auto it) -> int {
+        typedef typename decltype(it)::T IT;
+        hipLaunchKernelGGL(k_pack<IT>, dim3(grid), dim3(SHPL_BLOCK), 0, s, nnz, d_mij, d_values, n_values, n_rows,
+                           n_cols, (const IT *)d_idx, img_b, img_h, img_w, row_base, col_base, pix_base, d_cell, d_col,
+                           d_val, d_pix, d_err);
+        SHPL_LAUNCH_CHECK();
+        return SHPL_OK;
+    });
 }
 
 // Workspace: [tmp words | segmented path: kbuf | sorted words | counters].
@@ -1072,6 +1006,37 @@ CsrLayout csr_layout(int64_t n_keys, int64_t nnz_cap) {
     l.counters = l.sorted + align_up(sizeof(uint64_t) * cap, 256);
     l.total = l.counters + align_up(2 * sizeof(int32_t) * (size_t)seg_cap_of(nnz_cap), 256);
     return l;
+}
+
+// The builder that sorts one shpl_build_csr_path call, or the status of a call none takes.
+//  - Entry offsets inside a frame travel in 24 bits in the range builder, so it takes capacities under 2^24
+//    entries only; key ranges asked for beyond that: SHPL_ERR_BAD_SHAPE.
+//  - SHPL_CSR_FRAME by name is the frame builder (one workgroup per frame), followed by k_key_range when key
+//    ranges are asked for.
+//  - Otherwise key ranges come from the range builder, whatever the path: they fall out of its pass.
+//  - Without key ranges the range builder is taken by name (SHPL_CSR_RANGE) or, by default, for batches under
+//    SEG_FRAMES frames of at most RANGE_MAX_KEYS destinations each (every workgroup reads its whole frame, so
+//    many ranges per frame would multiply those reads) -- given the small capacity in both cases.
+//  - What is left sorts by segments when named (SHPL_CSR_SEGMENT) or, by default, under SEG_FRAMES frames
+//    (config 3, 4 frames: 0.305 -> 0.259 ms per step), provided the segment workspace and counters fit
+//    (seg_fits); else, and from SEG_FRAMES frames on, one workgroup per frame fills enough of the chip and,
+//    overlapped with the dense stream, measured faster (config 2, 64 frames: 2.34 vs 2.42 ms per step).
+// Tests and measurements force a path by name; a named path that cannot run falls back to the frame builder.
+enum class CsrBuilder { RANGE, FRAME, FRAME_RANGES, SEGMENT };
+
+int csr_builder(int path, bool key_ranges, int n_frames, int64_t keys_per_frame, int64_t nnz_cap, bool seg_fits,
+                CsrBuilder *builder) {
+    const bool small_cap = nnz_cap < ((int64_t)1 << 24), small_batch = n_frames < SEG_FRAMES;
+    if (key_ranges && !small_cap) return SHPL_ERR_BAD_SHAPE;
+    if (path == SHPL_CSR_FRAME)
+        *builder = key_ranges ? CsrBuilder::FRAME_RANGES : CsrBuilder::FRAME;
+    else if (key_ranges || (small_cap && (path == SHPL_CSR_AUTO ? small_batch && keys_per_frame <= RANGE_MAX_KEYS
+                                                                : path == SHPL_CSR_RANGE)))
+        *builder = CsrBuilder::RANGE;
+    else
+        *builder = (path == SHPL_CSR_AUTO ? small_batch : path == SHPL_CSR_SEGMENT) && seg_fits ? CsrBuilder::SEGMENT
+                                                                                                : CsrBuilder::FRAME;
+    return SHPL_OK;
 }
 }  // namespace
 
@@ -1104,39 +1069,6 @@ extern "C" int shpl_build_csr_path(int path, int direction, int order, int n_fra
     }
     if (!d_cell || !d_val || !d_pix || !csr->ent_dst || !csr->ent_src || !csr->ent_val || !d_ws) return SHPL_ERR_ARG;
     if (direction == SHPL_BY_PIXEL && !csr->ent_col) return SHPL_ERR_ARG;
-    const CsrLayout lay = csr_layout(csr->n_keys, nnz_cap);
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t *ws = (uint8_t *)d_ws;
-    // The range CSR: always when key ranges are asked for; by default for batches under
-    // SEG_FRAMES frames of at most RANGE_MAX_KEYS destinations (each workgroup reads its
-    // whole frame, so many ranges per frame would multiply those reads).
-    // (entry offsets inside a frame travel in 24 bits: capacities under 2^24 entries)
-    const bool small_cap = nnz_cap < ((int64_t)1 << 24);
-    if (csr->key_range && !small_cap) return SHPL_ERR_BAD_SHAPE;
-    // key ranges from the frame builder instead (asked for by name): its sort, then k_key_range
-    const bool frame_ranges = csr->key_range != nullptr && path == SHPL_CSR_FRAME;
-    const bool ranged = (csr->key_range != nullptr && !frame_ranges) ||
-                        (small_cap && !frame_ranges && (path != SHPL_CSR_AUTO
-                                           ? path == SHPL_CSR_RANGE
-                                           : (n_frames < SEG_FRAMES && keys_per_frame <= RANGE_MAX_KEYS)));
-    if (ranged) {
-        if (ws_bytes < align_up(sizeof(uint64_t) * (size_t)nnz_cap, 256)) return SHPL_ERR_WORKSPACE;
-        const int64_t n_ranges = (keys_per_frame + RANGE_KEYS - 1) / RANGE_KEYS;
-        if (n_ranges > 65535) return SHPL_ERR_BAD_SHAPE;
-        CsrIn c{direction, order, n_frames, d_frame_off, d_frame_nnz, keys_per_frame, 0,
-                d_cell, d_col, d_pix, d_val};
-        const dim3 grid((unsigned)n_ranges, (unsigned)n_frames);
-        if (d_col)
-            hipLaunchKernelGGL(k_csr_range<true>, grid, dim3(CSR_BLOCK), 0, st, c, (uint64_t *)ws, nnz_cap,
-                               csr->n_keys, (int)n_ranges, csr->ent_dst, csr->ent_src, csr->ent_val, csr->ent_col,
-                               csr->key_range);
-        else
-            hipLaunchKernelGGL(k_csr_range<false>, grid, dim3(CSR_BLOCK), 0, st, c, (uint64_t *)ws, nnz_cap,
-                               csr->n_keys, (int)n_ranges, csr->ent_dst, csr->ent_src, csr->ent_val, csr->ent_col,
-                               csr->key_range);
-        SHPL_LAUNCH_CHECK();
-        return SHPL_OK;
-    }
     // segments: about SEG_TARGET entries each (estimated from the capacity per frame)
     const int64_t est = (nnz_cap + n_frames - 1) / n_frames;
     int log_bin = 0;
@@ -1145,43 +1077,49 @@ extern "C" int shpl_build_csr_path(int path, int direction, int order, int n_fra
     int64_t S = (est + SEG_TARGET - 1) / SEG_TARGET;
     if (S < 1) S = 1;
     if (S > n_bins) S = n_bins;
-    // Small batches take the segmented path (config 3, 4 frames: 0.305 -> 0.259 ms per step); from
-    // SEG_FRAMES frames on, one workgroup per frame fills enough of the chip and, overlapped with the
-    // dense stream, measured faster (config 2, 64 frames: 2.34 vs 2.42 ms per step).
-    // shpl_build_csr_path(SHPL_CSR_FRAME | _SEGMENT | _RANGE, ...) forces a path (tests, measurements).
-    const bool want = path != SHPL_CSR_AUTO ? path == SHPL_CSR_SEGMENT : n_frames < SEG_FRAMES;
-    const bool segmented = want && ws_bytes >= lay.total && (int64_t)n_frames * (n_bins + S) <= seg_cap_of(nnz_cap);
-    if (frame_ranges) {
-        hipLaunchKernelGGL(k_zero32, dim3(grid_for(2 * csr->n_keys, SEG_BLOCK, 4096)), dim3(SEG_BLOCK), 0, st,
-                           csr->key_range, 2 * csr->n_keys);
+    const CsrLayout lay = csr_layout(csr->n_keys, nnz_cap);
+    const bool seg_fits = ws_bytes >= lay.total && (int64_t)n_frames * (n_bins + S) <= seg_cap_of(nnz_cap);
+    CsrBuilder builder;
+    const int rc = csr_builder(path, csr->key_range != nullptr, n_frames, keys_per_frame, nnz_cap, seg_fits, &builder);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t *ws = (uint8_t *)d_ws;
+    CsrIn c{direction, order, n_frames, d_frame_off, d_frame_nnz, keys_per_frame, 0, d_cell, d_col, d_pix, d_val};
+    const size_t tmp_bytes = align_up(sizeof(uint64_t) * (size_t)nnz_cap, 256);  // all but the segment builder need
+    const int64_t spans = d_frame_nnz ? (nnz_cap + HOLE_SPAN - 1) / HOLE_SPAN : 0;  // workgroups clearing the holes
+    if (builder == CsrBuilder::RANGE) {
+        if (ws_bytes < tmp_bytes) return SHPL_ERR_WORKSPACE;
+        const int64_t n_ranges = (keys_per_frame + RANGE_KEYS - 1) / RANGE_KEYS;
+        if (n_ranges > 65535) return SHPL_ERR_BAD_SHAPE;
+        by_bools([&](auto HAS_COL) {
+            hipLaunchKernelGGL(k_csr_range<HAS_COL.value>, dim3((unsigned)n_ranges, (unsigned)n_frames), dim3(CSR_BLOCK),
+                               0, st, c, (uint64_t *)ws, nnz_cap, csr->n_keys, (int)n_ranges, csr->ent_dst,
+                               csr->ent_src, csr->ent_val, csr->ent_col, csr->key_range);
+        }, d_col != nullptr);
         SHPL_LAUNCH_CHECK();
+        return SHPL_OK;
     }
-    if (!segmented) {
-        // one workgroup per frame; needs only the tmp words
-        if (ws_bytes < align_up(sizeof(uint64_t) * (size_t)nnz_cap, 256)) return SHPL_ERR_WORKSPACE;
-        int log_tile = 0;
-        while (((keys_per_frame - 1) >> log_tile) + 1 > CSR_TILES) ++log_tile;
-        CsrIn c{direction, order, n_frames, d_frame_off, d_frame_nnz, keys_per_frame, log_tile,
-                d_cell, d_col, d_pix, d_val};
-        // n_frames sorting workgroups + the workgroups clearing the unused capacity
-        const int64_t spans = d_frame_nnz ? (nnz_cap + HOLE_SPAN - 1) / HOLE_SPAN : 0;
-        const dim3 grid((unsigned)(n_frames + spans));
-        if (d_col)
-            hipLaunchKernelGGL(k_csr_frame<true>, grid, dim3(CSR_BLOCK), 0, st, c, (uint64_t *)ws, nnz_cap,
-                               csr->ent_dst, csr->ent_src, csr->ent_val, csr->ent_col);
-        else
-            hipLaunchKernelGGL(k_csr_frame<false>, grid, dim3(CSR_BLOCK), 0, st, c, (uint64_t *)ws, nnz_cap,
-                               csr->ent_dst, csr->ent_src, csr->ent_val, csr->ent_col);
+    if (builder != CsrBuilder::SEGMENT) {  // one workgroup per frame (+ the hole spans)
+        const bool ranges = builder == CsrBuilder::FRAME_RANGES;
+        if (ranges) {
+            hipLaunchKernelGGL(k_zero32, dim3(grid_for(2 * csr->n_keys, SEG_BLOCK, 4096)), dim3(SEG_BLOCK), 0, st,
+                               csr->key_range, 2 * csr->n_keys);
+            SHPL_LAUNCH_CHECK();
+        }
+        if (ws_bytes < tmp_bytes) return SHPL_ERR_WORKSPACE;
+        while (((keys_per_frame - 1) >> c.log_tile) + 1 > CSR_TILES) ++c.log_tile;
+        by_bools([&](auto HAS_COL) {
+            hipLaunchKernelGGL(k_csr_frame<HAS_COL.value>, dim3((unsigned)(n_frames + spans)), dim3(CSR_BLOCK), 0, st,
+                               c, (uint64_t *)ws, nnz_cap, csr->ent_dst, csr->ent_src, csr->ent_val, csr->ent_col);
+        }, d_col != nullptr);
         SHPL_LAUNCH_CHECK();
-        if (frame_ranges) {
+        if (ranges) {
             hipLaunchKernelGGL(k_key_range, dim3(grid_for(nnz_cap, SEG_BLOCK, 4096)), dim3(SEG_BLOCK), 0, st,
                                csr->ent_dst, nnz_cap, csr->key_range);
             SHPL_LAUNCH_CHECK();
         }
         return SHPL_OK;
     }
-    CsrIn c{direction, order, n_frames, d_frame_off, d_frame_nnz, keys_per_frame, 0,
-            d_cell, d_col, d_pix, d_val};
     SegIn g = {};
     g.S = (int)S;
     g.n_bins = (int)n_bins;
@@ -1196,21 +1134,16 @@ extern "C" int shpl_build_csr_path(int path, int direction, int order, int n_fra
     SHPL_LAUNCH_CHECK();
     const int gx = (int)(est / 1024 < 1 ? 1 : (est / 1024 > 1024 ? 1024 : est / 1024));
     const dim3 grid_fr((unsigned)gx, (unsigned)n_frames);
-    if (d_col)
-        hipLaunchKernelGGL(k_csr_count<true>, grid_fr, dim3(SEG_BLOCK), 0, st, c, g);
-    else
-        hipLaunchKernelGGL(k_csr_count<false>, grid_fr, dim3(SEG_BLOCK), 0, st, c, g);
+    by_bools([&](auto HAS_COL) { hipLaunchKernelGGL(k_csr_count<HAS_COL.value>, grid_fr, dim3(SEG_BLOCK), 0, st, c, g); },
+             d_col != nullptr);
     SHPL_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_csr_bucket, grid_fr, dim3(SEG_BLOCK), 0, st, c, g);
     SHPL_LAUNCH_CHECK();
-    const int64_t spans = d_frame_nnz ? (nnz_cap + HOLE_SPAN - 1) / HOLE_SPAN : 0;
     const dim3 grid_seg((unsigned)S, (unsigned)(n_frames + (spans + S - 1) / S));
-    if (d_col)
-        hipLaunchKernelGGL(k_csr_segment<true>, grid_seg, dim3(CSR_BLOCK), 0, st, c, g, nnz_cap, csr->ent_dst,
+    by_bools([&](auto HAS_COL) {
+        hipLaunchKernelGGL(k_csr_segment<HAS_COL.value>, grid_seg, dim3(CSR_BLOCK), 0, st, c, g, nnz_cap, csr->ent_dst,
                            csr->ent_src, csr->ent_val, csr->ent_col);
-    else
-        hipLaunchKernelGGL(k_csr_segment<false>, grid_seg, dim3(CSR_BLOCK), 0, st, c, g, nnz_cap, csr->ent_dst,
-                           csr->ent_src, csr->ent_val, csr->ent_col);
+    }, d_col != nullptr);
     SHPL_LAUNCH_CHECK();
     return SHPL_OK;
 }
@@ -1232,9 +1165,8 @@ extern "C" int shpl_build_csr_buckets(const shpl_buckets *bk, const shpl_csr *by
     if (rc) return rc;
     if (bk->ws_bytes < need) return SHPL_ERR_WORKSPACE;
     if (bk->nnz_cap > 0 && (!bk->cell || !bk->pix || !bk->val)) return SHPL_ERR_ARG;
-    const int64_t chunks = (bk->max_points_per_frame + 1023) / 1024;
-    const BkLayout l = bk_layout(bk->n_frames, (int)(chunks < 1 ? 1 : chunks), bk->nnz_cap, bk->cells_per_frame,
-                                 bk->pix_per_frame);
+    const BkLayout l = bk_layout(bk->n_frames, n_chunks_for(bk->max_points_per_frame), bk->nnz_cap,
+                                 bk->cells_per_frame, bk->pix_per_frame);
     const shpl_csr *cs[2] = {by_cell, by_pixel};
     BsSide s[2] = {};
     for (int k = 0; k < 2; ++k) {

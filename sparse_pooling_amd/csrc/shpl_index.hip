@@ -5,9 +5,9 @@
 //   gen_sparse_pooling_input_avod           avod/avod/utils/sparse_pool_utils.py:6-20
 //   produce_sparse_pooling_input            avod/avod/utils/sparse_pool_utils.py:22-58
 //
-// Two launches over 4096-point chunks of every frame (shpl_compact.h): a
+// Two launches over IDX_CHUNK-point chunks of every frame (shpl_compact.h): a
 // per-chunk count of the kept points, then the placement, where each thread
-// evaluates one point per row and the kept points are ranked by wave ballots
+// evaluates one point and the kept points are ranked by wave ballots
 // + an LDS prefix and written in point order (a stable compaction). A frame's
 // entries start at its first input point ("capacity layout"); the tail up to
 // the next frame is filled with -1 sentinels that every consumer skips, so no
@@ -52,11 +52,7 @@ struct Geometry {
 
 // 1 / s when s is a power of two (its reciprocal exact, so x * (1 / s) is bitwise x / s for every finite x that
 // stays normal -- the image and voxel indices here), else 0: the division then stays a division.
-#ifndef SHPL_POW2_DIV
-#define SHPL_POW2_DIV 1
-#endif
 inline double pow2_reciprocal(double s) {
-    if (!SHPL_POW2_DIV) return 0.0;
     int e = 0;
     return (s > 0.0 && frexp(s, &e) == 0.5 && e > -1000 && e < 1000) ? ldexp(1.0, 1 - e) : 0.0;
 }
@@ -313,19 +309,12 @@ static int build_index(int n_frames, const int64_t *d_point_offsets, const int64
                        const float *d_mval, int32_t *d_cell, int32_t *d_pix, float *d_val, int64_t *d_mij,
                        int64_t *d_flip, int64_t *d_frame_nnz, int64_t *d_frame_out_off, uint32_t *d_err, void *d_ws,
                        size_t ws_bytes, hipStream_t s, const Bkt *bk) {
-#define SHPL_FUSED(PT, VT)                                                                       \
-    {                                                                                            \
-        FusedStage<PT, VT> st{d_points, d_voxels, vox_stride, d_P, g, d_mval, d_cell, d_pix,     \
-                              d_val, d_mij, d_flip, d_err};                                      \
-        return run_compaction(st, n_frames, max_points_per_frame, d_point_offsets, d_point_counts, d_frame_nnz, \
-                              d_frame_out_off, d_err, d_ws, ws_bytes, s, bk);                    \
-    }
-    if (points_dtype == SHPL_F64 && voxels_itype == SHPL_I64) SHPL_FUSED(double, int64_t)
-    if (points_dtype == SHPL_F64 && voxels_itype == SHPL_I32) SHPL_FUSED(double, int32_t)
-    if (points_dtype == SHPL_F32 && voxels_itype == SHPL_I64) SHPL_FUSED(float, int64_t)
-    if (points_dtype == SHPL_F32 && voxels_itype == SHPL_I32) SHPL_FUSED(float, int32_t)
-#undef SHPL_FUSED
-    return SHPL_ERR_ARG;
+    return by_point_types(points_dtype, voxels_itype, [&](auto pt, auto vt) {
+        FusedStage<typename decltype(pt)::T, typename decltype(vt)::T> st{
+            d_points, d_voxels, vox_stride, d_P, g, d_mval, d_cell, d_pix, d_val, d_mij, d_flip, d_err};
+        return run_compaction(st, n_frames, max_points_per_frame, d_point_offsets, d_point_counts, d_frame_nnz,
+                              d_frame_out_off, d_err, d_ws, ws_bytes, s, bk);
+    });
 }
 
 static int index_args(int n_frames, const int64_t *d_point_offsets, int64_t max_points_per_frame,
@@ -402,14 +391,8 @@ extern "C" int shpl_build_index_buckets(int n_frames, const int64_t *d_point_off
     const BkLayout l = bk_layout(n_frames, n_chunks_for(max_points_per_frame), nnz_cap, g.n_cells, g.n_pix);
     if (bkt_bytes < l.bytes) return SHPL_ERR_WORKSPACE;
     char *b = (char *)d_bkt;
-    // which index launch each rider copy rides (SHPL_RIDERS: 0 = cell copy with the count, pixel copy with the
-    // placement; 1 = both with the count; 2 = both with the placement)
-#ifndef SHPL_RIDERS
-#define SHPL_RIDERS 0
-#endif
     Bkt bk{{l.nr[0], l.nr[1]}, l.nrmax, nnz_cap, (int32_t *)(b + l.hist), (int32_t *)(b + l.ext),
-           (uint32_t *)(b + l.words), {}, {SHPL_RIDERS == 2 ? 1 : 0, SHPL_RIDERS == 1 ? 0 : 1}, 0,
-           (int32_t *)(b + l.bar)};
+           (uint32_t *)(b + l.words), {}, 0, (int32_t *)(b + l.bar)};
     const shpl_pass_copy *cps[2] = {cell_copy, pixel_copy};
     int64_t copy_bytes = 0;
     for (int k = 0; k < 2; ++k) {
@@ -444,18 +427,11 @@ extern "C" int shpl_gen_index(int64_t n, const void *d_points, int points_dtype,
     int64_t *off;
     int rc = single_frame_offsets(n, d_ws, ws_bytes, s, &off);
     if (rc) return rc;
-#define SHPL_GEN(PT, VT)                                                                          \
-    {                                                                                             \
-        GenStage<PT, VT> st{d_points, d_voxels, vox_stride, d_P, im_w, im_h, d_bv_index,          \
-                            d_img_index, ld};                                                     \
-        return run_compaction(st, 1, n, off, nullptr, d_nv, nullptr, nullptr, d_ws, ws_bytes, s);   \
-    }
-    if (points_dtype == SHPL_F64 && voxels_itype == SHPL_I64) SHPL_GEN(double, int64_t)
-    if (points_dtype == SHPL_F64 && voxels_itype == SHPL_I32) SHPL_GEN(double, int32_t)
-    if (points_dtype == SHPL_F32 && voxels_itype == SHPL_I64) SHPL_GEN(float, int64_t)
-    if (points_dtype == SHPL_F32 && voxels_itype == SHPL_I32) SHPL_GEN(float, int32_t)
-#undef SHPL_GEN
-    return SHPL_ERR_ARG;
+    return by_point_types(points_dtype, voxels_itype, [&](auto pt, auto vt) {
+        GenStage<typename decltype(pt)::T, typename decltype(vt)::T> st{
+            d_points, d_voxels, vox_stride, d_P, im_w, im_h, d_bv_index, d_img_index, ld};
+        return run_compaction(st, 1, n, off, nullptr, d_nv, nullptr, nullptr, d_ws, ws_bytes, s);
+    });
 }
 
 extern "C" int shpl_produce_index(int64_t nv, const void *d_bv_index, int bv_itype, int64_t bv_stride,
@@ -471,15 +447,11 @@ extern "C" int shpl_produce_index(int64_t nv, const void *d_bv_index, int bv_ity
     int64_t *off;
     int rc = single_frame_offsets(nv, d_ws, ws_bytes, s, &off);
     if (rc) return rc;
-    if (bv_itype == SHPL_I64) {
-        ProduceStage<int64_t> st{d_bv_index, bv_stride, d_img_index, ld, g, d_mij, d_flip, d_cell, d_pix, d_err};
+    return by_itype(bv_itype, [&](auto vt) {
+        ProduceStage<typename decltype(vt)::T> st{d_bv_index, bv_stride, d_img_index, ld, g,
+                                                  d_mij, d_flip, d_cell, d_pix, d_err};
         return run_compaction(st, 1, nv, off, nullptr, d_nk, nullptr, d_err, d_ws, ws_bytes, s);
-    }
-    if (bv_itype == SHPL_I32) {
-        ProduceStage<int32_t> st{d_bv_index, bv_stride, d_img_index, ld, g, d_mij, d_flip, d_cell, d_pix, d_err};
-        return run_compaction(st, 1, nv, off, nullptr, d_nk, nullptr, d_err, d_ws, ws_bytes, s);
-    }
-    return SHPL_ERR_ARG;
+    });
 }
 
 #if SHPL_IDX1_PROBE

@@ -871,8 +871,7 @@ int plan(int direction, int dtype, const shpl_csr *csr, const void *d_src, int64
     return SHPL_OK;
 }
 
-// Run-time values to template arguments: each dispatcher calls a generic lambda with a tag that carries the
-// compile-time form (shpl_batch_norm's style, shpl_bn.hip).
+// Run-time values to template arguments, beside shpl_common.h's by_bools.
 template <typename T_, int VEC_>
 struct Elems {  // the element type and the elements per chunk
     typedef T_ T;
@@ -883,16 +882,6 @@ template <typename F>
 auto by_elems(int dtype, bool v16, F &&fn) {
     if (dtype == SHPL_F32) return v16 ? fn(Elems<float, 4>()) : fn(Elems<float, 1>());
     return v16 ? fn(Elems<uint16_t, 8>()) : fn(Elems<uint16_t, 1>());
-}
-
-// fn(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...) for run-time switches b0, b1, ...
-template <bool... Bs, typename F>
-auto by_bools(F &&fn) {
-    return fn(std::bool_constant<Bs>{}...);
-}
-template <bool... Bs, typename F, typename... R>
-auto by_bools(F &&fn, bool b, R... rest) {
-    return b ? by_bools<Bs..., true>(fn, rest...) : by_bools<Bs..., false>(fn, rest...);
 }
 
 // fn(std::integral_constant<int, V>{}) for the listed V that v equals, the last one when none does

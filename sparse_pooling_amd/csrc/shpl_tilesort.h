@@ -31,17 +31,7 @@ __device__ __forceinline__ void ts_scan(TileSortLds &l) {
         v[q] = l.cnt[threadIdx.x * PER + q];
         sum += v[q];
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int32_t x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) l.wsum[wid] = x;
-    __syncthreads();
-    int32_t run = x - sum;
-    for (int w = 0; w < wid; ++w) run += l.wsum[w];
+    int32_t run = block_excl_scan(sum, l.wsum);
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         l.cnt[threadIdx.x * PER + q] = run;
