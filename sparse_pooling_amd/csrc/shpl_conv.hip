@@ -48,7 +48,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int TH = 8, TW = 32;              // output tile (rows x columns)
+// Output rows per wave: 2 at both dtypes (8 x 32 tiles). Tried for bf16 and not shipped: 4 rows per wave (16 x 32
+// tiles: half the staging round trips, halo rows and weight rows per output pixel, each A operand reused for up
+// to three kernel rows); its timings are not recorded in docs/HISTORY.md or profiles/.
+constexpr int RPW = 2;
+constexpr int TH = 4 * RPW, TW = 32;        // output tile (rows x columns)
 constexpr int HH = TH + 2, HWD = TW + 2;    // halo tile
 constexpr int NCO = 32;                     // output channels per workgroup
 constexpr int CONV_BLOCK = 256;             // 4 waves, wave w: tile rows 2w, 2w+1
@@ -141,50 +145,12 @@ __device__ __forceinline__ void piece_to_lds(const T *row, int c, int c_src, boo
         *reinterpret_cast<u32x4 *>(wave_dst + lane * 16) = load_piece<T>(row, c, c_src, vec);
 }
 
-// blockIdx -> tile, so that each XCD gets one contiguous run of tiles:
-// neighbouring tiles share halo rows through that XCD's L2.
-__device__ __forceinline__ int xcd_tile(int bid, int n) { return (int)xcd_block(bid, n); }
-
-// Pooled vector of one occupied cell for the channels [c0, c0 + CK) of the
-// chunk: sum over the cell's run of CSR entries [e0, e1) of val * img[src],
-// in entry order with separate multiply and add from 0 -- the arithmetic of
-// k_sparse (shpl_pull.hip) -- written to the cell's LDS row. GROUP: a pixel's run of the pixel-keyed CSR with
-// ent_col, summed per column first (RunSum: walk_run<GROUP>'s order).
-template <typename T, bool SWZ, int PSTR, bool GROUP>
-__device__ __forceinline__ void pool_run(const ConvArgs &p, const T *img, int c0, int32_t e0, int32_t e1,
-                                         int32_t src0, float val0, uint8_t *s_base, int pix) {
-    typedef Elem<T> E;
-    constexpr int HE = E::HE;
-    for (int g = 0; g < E::NP; ++g) {  // one 16-byte piece (4 f32 / 8 bf16 channels) at a time
-        RunSum<GROUP, HE> sum;
-        sum.init();
-        for (int32_t i = e0; i < e1; ++i) {
-            const T *row = img + (int64_t)(i == e0 ? src0 : p.ent_src[i]) * p.b_stride;
-            const float wv = i == e0 ? val0 : p.ent_val[i];
-            const int32_t kc = GROUP ? p.ent_col[i] : 0;
-            const u32x4 raw = load_piece<T>(row, c0 + g * HE, p.c_b, p.vec_b);
-            T x[HE];
-            __builtin_memcpy(x, &raw, sizeof(raw));
-            float xf[HE];
-#pragma unroll
-            for (int c = 0; c < HE; ++c) xf[c] = E::f(x[c]);
-            sum.add(kc, wv, xf);
-        }
-        sum.finish();
-        T o[HE];
-#pragma unroll
-        for (int c = 0; c < HE; ++c) o[c] = E::back(sum.acc[c]);
-        __builtin_memcpy(s_base + piece_off<SWZ, PSTR>(pix, g), o, 16);
-    }
-}
-
-// One 16-byte piece (channels [c, c + HE)) of an occupied cell's pooled
-// vector: pool_run's sum for one piece, its entries' loads issued
-// POOL_BATCH at a time (one round trip for runs of up to POOL_BATCH entries)
-// and summed in entry order.
-#ifndef SHPL_POOL_PIECES
-#define SHPL_POOL_PIECES 1
-#endif
+// One 16-byte piece (channels [c, c + HE)) of an occupied cell's pooled vector, written to the cell's LDS
+// row: the sum over the cell's run of CSR entries [e0, e1) of val * img[src], in entry order with separate
+// multiply and add from 0 -- the arithmetic of k_sparse (shpl_pull.hip), so the fused conv is bitwise the conv
+// of the materialised map. The entries' loads are issued POOL_BATCH at a time (one round trip for runs of up to
+// POOL_BATCH entries). GROUP: a pixel's run of the pixel-keyed CSR with ent_col, summed per column first
+// (RunSum: walk_run<GROUP>'s order).
 constexpr int POOL_BATCH = 4;
 template <typename T, bool SWZ, int PSTR, bool GROUP>
 __device__ __forceinline__ void pool_piece(const ConvArgs &p, const T *img, int c, int32_t e0, int32_t e1,
@@ -235,13 +201,12 @@ struct HaloRuns {
     int64_t *scan;                        // [SHPL_BLOCK/64+1]
 };
 
-// Lists the runs of the HHT-row halo of output tile (f, y0, x0): per halo
+// Lists the runs of the halo of output tile (f, y0, x0): per halo
 // row the entry range of cells [x0-1, x0+TW+1) (row pointers + counting the
 // row's sorted entries below each bound), then one block scan in entry
 // order. Every thread of the 256 calls it.
-template <int HHT = HH>
 __device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRuns &r) {
-    constexpr int NPIX = HHT * HWD;
+    constexpr int NPIX = HH * HWD;
     const int tid = threadIdx.x;
     const int H = p.h, W = p.w;
     const int64_t frame_row0 = (int64_t)f * H * W;
@@ -250,25 +215,25 @@ __device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRun
     // 64 at a time against the two cell bounds (ballots), the rows' loads in
     // flight together: two round trips for rows of up to 64 entries.
     const int lane = tid & 63, wave = tid >> 6;
-    constexpr int RPW = (HHT + 3) / 4;  // rows per wave
-    int32_t ra[RPW], rb[RPW], kl[RPW], kh[RPW];
+    constexpr int HRW = (HH + 3) / 4;  // halo rows per wave
+    int32_t ra[HRW], rb[HRW], kl[HRW], kh[HRW];
 #pragma unroll
-    for (int u = 0; u < RPW; ++u) {
+    for (int u = 0; u < HRW; ++u) {
         const int k = wave + 4 * u, y = y0 - 1 + k;
         ra[u] = rb[u] = 0;
         kl[u] = kh[u] = 0;
-        if (k < HHT && y >= 0 && y < H) {
+        if (k < HH && y >= 0 && y < H) {
             ra[u] = p.row_ptr[(int64_t)f * (H + 1) + y];
             rb[u] = p.row_ptr[(int64_t)f * (H + 1) + y + 1];
             kl[u] = (int32_t)(frame_row0 + (int64_t)y * W + (x0 > 0 ? x0 - 1 : 0));
             kh[u] = (int32_t)(frame_row0 + (int64_t)y * W + (x0 + TW + 1 < W ? x0 + TW + 1 : W));
         }
     }
-    int32_t d[RPW];
+    int32_t d[HRW];
 #pragma unroll
-    for (int u = 0; u < RPW; ++u) d[u] = ra[u] + lane < rb[u] ? p.ent_dst[ra[u] + lane] : 0x7fffffff;
+    for (int u = 0; u < HRW; ++u) d[u] = ra[u] + lane < rb[u] ? p.ent_dst[ra[u] + lane] : 0x7fffffff;
 #pragma unroll
-    for (int u = 0; u < RPW; ++u) {
+    for (int u = 0; u < HRW; ++u) {
         const int k = wave + 4 * u;
         int32_t n_lo = __popcll(__ballot(d[u] < kl[u])), n_hi = __popcll(__ballot(d[u] < kh[u]));
         for (int32_t base = ra[u] + 64; base < rb[u] && n_hi == base - ra[u]; base += 64) {  // rows over 64 entries
@@ -276,7 +241,7 @@ __device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRun
             n_lo += __popcll(__ballot(dd < kl[u]));
             n_hi += __popcll(__ballot(dd < kh[u]));
         }
-        if (lane == 0 && k < HHT) {
+        if (lane == 0 && k < HH) {
             r.lo[k] = ra[u] + n_lo;
             r.pre[k + 1] = n_hi - n_lo;
         }
@@ -284,10 +249,10 @@ __device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRun
     __syncthreads();
     if (tid == 0) {
         r.pre[0] = 0;
-        for (int k = 0; k < HHT; ++k) r.pre[k + 1] += r.pre[k];
+        for (int k = 0; k < HH; ++k) r.pre[k + 1] += r.pre[k];
     }
     __syncthreads();
-    const int n_ent = r.pre[HHT];
+    const int n_ent = r.pre[HH];
     int n_run = 0, n_tail = 0;
     for (int base = 0; base < n_ent; base += CONV_BLOCK) {
         const int j = base + tid;
@@ -323,39 +288,62 @@ __device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRun
     return n_run;
 }
 
+// The dense source of input chunk q: A for the chunks [0, qa), B after them -- its rows' first element, their
+// stride, the source's channels, the chunk's first channel in it, and whether every row is 16-byte aligned. PAST
+// (the weight gradient, whose last block of WG_CI input channels may reach past the last chunk): chunks q >= Q
+// hold zeros and are addressed in a source that exists -- A, or B when c_a == 0. Outputs by reference:
+// the form whose code is closest to the four open-coded copies it replaced (docs/HISTORY.md §9).
+template <typename T, bool PAST = false>
+__device__ __forceinline__ void chunk_src(const ConvArgs &p, int q, const T *&src, int64_t &stride, int &c_src, int &c0,
+                                          bool &vec) {
+    const bool from_a = PAST ? p.c_a > 0 && (q < p.qa || q >= p.qa + p.qb) : q < p.qa;
+    src = reinterpret_cast<const T *>(from_a ? p.a : p.b) + (from_a ? p.a_off : p.b_off);
+    stride = from_a ? p.a_stride : p.b_stride;
+    c_src = from_a ? p.c_a : p.c_b;
+    c0 = (from_a ? q : q - p.qa) * Elem<T>::CK;
+    vec = from_a ? p.vec_a : p.vec_b;
+}
+
+// Halo pixel pix (row-major in the HH x HWD halo) of the output tile at (y0, x0) of an H x W map: its halo row
+// and column, its map row and column, and whether those lie inside the map.
+struct HaloPix { int hr, hc, y, x; bool in; };
+__device__ __forceinline__ HaloPix halo_pix(int pix, int y0, int x0, int H, int W) {
+    const int hr = pix / HWD, hc = pix - hr * HWD;
+    const int y = y0 - 1 + hr, x = x0 - 1 + hc;
+    return {hr, hc, y, x, y >= 0 && y < H && x >= 0 && x < W};
+}
+
 // Stages input chunk q (channels of A, then of B) of the 10 x 34 halo of
 // output tile (f, y0, x0) into s_in ([pixel][chunk] rows, piece_off); zero
 // outside the map. Pooled chunks: zeros where no entry lands, each run's sum
 // elsewhere (disjoint cells: no barrier between the two). The caller
 // synchronises after.
-template <typename T, bool POOLED, int PSTR, bool SWZ = false, int HHT = HH, bool GROUP = false>
+template <typename T, bool POOLED, int PSTR, bool SWZ = false, bool GROUP = false>
 __device__ __forceinline__ void stage_halo(const ConvArgs &p, int q, int f, int y0, int x0, uint8_t *s_in,
                                            const HaloRuns &r, int n_run) {
     typedef Elem<T> E;
     constexpr int CK = E::CK, HE = E::HE, NP = E::NP;
-    constexpr int IN_PIECES = HHT * HWD * NP;
+    constexpr int IN_PIECES = HH * HWD * NP;
     constexpr int IN_IT = (IN_PIECES + CONV_BLOCK - 1) / CONV_BLOCK;
     const int tid = threadIdx.x;
     const int H = p.h, W = p.w;
     const int64_t frame_row0 = (int64_t)f * H * W;
-    const bool from_a = q < p.qa;
-    if (from_a || !POOLED) {
-        const T *src = reinterpret_cast<const T *>(from_a ? p.a : p.b) + (from_a ? p.a_off : p.b_off);
-        const int64_t stride = from_a ? p.a_stride : p.b_stride;
-        const int c_src = from_a ? p.c_a : p.c_b;
-        const int c0 = (from_a ? q : q - p.qa) * CK;
-        const bool vec = from_a ? p.vec_a : p.vec_b;
+    if (q < p.qa || !POOLED) {
+        const T *src;
+        int64_t stride;
+        int c_src, c0;
+        bool vec;
+        chunk_src<T>(p, q, src, stride, c_src, c0, vec);
         u32x4 v[IN_IT];
 #pragma unroll
         for (int u = 0; u < IN_IT; ++u) {
             const int j = tid + u * CONV_BLOCK;
             v[u] = u32x4{0u, 0u, 0u, 0u};
             if (j < IN_PIECES) {
-                const int pix = j / NP, hr = pix / HWD, hc = pix - hr * HWD;
-                const int y = y0 - 1 + hr, x = x0 - 1 + hc;
-                if (y >= 0 && y < H && x >= 0 && x < W)
-                    v[u] = load_piece<T>(src + (frame_row0 + (int64_t)y * W + x) * stride, c0 + (j % NP) * HE, c_src,
-                                         vec);
+                const HaloPix h = halo_pix(j / NP, y0, x0, H, W);
+                if (h.in)
+                    v[u] = load_piece<T>(src + (frame_row0 + (int64_t)h.y * W + h.x) * stride, c0 + (j % NP) * HE,
+                                         c_src, vec);
             }
         }
 #pragma unroll
@@ -371,40 +359,24 @@ __device__ __forceinline__ void stage_halo(const ConvArgs &p, int q, int f, int 
                 *reinterpret_cast<u32x4 *>(s_in + piece_off<SWZ, PSTR>(j / NP, j % NP)) = u32x4{0u, 0u, 0u, 0u};
         }
         const T *img = reinterpret_cast<const T *>(p.b) + p.b_off;
-#if SHPL_POOL_PIECES
         // one (run, 16-byte piece) pair per thread, POOL_BATCH entries' loads in flight per round trip
         for (int t = tid; t < n_run * NP; t += CONV_BLOCK)
             pool_piece<T, SWZ, PSTR, GROUP>(p, img, (q - p.qa) * CK + (t % NP) * HE, r.e[t / NP], r.end[t / NP],
                                             r.src[t / NP], r.val[t / NP], s_in, r.pix[t / NP], t % NP);
-#else
-        for (int k = tid; k < n_run; k += CONV_BLOCK)
-            pool_run<T, SWZ, PSTR, GROUP>(p, img, (q - p.qa) * CK, r.e[k], r.end[k], r.src[k], r.val[k], s_in, r.pix[k]);
-#endif
     }
 }
 
-#define SHPL_HALO_RUNS_LDS(POOLED, HHT)                                                                       \
-    __shared__ int32_t s_lo[HHT], s_pre[HHT + 1];                                                            \
-    __shared__ int32_t s_run_pix[POOLED ? HHT * HWD : 1], s_run_e[POOLED ? HHT * HWD : 1],                   \
-        s_run_end[POOLED ? HHT * HWD : 1], s_run_src[POOLED ? HHT * HWD : 1];                               \
-    __shared__ float s_run_val[POOLED ? HHT * HWD : 1];                                                      \
-    __shared__ uint8_t s_occ[POOLED ? HHT * HWD : 1];                                                        \
-    __shared__ int64_t s_scan[SHPL_BLOCK / 64 + 1];                                                          \
-    const HaloRuns runs{s_lo, s_pre, s_run_pix, s_run_e, s_run_end, s_run_src, s_run_val, s_occ, s_scan};
-
-// Forward tile shape: output rows per wave, 2 at f32 (8 x 32 tiles) and 4 at
-// bf16 (16 x 32 tiles). A bf16 chunk's MFMAs are 16x faster than an f32
-// chunk's: the taller tile halves the staging round trips, halo rows and
-// weight rows per output pixel, and each wave reuses every A operand it reads
-// for up to three kernel rows (0.75 KB of LDS reads per MFMA instead of 1.5).
-#ifndef SHPL_BF16_RPW
-#define SHPL_BF16_RPW 2
-#endif
-template <typename T>
-struct ConvTile {
-    static constexpr int RPW = sizeof(T) == 2 ? SHPL_BF16_RPW : 2;
-    static constexpr int TH = 4 * RPW, HH = TH + 2;
-};
+// The workgroup's HaloRuns (one element per array when the kernel is not POOLED: it never reads them).
+template <bool POOLED>
+__device__ __forceinline__ HaloRuns halo_runs_lds() {
+    constexpr int N = POOLED ? HH * HWD : 1;
+    __shared__ int32_t s_lo[HH], s_pre[HH + 1];
+    __shared__ int32_t s_run_pix[N], s_run_e[N], s_run_end[N], s_run_src[N];
+    __shared__ float s_run_val[N];
+    __shared__ uint8_t s_occ[N];
+    __shared__ int64_t s_scan[SHPL_BLOCK / 64 + 1];
+    return {s_lo, s_pre, s_run_pix, s_run_e, s_run_end, s_run_src, s_run_val, s_occ, s_scan};
+}
 
 // Stages input chunk q of output tile (f, y0, x0) -- its 9x32 weight rows
 // and its HH x 34 halo -- into one LDS buffer pair (swizzled 32-byte rows).
@@ -416,8 +388,8 @@ __device__ __forceinline__ void conv_stage(const ConvArgs &p, int q, int f, int 
                                            int64_t wq_cb, uint8_t *s_in, uint8_t *s_w, const HaloRuns &runs,
                                            int n_run) {
     typedef Elem<T> E;
-    constexpr int CK = E::CK, HE = E::HE, NP = E::NP, HHT = ConvTile<T>::HH;
-    constexpr int IN_PIECES = HHT * HWD * NP, W_PIECES = W_ROWS * NP;
+    constexpr int CK = E::CK, HE = E::HE, NP = E::NP;
+    constexpr int IN_PIECES = HH * HWD * NP, W_PIECES = W_ROWS * NP;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {  // the weight rows of each output block, W_PIECES slots apart
@@ -433,27 +405,32 @@ __device__ __forceinline__ void conv_stage(const ConvArgs &p, int q, int f, int 
     if (!POOLED || q < p.qa) {
         const int H = p.h, W = p.w;
         const int64_t frame_row0 = (int64_t)f * H * W;
-        const bool from_a = q < p.qa;
-        const T *src = reinterpret_cast<const T *>(from_a ? p.a : p.b) + (from_a ? p.a_off : p.b_off);
-        const int64_t stride = from_a ? p.a_stride : p.b_stride;
-        const int c_src = from_a ? p.c_a : p.c_b;
-        const int c0 = (from_a ? q : q - p.qa) * CK;
-        const bool vec = from_a ? p.vec_a : p.vec_b;
+        const T *src;
+        int64_t stride;
+        int c_src, c0;
+        bool vec;
+        chunk_src<T>(p, q, src, stride, c_src, c0, vec);
 #pragma unroll
         for (int u = 0; u < (IN_PIECES + CONV_BLOCK - 1) / CONV_BLOCK; ++u) {
             const int base = u * CONV_BLOCK + wave * 64;
             if (base >= IN_PIECES) break;
             const int k = base + lane, pix = k >> 1, g = (k & 1) ^ ((pix >> 3) & 1);
-            const int hr = pix / HWD, hc = pix - hr * HWD;
-            const int y = y0 - 1 + hr, x = x0 - 1 + hc;
-            const bool ok = y >= 0 && y < H && x >= 0 && x < W;
+            const HaloPix h = halo_pix(pix, y0, x0, H, W);
             if (k < IN_PIECES)
-                piece_to_lds<T>(ok ? src + (frame_row0 + (int64_t)y * W + x) * stride : nullptr, c0 + g * HE, c_src, vec,
-                                s_in + base * 16, lane);
+                piece_to_lds<T>(h.in ? src + (frame_row0 + (int64_t)h.y * W + h.x) * stride : nullptr, c0 + g * HE,
+                                c_src, vec, s_in + base * 16, lane);
         }
     } else {
-        stage_halo<T, true, E::CB, true, HHT, GROUP>(p, q, f, y0, x0, s_in, runs, n_run);
+        stage_halo<T, true, E::CB, true, GROUP>(p, q, f, y0, x0, s_in, runs, n_run);
     }
+}
+
+// Where channel c of output pixel `row` is stored: in out, or -- the input gradient's second map -- in out2 as
+// channel c - c_split.
+template <typename T>
+__device__ __forceinline__ T *out_ptr(const ConvArgs &p, int64_t row, int c) {
+    return p.out2 && c >= p.c_split ? reinterpret_cast<T *>(p.out2) + row * p.out2_stride + (c - p.c_split)
+                                    : reinterpret_cast<T *>(p.out) + row * p.out_stride + c;
 }
 
 // NCB: output-channel blocks per workgroup (blockIdx.y covers NCB of them):
@@ -463,10 +440,10 @@ __device__ __forceinline__ void conv_stage(const ConvArgs &p, int q, int f, int 
 template <typename T, bool POOLED, bool STATS, int NCB = 1, bool GROUP = false>
 __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const ConvArgs p) {
     typedef Elem<T> E;
-    constexpr int CK = E::CK, NP = E::NP, RPW = ConvTile<T>::RPW, HHT = ConvTile<T>::HH;
+    constexpr int CK = E::CK, NP = E::NP;
     static_assert(NCB == 1 || !STATS, "statistics: one output block per workgroup");
     static_assert(NP == 2, "two 16-byte pieces per LDS row (the swizzle)");
-    constexpr int IN_BYTES = HHT * HWD * NP * 16, W_BYTES = W_ROWS * NP * 16 * NCB;
+    constexpr int IN_BYTES = HH * HWD * NP * 16, W_BYTES = W_ROWS * NP * 16 * NCB;
     // the output rows' transpose (epilogue) reuses the chunk buffers: 4 waves x 32 pixels x OPITCH
     constexpr int OPITCH = NCO * (int)sizeof(T) + 16;
     static_assert(4 * 32 * OPITCH <= IN_BYTES + W_BYTES, "epilogue rows fit the chunk buffers");
@@ -474,16 +451,17 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
     uint8_t *const s_in = s_buf, *const s_w = s_buf + IN_BYTES;
     __shared__ float s_red[4][2][NCO];
     __shared__ __attribute__((aligned(16))) float s_par[NCB][2][NCO];  // scale, shift - center * scale of the block's channels
-    SHPL_HALO_RUNS_LDS(POOLED, HHT)
+    const HaloRuns runs = halo_runs_lds<POOLED>();
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int pl = lane & 31, hf = lane >> 5;
-    const int tile = xcd_tile(blockIdx.x, p.n_tiles);
+    // each XCD gets one contiguous run of tiles: neighbouring tiles share halo rows through that XCD's L2
+    const int tile = (int)xcd_block((int)blockIdx.x, p.n_tiles);
     const int cob0 = blockIdx.y * NCB;
     const int f = tile / p.tiles_per_frame;
     const int t_in = tile - f * p.tiles_per_frame;
     const int ty = t_in / p.tiles_x, tx = t_in - ty * p.tiles_x;
-    const int y0 = ty * ConvTile<T>::TH, x0 = tx * TW;
+    const int y0 = ty * TH, x0 = tx * TW;
     const int H = p.h, W = p.w;
     const int64_t frame_row0 = (int64_t)f * H * W;
     const int Q = p.qa + p.qb;
@@ -499,7 +477,7 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
         s_par[cb][0][tid & 31] = sc;
         s_par[cb][1][tid & 31] = __fsub_rn(sh, __fmul_rn(ce, sc));
     }
-    const int n_run = POOLED ? find_runs<HHT>(p, f, y0, x0, runs) : 0;  // (s_par: published by the next barrier)
+    const int n_run = POOLED ? find_runs(p, f, y0, x0, runs) : 0;  // (s_par: published by the next barrier)
 
     f32x16 acc[NCB][RPW];
 #pragma unroll
@@ -621,10 +599,7 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         if (c + j >= p.c_out) break;
-                        T *d = p.out2 && c + j >= p.c_split
-                                   ? reinterpret_cast<T *>(p.out2) + row * p.out2_stride + (c + j - p.c_split)
-                                   : reinterpret_cast<T *>(p.out) + row * p.out_stride + c + j;
-                        *d = o[j];
+                        *out_ptr<T>(p, row, c + j) = o[j];
                     }
                 }
             }
@@ -636,11 +611,7 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
                     const u32x4 v = *reinterpret_cast<const u32x4 *>(s_o + px * OPITCH + pi * 16);
                     if (y < H && x0 + px < W) {
                         const int64_t row = frame_row0 + (int64_t)y * W + x0 + px;
-                        const int c = cob * NCO + pi * HE;
-                        T *d = p.out2 && c >= p.c_split
-                                   ? reinterpret_cast<T *>(p.out2) + row * p.out2_stride + (c - p.c_split)
-                                   : reinterpret_cast<T *>(p.out) + row * p.out_stride + c;
-                        *reinterpret_cast<u32x4 *>(d) = v;
+                        *reinterpret_cast<u32x4 *>(out_ptr<T>(p, row, cob * NCO + pi * HE)) = v;
                     }
                 }
             }
@@ -809,22 +780,19 @@ __device__ __forceinline__ void wg_stage(const ConvArgs &p, const WgArgs &g, int
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int q = cib * NQ + j;
-            // chunks past the last (q >= Q) are zeros, addressed in a source that exists
-            const bool from_a = p.c_a > 0 && (q < p.qa || q >= Q);
-            const T *src = reinterpret_cast<const T *>(from_a ? p.a : p.b) + (from_a ? p.a_off : p.b_off);
-            const int64_t stride = from_a ? p.a_stride : p.b_stride;
-            const int c_src = from_a ? p.c_a : p.c_b;
-            const int c0 = (from_a ? q : q - p.qa) * CK;
-            const bool vec = from_a ? p.vec_a : p.vec_b;
+            const T *src;
+            int64_t stride;
+            int c_src, c0;
+            bool vec;
+            chunk_src<T, true>(p, q, src, stride, c_src, c0, vec);
 #pragma unroll
             for (int u = 0; u < (IN_PIECES + CONV_BLOCK - 1) / CONV_BLOCK; ++u) {
                 const int base = u * CONV_BLOCK + wave * 64;  // the wave's first piece
                 if (base >= IN_PIECES) break;
                 const int jj = base + lane;
-                const int pix = jj / NP, hr = pix / HWD, hc = pix - hr * HWD;
-                const int y = y0 - 1 + hr, xx = x0 - 1 + hc;
-                const bool ok = q < Q && jj < IN_PIECES && y >= 0 && y < H && xx >= 0 && xx < W;
-                const int64_t row = frame_row0 + (int64_t)y * W + xx;
+                const HaloPix h = halo_pix(jj / NP, y0, x0, H, W);
+                const bool ok = q < Q && jj < IN_PIECES && h.in;
+                const int64_t row = frame_row0 + (int64_t)h.y * W + h.x;
                 const int c = c0 + (jj % NP) * HE;
                 uint8_t *dst = s_x + j * NPIX * CB + base * 16;
                 if (jj < IN_PIECES) {
@@ -864,7 +832,7 @@ __global__ __launch_bounds__(CONV_BLOCK, POOLED ? 1 : 2) void k_conv3x3_wgrad(co
     constexpr int NPIX = HH * HWD;
     __shared__ __attribute__((aligned(16))) uint8_t s_x[NQ * NPIX * CB];
     __shared__ __attribute__((aligned(16))) uint8_t s_g[TH * TW * NCO * sizeof(T)];
-    SHPL_HALO_RUNS_LDS(POOLED, HH)
+    const HaloRuns runs = halo_runs_lds<POOLED>();
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, kq = lane >> 4;
     const int grp = blockIdx.x, cib = blockIdx.y, cob = blockIdx.z;
@@ -893,7 +861,7 @@ __global__ __launch_bounds__(CONV_BLOCK, POOLED ? 1 : 2) void k_conv3x3_wgrad(co
             for (int j = 0; j < NQ; ++j) {
                 const int q = cib * NQ + j;
                 if (q < Q)
-                    stage_halo<T, POOLED, CB, false, HH, GROUP>(p, q, f, y0, x0, s_x + j * NPIX * CB, runs, n_run);
+                    stage_halo<T, POOLED, CB, false, GROUP>(p, q, f, y0, x0, s_x + j * NPIX * CB, runs, n_run);
             }
         }
         wg_stage<T, !POOLED>(p, g, f, y0, x0, cib, cob, s_x, s_g);
@@ -1016,20 +984,20 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_wgrad_bf16(const ConvArgs p, 
             const int j = tid + u * CONV_BLOCK;
             const int q = cib * NQ + j / (HH * HWD * 2);
             const int rem = j % (HH * HWD * 2), pix = rem >> 1, pc = rem & 1;
-            const int hr = pix / HWD, hc = pix - hr * HWD;
-            const int y = y0 - 1 + hr, x = x0 - 1 + hc;
-            const bool ok = j < IN_PIECES && q < Q && y >= 0 && y < H && x >= 0 && x < W;
-            const bool from_a = p.c_a > 0 && (q < p.qa || q >= Q);
-            const uint16_t *src = reinterpret_cast<const uint16_t *>(from_a ? p.a : p.b) + (from_a ? p.a_off : p.b_off);
-            const int64_t row = ok ? frame_row0 + (int64_t)y * W + x : frame_row0;
-            const int c = ok ? (from_a ? q : q - p.qa) * CK + pc * HE : 0;
+            const HaloPix hp = halo_pix(pix, y0, x0, H, W);
+            const bool ok = j < IN_PIECES && q < Q && hp.in;
+            const uint16_t *src;
+            int64_t stride;
+            int c_src, c0;
+            bool vec;
+            chunk_src<uint16_t, true>(p, q, src, stride, c_src, c0, vec);
+            const int64_t row = ok ? frame_row0 + (int64_t)hp.y * W + hp.x : frame_row0;
+            const int c = ok ? c0 + pc * HE : 0;
             if (g.whole) {  // unmasked, branch-free: out-of-map pieces read row 0 and are zeroed
-                const u32x4 v = *reinterpret_cast<const u32x4 *>(src + row * (from_a ? p.a_stride : p.b_stride) + c);
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(src + row * stride + c);
                 xv[u] = ok ? v : z;
             } else {
-                xv[u] = ok ? load_piece<uint16_t>(src + row * (from_a ? p.a_stride : p.b_stride), c,
-                                                  from_a ? p.c_a : p.c_b, from_a ? p.vec_a : p.vec_b)
-                           : z;
+                xv[u] = ok ? load_piece<uint16_t>(src + row * stride, c, c_src, vec) : z;
             }
         }
 #pragma unroll
@@ -1148,17 +1116,17 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_wgrad_reduce(const float *part, 
     }
 }
 
-#ifndef SHPL_CONV_ROWS
-#define SHPL_CONV_ROWS 1  // 0: the tiled kernel for every forward (A/B builds)
-#endif
-#ifndef SHPL_CONV_WIDE
-#define SHPL_CONV_WIDE 1  // 0: wide bf16 convs on the tiled kernel (A/B builds)
-#endif
-#ifndef SHPL_ROWS_BAND
-#define SHPL_ROWS_BAND 0  // 0: about 60 rows, equal bands (k_conv_rows stages band + 2 rows, at most 64)
-#endif
-
 // ---------------------------------------------------------------- host: plans
+// A dtype code to its element type, beside shpl_common.h's by_bools: fn(TypeOf<float>()) for SHPL_F32,
+// fn(TypeOf<uint16_t>()) for SHPL_BF16 (conv_plan has rejected every other code by then).
+template <typename F>
+auto by_dtype(int dtype, F &&fn) {
+    return dtype == SHPL_F32 ? fn(TypeOf<float>()) : fn(TypeOf<uint16_t>());
+}
+
+// Channels per 16-byte piece of a dtype (Elem<T>::HE).
+int piece_elems(int dtype) { return by_dtype(dtype, [](auto t) { return Elem<typename decltype(t)::T>::HE; }); }
+
 // One source of the conv: rows of `stride` elements, of which the channels [off, off + c) are read.
 struct Src { const void *p; int64_t stride, off, c; };
 
@@ -1193,20 +1161,15 @@ Pooled pooled_in(const void *ws, const PooledAt &at) {
 }
 
 // How the row kernels (k_conv_rows, k_wgrad_rows) cut an h x w map: strips of TW columns, wpr occupancy
-// words per row, n_bands equal bands of about 60 rows -- or bands of `band` rows (the forward's
-// SHPL_ROWS_BAND; the kernels stage band + 2 rows, at most 64).
+// words per row, n_bands equal bands of about 60 rows (the kernels stage band + 2 rows, at most 64).
 struct RowGeom { int strips, wpr, n_bands, band; };
 
-RowGeom row_geom(int64_t h, int64_t w, int band = 0) {
+RowGeom row_geom(int64_t h, int64_t w) {
     RowGeom g;
     g.strips = (int)((w + TW - 1) / TW);
     g.wpr = (int)((w + 31) / 32);
     g.n_bands = (int)((h + 59) / 60);
     g.band = (int)((h + g.n_bands - 1) / g.n_bands);
-    if (band > 0 && band <= 62) {
-        g.band = band;
-        g.n_bands = (int)((h + band - 1) / band);
-    }
     return g;
 }
 
@@ -1228,42 +1191,39 @@ struct ConvPlan {
     int64_t pool_cap;
 };
 
-// th: output tile rows -- the forward's ConvTile (8 f32, 16 bf16) unless the
-// weight gradient asks for its own 8. pool_cap: the pooling CSR's entry
-// capacity (pooled forward: sizes the compact buffer of pooled runs).
+// The tiles are TH x TW output pixels at both dtypes, for the forward and the weight gradient alike. pool_cap:
+// the pooling CSR's entry capacity (pooled forward: sizes the compact buffer of pooled runs).
 int conv_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b, int64_t c_out, bool pooled,
-              bool stats, ConvPlan *pl, int th = 0, int64_t pool_cap = 0) {
+              bool stats, ConvPlan *pl, int64_t pool_cap = 0) {
     if (dtype != SHPL_F32 && dtype != SHPL_BF16) return SHPL_ERR_ARG;
     if (n_frames < 0 || h < 0 || w < 0 || c_a < 0 || c_b < 0 || c_out < 1 || c_a + c_b < 1) return SHPL_ERR_BAD_SHAPE;
     if (h > (1 << 20) || w > (1 << 20) || c_a + c_b > (1 << 16) || c_out > (1 << 16)) return SHPL_ERR_BAD_SHAPE;
     if (pool_cap < 0 || pool_cap >= (1LL << 31)) return SHPL_ERR_BAD_SHAPE;
-    const int esz = dtype == SHPL_F32 ? 4 : 2;
-    const int chunk_b = 32;  // Elem<T>::CB
-    pl->ck = chunk_b / esz;
+    const int chunk_b = Elem<float>::CB;  // the same at both dtypes
+    pl->ck = by_dtype(dtype, [](auto t) { return Elem<typename decltype(t)::T>::CK; });
     pl->qa = (int)((c_a + pl->ck - 1) / pl->ck);
     pl->qb = (int)((c_b + pl->ck - 1) / pl->ck);
     pl->n_cob = (int)((c_out + NCO - 1) / NCO);
     pl->tiles_x = (int)((w + TW - 1) / TW);
-    if (th == 0) th = dtype == SHPL_F32 ? ConvTile<float>::TH : ConvTile<uint16_t>::TH;
-    pl->tiles_y = (int)((h + th - 1) / th);
+    pl->tiles_y = (int)((h + TH - 1) / TH);
     pl->tiles_per_frame = pl->tiles_x * pl->tiles_y;
     pl->n_tiles = (int64_t)n_frames * pl->tiles_per_frame;
     if (pl->n_tiles >= (1LL << 31) || (int64_t)n_frames * h * w >= (1LL << 31)) return SHPL_ERR_BAD_SHAPE;
-    pl->g = row_geom(h, w, SHPL_ROWS_BAND);
+    pl->g = row_geom(h, w);
     const int64_t n_items = (int64_t)n_frames * pl->g.n_bands * pl->g.strips;
     // the occupancy table and the compact pooled rows hold this map
     const bool occ_fits = h * pl->g.wpr <= rows::OCC_MAX_WORDS && pool_cap * c_b * 2 < (1LL << 31);
-    pl->rows = SHPL_CONV_ROWS && dtype == SHPL_BF16 && pl->qa + pl->qb <= 4 && c_a % 8 == 0 && c_b % 8 == 0 && h > 0 &&
+    pl->rows = dtype == SHPL_BF16 && pl->qa + pl->qb <= 4 && c_a % 8 == 0 && c_b % 8 == 0 && h > 0 &&
                w > 0 && rows::supported(pl->qa + pl->qb, pl->qa) && (!pooled || occ_fits) && n_items < (1LL << 31);
-    pl->wide = SHPL_CONV_WIDE && dtype == SHPL_BF16 && !stats && !pl->rows && h > 0 && w > 0 &&
+    pl->wide = dtype == SHPL_BF16 && !stats && !pl->rows && h > 0 && w > 0 &&
                wide::supported(c_a, c_b, c_out) && (int64_t)n_frames * h * w * (c_b > 0 ? c_b : 1) < (1LL << 40);
     pl->wide_cmp = pl->wide && pooled && occ_fits;
     pl->pool_cap = pool_cap;
     size_t wp_bytes = (size_t)pl->n_cob * (pl->qa + pl->qb) * W_ROWS * chunk_b;
     if (pl->wide && wide::packed_bytes(c_a, c_b, c_out) > wp_bytes) wp_bytes = wide::packed_bytes(c_a, c_b, c_out);
-    // statistics partials: one per tile (tiled kernel) or per item (k_conv_rows, SHPL_ROWS_BAND may cut more
-    // bands than there are tile rows)
-    const int64_t n_part = !stats ? 0 : pl->rows && n_items > pl->n_tiles ? n_items : pl->n_tiles;
+    // statistics partials: one per tile (tiled kernel) or per item (k_conv_rows); a band is several tile rows
+    // (ceil(h / 60) <= ceil(h / TH)) over the same strips, so the items never outnumber the tiles
+    const int64_t n_part = stats ? pl->n_tiles : 0;
     Layout l;
     pl->wp = l.take(wp_bytes);
     pl->row_ptr = l.take(pooled ? (size_t)n_frames * (h + 1) * 4 : 0);
@@ -1278,7 +1238,7 @@ int conv_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_
 // The fields of ConvArgs every form fills: frame and tile geometry, the sources, the pool's arrays; the rest 0.
 ConvArgs conv_args(int dtype, int n_frames, int64_t h, int64_t w, const ConvPlan &pl, const Src &A, const Src &B,
                    const shpl_csr *pool) {
-    const int he = dtype == SHPL_F32 ? 4 : 8;
+    const int he = piece_elems(dtype);
     ConvArgs a = {};
     a.n_frames = n_frames;
     a.h = (int)h;
@@ -1468,11 +1428,15 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, void *ws, bool pooled, bool sta
     // memory-pipeline-bound kernel) and keeps one.
     const bool pair = sizeof(T) == 4 && !pooled && !stats && pl.n_cob % 2 == 0;
     const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
-    const auto kernel = group   ? (stats ? k_conv3x3<T, true, true, 1, true> : k_conv3x3<T, true, false, 1, true>)
-                        : pooled ? (stats ? k_conv3x3<T, true, true> : k_conv3x3<T, true, false>)
-                        : stats ? k_conv3x3<T, false, true>
-                        : pair  ? k_conv3x3<T, false, false, 2>
-                                : k_conv3x3<T, false, false>;
+    using Kernel = void (*)(const ConvArgs);
+    const Kernel kernel = by_bools(
+        [](auto po, auto st, auto gr, auto pr) -> Kernel {
+            if constexpr ((gr() && !po()) || (pr() && (po() || st() || sizeof(T) != 4)))
+                return nullptr;  // no such form: the switches above never say so
+            else
+                return k_conv3x3<T, po(), st(), pr() ? 2 : 1, gr()>;
+        },
+        pooled, stats, group, pair);
     hipLaunchKernelGGL(kernel, pair ? dim3(grid.x, grid.y / 2) : grid, dim3(CONV_BLOCK), 0, s, a);
     SHPL_LAUNCH_CHECK();
     if (stats) {
@@ -1490,7 +1454,7 @@ int forward_setup(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, c
                   void *d_ws, size_t ws_bytes, bool check_ws, ConvPlan &pl, ConvArgs &a, bool *empty) {
     const bool pooled = pool != nullptr;
     *empty = false;
-    int rc = conv_plan(dtype, n_frames, h, w, A.c, B.c, c_out, pooled, stats, &pl, 0, pooled ? pool->nnz_cap : 0);
+    int rc = conv_plan(dtype, n_frames, h, w, A.c, B.c, c_out, pooled, stats, &pl, pooled ? pool->nnz_cap : 0);
     if (rc) return rc;
     if (act != 0 && act != 1) return SHPL_ERR_ARG;
     if (!d_weights || (check_ws && ws_bytes > 0 && !d_ws)) return SHPL_ERR_ARG;
@@ -1513,7 +1477,7 @@ int forward_setup(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, c
     a.out = d_out;
     a.out_stride = out_stride;
     a.c_out = (int)c_out;
-    a.vec_out = vec16({d_out, out_stride, 0, c_out}, dtype == SHPL_F32 ? 4 : 8);
+    a.vec_out = vec16({d_out, out_stride, 0, c_out}, piece_elems(dtype));
     return SHPL_OK;
 }
 
@@ -1524,7 +1488,7 @@ int forward_setup(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, c
 int forward_pooled(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b, int64_t c_out,
                    int64_t pool_cap, int fwd_stats, const void *d_fwd_ws, size_t fwd_ws_bytes, Pooled *po) {
     ConvPlan fp;
-    const int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, true, fwd_stats != 0, &fp, 0, pool_cap);
+    const int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, true, fwd_stats != 0, &fp, pool_cap);
     if (rc) return rc;
     if (!fp.rows || fwd_ws_bytes < fp.total || c_out % NCO != 0 ||
         (fwd_stats != 0 && !rows::supported_st(fp.qa + fp.qb, fp.qa, true)))
@@ -1548,7 +1512,7 @@ int dgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, 
         return SHPL_ERR_BAD_SHAPE;
     if (pl.n_tiles == 0) return SHPL_OK;
     if (!d_gy || (c_split > 0 && !d_dx)) return SHPL_ERR_ARG;
-    const int he = dtype == SHPL_F32 ? 4 : 8;
+    const int he = piece_elems(dtype);
     ConvArgs a = conv_args(dtype, n_frames, h, w, pl, {d_gy, gy_stride, 0, c_gy}, {}, nullptr);
     a.wp = region<void>(d_ws, pl.wp);
     a.out = d_dx;
@@ -1561,8 +1525,9 @@ int dgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, 
                 (!d_dx_b || (aligned16(d_dx_b) && dx_b_stride % he == 0 && c_split % he == 0));
     a.occ2 = d_dx_b ? occ2 : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SHPL_F32) return conv_launch<float>(pl, a, d_ws, false, false, d_weights, nullptr, nullptr, s, 1);
-    return conv_launch<uint16_t>(pl, a, d_ws, false, false, d_weights, nullptr, nullptr, s, 1);
+    return by_dtype(dtype, [&](auto t) {
+        return conv_launch<typename decltype(t)::T>(pl, a, d_ws, false, false, d_weights, nullptr, nullptr, s, 1);
+    });
 }
 
 // ---------------------------------------------------------------- host: weight gradient
@@ -1582,7 +1547,7 @@ struct WgPlan {
 
 int wgrad_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b, int64_t c_out, bool pooled,
                WgPlan *wp, int64_t pool_cap = 0) {
-    int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, false, &wp->cp, TH);
+    int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, false, &wp->cp);
     if (rc) return rc;
     const int Q = wp->cp.qa + wp->cp.qb;
     wp->n_cib = (Q * wp->cp.ck + WG_CI - 1) / WG_CI;
@@ -1602,7 +1567,7 @@ int wgrad_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64
     wp->g = row_geom(h, w);
     const int64_t n_items = (int64_t)n_frames * wp->g.n_bands * wp->g.strips;
     // pooled: B gathered from the compact pooled rows of prep_pooled (the forward's k_occ_frame + k_pool_runs)
-    wp->rows = SHPL_CONV_ROWS && dtype == SHPL_BF16 && h > 0 && w > 0 && n_items > 0 && n_items < (1LL << 31) &&
+    wp->rows = dtype == SHPL_BF16 && h > 0 && w > 0 && n_items > 0 && n_items < (1LL << 31) &&
                rows::wgrad_supported((int)c_a, (int)c_b, (int)c_out) &&
                (!pooled || (c_a > 0 && c_b <= 64 && h * wp->g.wpr <= rows::OCC_MAX_WORDS && pool_cap >= 0 &&
                             pool_cap * c_b * 2 < (1LL << 31)));
@@ -1634,7 +1599,7 @@ int wgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, cons
     if (rc) return rc;
     if ((A.c > 0 && !A.p) || !d_gy) return SHPL_ERR_ARG;
     const ConvPlan &pl = wp.cp;
-    const int he = dtype == SHPL_F32 ? 4 : 8;
+    const int he = piece_elems(dtype);
     const bool vec_g = vec16({d_gy, gy_stride, 0, c_out}, he);
     hipStream_t s = (hipStream_t)stream;
     if (pl.n_tiles == 0) {  // no pixels: dW = 0
@@ -1708,12 +1673,20 @@ int wgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, cons
     }
     const dim3 grid((unsigned)wp.n_groups, (unsigned)wp.n_cib, (unsigned)pl.n_cob);
     const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
-    const auto kernel = dtype == SHPL_F32 ? (group    ? k_conv3x3_wgrad<float, true, true>
-                                             : pooled ? k_conv3x3_wgrad<float, true>
-                                                      : k_conv3x3_wgrad<float, false>)
-                        : group           ? k_conv3x3_wgrad<uint16_t, true, true>
-                        : pooled          ? k_conv3x3_wgrad<uint16_t, true>
-                                          : k_wgrad_bf16;
+    using Kernel = void (*)(const ConvArgs, const WgArgs);
+    const Kernel kernel = by_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::T T;
+        return by_bools(
+            [](auto po, auto gr) -> Kernel {
+                if constexpr (gr() && !po())
+                    return nullptr;  // no such form
+                else if constexpr (sizeof(T) == 2 && !po())
+                    return k_wgrad_bf16;  // dense bf16 sources: the bf16 MFMA kernel
+                else
+                    return k_conv3x3_wgrad<T, po(), gr()>;
+            },
+            pooled, group);
+    });
     hipLaunchKernelGGL(kernel, grid, dim3(CONV_BLOCK), 0, s, a, g);
     SHPL_LAUNCH_CHECK();
     const int64_t n_out = 9 * (A.c + B.c) * c_out;
@@ -1734,7 +1707,7 @@ extern "C" int shpl_conv3x3_workspace_bytes(int dtype, int n_frames, int64_t h, 
     if (!bytes) return SHPL_ERR_ARG;
     ConvPlan pl;
     const bool pooled = pool_nnz_cap >= 0;
-    const int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, stats != 0, &pl, 0,
+    const int rc = conv_plan(dtype, n_frames, h, w, c_a, c_b, c_out, pooled, stats != 0, &pl,
                              pooled ? pool_nnz_cap : 0);
     if (rc) return rc;
     *bytes = pl.total;
@@ -1756,8 +1729,10 @@ extern "C" int shpl_conv3x3(int dtype, int n_frames, int64_t h, int64_t w, const
                                  stats, d_ws, ws_bytes, true, pl, a, &empty);
     if (rc || empty) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SHPL_F32) return conv_launch<float>(pl, a, d_ws, pooled, stats, d_weights, d_frame_off, d_stats, s);
-    return conv_launch<uint16_t>(pl, a, d_ws, pooled, stats, d_weights, d_frame_off, d_stats, s, 0, pool);
+    return by_dtype(dtype, [&](auto t) {
+        return conv_launch<typename decltype(t)::T>(pl, a, d_ws, pooled, stats, d_weights, d_frame_off, d_stats, s, 0,
+                                                    pool);
+    });
 }
 
 extern "C" int shpl_conv3x3_rows_form(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a,

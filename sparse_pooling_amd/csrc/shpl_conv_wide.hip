@@ -33,11 +33,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef SHPL_WIDE_PROBE
-// timing probes (wrong results): 1 no staging in the K loop, 3 no MFMAs
-#define SHPL_WIDE_PROBE 0
-#endif
-
 constexpr int TH = 16, TW = 16;                        // output tile
 constexpr int HH = TH + 2, HW = TW + 2, HPIX = HH * HW;  // 18 x 18 halo
 constexpr int WAVES = 8, BLOCK = 64 * WAVES;
@@ -65,12 +60,6 @@ __device__ u32x4 g_wide_zero;  // the LDS-DMA source of pieces outside the map
 __device__ __forceinline__ void dma(const void *src, uint8_t *dst) {
     const uint32_t lds = (uint32_t)(uintptr_t)dst;
     asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(lds) : "memory");
-}
-__device__ __forceinline__ void dma_halo(const void *src, uint8_t *dst) { dma(src, dst); }
-
-__device__ __forceinline__ int64_t xcd_tile(int64_t bid, int64_t n) {
-    const int64_t q = n >> 3, r = n & 7, xcd = bid & 7, i = bid >> 3;
-    return xcd < r ? xcd * (q + 1) + i : r * (q + 1) + (xcd - r) * q + i;
 }
 
 // Packed weights, HWIO [3][3][c_a+c_b][c_out] bf16 -> [nb][chunk q][tap t][co 256][64 channels], piece c of
@@ -101,7 +90,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_conv_wide(const WideArgs p) {
     const int nb = blockIdx.y;
     const int H = p.h, W = p.w;
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int64_t tile = xcd_tile(blockIdx.x, gridDim.x);
+    const int64_t tile = xcd_block(blockIdx.x, gridDim.x);
     const int f = (int)(tile / ((int64_t)tiles_x * tiles_y));
     const int tr = (int)(tile - (int64_t)f * tiles_x * tiles_y);
     const int ty0 = (tr / tiles_x) * TH, tx0 = (tr % tiles_x) * TW;
@@ -165,7 +154,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_conv_wide(const WideArgs p) {
     // prologue: chunk 0's halo (and, LDS-DMA form, step 0's weights)
 #pragma unroll
     for (int j = 0; j < HW_PER_WAVE; ++j)
-        if (WAVES * j + wave < HALO_DMAS) dma_halo(halo_src(0, j), hbuf0 + (WAVES * j + wave) * 1024);
+        if (WAVES * j + wave < HALO_DMAS) dma(halo_src(0, j), hbuf0 + (WAVES * j + wave) * 1024);
 
     f32x4 acc[MI][NJ];
 #pragma unroll
@@ -214,18 +203,12 @@ __global__ __launch_bounds__(BLOCK, 2) void k_conv_wide(const WideArgs p) {
             for (int i = 0; i < MI; ++i) {
                 // the next step's DMAs among the MFMA groups: the weights first, then the halo
                 const int g = ks * MI + i;
-                if (SHPL_WIDE_PROBE != 1) {
-                    if (g < WD_PER_WAVE) issue_w(s_next, g);
-                    if (g == WD_PER_WAVE)
-                        dma_halo(halo_src(q_next, jh), hbuf0 + (q_next & 1) * HALO_BYTES + (WAVES * jh + wave) * 1024);
-                }
+                if (g < WD_PER_WAVE) issue_w(s_next, g);
+                if (g == WD_PER_WAVE)
+                    dma(halo_src(q_next, jh), hbuf0 + (q_next & 1) * HALO_BYTES + (WAVES * jh + wave) * 1024);
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    if (SHPL_WIDE_PROBE == 3)
-                        acc[i][j][0] += (float)av[i][0] * (float)bv[j][0];
-                    else
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv[j], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < NJ; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv[j], acc[i][j], 0, 0, 0);
             }
         }
         // the step's weight DMAs have landed (the halo DMA issued last may stay in flight, but not past the
@@ -284,69 +267,14 @@ __device__ __forceinline__ Piece8 piece_f32(const u32x4 &raw) {
     return r;
 }
 
-// The pooled vector of every run of the cell-keyed CSR, piece g, into its compact row frame_off[f] + (run rank
-// in frame f): one thread per (entry, 16-byte piece); the thread on a run's first entry sums the run in entry
-// order with separate multiply and add from 0 and rounds once -- k_sparse's arithmetic, bit for bit. GROUP: a
-// pixel-keyed CSR with ent_col, summed per column first (RunSum: walk_run<GROUP>'s order).
-template <bool GROUP>
-__global__ __launch_bounds__(256) void k_pool_runs_wide(const int32_t *ent_dst, const int32_t *ent_src,
-                                                        const float *ent_val, const int32_t *ent_col,
-                                                        int64_t nnz_cap, const uint16_t *img,
-                                                        int64_t img_stride, int64_t img_off, int c_b, int np, int H,
-                                                        int W, int wpr, const uint32_t *occ, const int32_t *occ_base,
-                                                        const int64_t *frame_off, uint16_t *cmp) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t e = t / np;
-    const int g = (int)(t - e * np);
-    if (e >= nnz_cap) return;
-    const int32_t d = ent_dst[e];
-    const int32_t prev = e > 0 ? ent_dst[e - 1] : -1;
-    int32_t dn = e + 1 < nnz_cap ? ent_dst[e + 1] : -1;
-    float wv = ent_val[e];
-    int32_t src = ent_src[e];
-    int32_t kc = GROUP ? ent_col[e] : 0;
-    if (d < 0 || prev == d) return;
-    const int64_t cells = (int64_t)H * W;
-    const int f = (int)(d / cells);
-    const int c = (int)(d - f * cells), y = c / W, x = c - y * W;
-    const int64_t wi = ((int64_t)f * H + y) * wpr + (x >> 5);
-    const int32_t rid = occ_base[wi] + __popc(occ[wi] & ((1u << (x & 31)) - 1u));
-    RunSum<GROUP, 8> sum;
-    sum.init();
-    // entry i's row piece goes out with entry i+1's index words (one round trip per entry)
-    for (int64_t i = e;; ++i) {
-        const u32x4 raw = *reinterpret_cast<const u32x4 *>(img + (int64_t)src * img_stride + img_off + g * 8);
-        const bool more = dn == d;
-        float wn = 0.0f;
-        int32_t sn = 0, dnn = -1, kn = 0;
-        if (more) {
-            wn = ent_val[i + 1];
-            sn = ent_src[i + 1];
-            if (GROUP) kn = ent_col[i + 1];
-            dnn = i + 2 < nnz_cap ? ent_dst[i + 2] : -1;
-        }
-        sum.add(kc, wv, piece_f32(raw).x);
-        if (!more) break;
-        wv = wn;
-        src = sn;
-        kc = kn;
-        dn = dnn;
-    }
-    sum.finish();
-    uint16_t v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(sum.acc[j]);
-    *reinterpret_cast<u32x4 *>(cmp + (frame_off[f] + rid) * (int64_t)c_b + g * 8) = *reinterpret_cast<u32x4 *>(v);
-}
-
-// K consecutive entries per thread, one 8-channel piece g of each: their index words in one round trip and
+// The pooled vector of every run of the pool's CSR, piece g, into its compact row frame_off[f] + (run rank in
+// frame f). A thread takes one 8-channel piece of K consecutive entries: their index words in one round trip and
 // their K row pieces in flight together (the runs of a cell are mostly one entry long, so a thread per entry
-// spent a round trip per index word and per row with little else in flight); each run head sums its run in
-// entry order from 0 with separate multiply and add, as k_pool_runs_wide does -- bit for bit -- walking on past
-// the group when the run does. GROUP: as k_pool_runs_wide's.
-#ifndef SHPL_WIDE_RUNS_K
-#define SHPL_WIDE_RUNS_K 4  // 1: k_pool_runs_wide (a thread per entry and piece)
-#endif
+// spent a round trip per index word and per row with little else in flight). Each run head sums its run in entry
+// order from 0 with separate multiply and add and rounds once -- k_sparse's arithmetic, bit for bit -- walking on
+// past the group, one round trip per entry, when the run does. GROUP: a pixel-keyed CSR with ent_col, summed per
+// column first (RunSum: walk_run<GROUP>'s order).
+constexpr int RUNS_K = 4;  // measured: 1, 4, 8, 16 entries per thread (docs/HISTORY.md §5)
 template <int K, bool GROUP>
 __global__ __launch_bounds__(256) void k_pool_runs_wide_k(const int32_t *ent_dst, const int32_t *ent_src,
                                                           const float *ent_val, const int32_t *ent_col,
@@ -439,16 +367,9 @@ int prep(int n_frames, int h, int w, int wpr, const int32_t *ent_dst, const int3
                                img_stride, img_off, 0, occ, occ_base, cmp, s);
     if (rc) return rc;
     const int np = c_b / 8;
-    if (nnz_cap > 0 && np > 0 && SHPL_WIDE_RUNS_K > 1) {
-        const int64_t threads = (nnz_cap + SHPL_WIDE_RUNS_K - 1) / SHPL_WIDE_RUNS_K * np;
-        const auto kernel = ent_col ? k_pool_runs_wide_k<SHPL_WIDE_RUNS_K, true>
-                                    : k_pool_runs_wide_k<SHPL_WIDE_RUNS_K, false>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ent_dst, ent_src, ent_val,
-                           ent_col, nnz_cap, img, img_stride, img_off, c_b, np, h, w, wpr, occ, occ_base, frame_off, cmp);
-        SHPL_LAUNCH_CHECK();
-    } else if (nnz_cap > 0 && np > 0) {
-        const int64_t threads = nnz_cap * np;
-        const auto kernel = ent_col ? k_pool_runs_wide<true> : k_pool_runs_wide<false>;
+    if (nnz_cap > 0 && np > 0) {
+        const int64_t threads = (nnz_cap + RUNS_K - 1) / RUNS_K * np;
+        const auto kernel = ent_col ? k_pool_runs_wide_k<RUNS_K, true> : k_pool_runs_wide_k<RUNS_K, false>;
         hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ent_dst, ent_src, ent_val,
                            ent_col, nnz_cap, img, img_stride, img_off, c_b, np, h, w, wpr, occ, occ_base, frame_off, cmp);
         SHPL_LAUNCH_CHECK();
