@@ -695,6 +695,68 @@ int shpl_conv3x3_wgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, cons
                              int64_t gy_stride, int64_t c_out, float *d_dw, void *d_ws, size_t ws_bytes,
                              const void *d_fwd_ws, size_t fwd_ws_bytes, int fwd_stats, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * 1x1 heads over the fused map, the SHPL applied after the projection
+ * (MV3D's rpn_cls_score / rpn_bbox_pred)
+ * ------------------------------------------------------------------------- */
+
+/* out[r, co] = sum_ci [a || b'][r, ci] * W[ci, co] + bias[co], a 1x1 VALID conv with a bias and no activation
+ * over `rows` rows. Channels [0, c_a) are row r of d_a (element r*a_stride + a_off + c); channels
+ * [c_a, c_a + c_b) come from d_b:
+ *   pool == NULL: row r of d_b (r*b_stride + b_off + c), a second dense map of rows_b == rows rows; c_b = 0
+ *                 (d_b NULL, rows_b ignored) is the one-map form, the head of a materialised conv_lidar_fused;
+ *   pool != NULL: the img->BEV pooled map of the image map d_b (rows_b pixels) through the cell-keyed CSR
+ *                 (shpl_build_csr SHPL_BY_CELL, SHPL_ORDER_ENTRY, n_keys == rows; a pixel-keyed CSR -- ent_col
+ *                 set or SHPL_CSR_IDENTITY_COLS -- is SHPL_ERR_ARG). A 1x1 conv and the SHPL are both linear,
+ *                 so the head is applied before the pooling and neither the pooled map nor the concat is
+ *                 ever written. The summation contract:
+ *                     Z[p, :]   = b[p, :] . W[c_a:, :]                       (f32, in the workspace, no bias)
+ *                     out[r, :] = a[r, :] . W[:c_a, :] + bias + sum_{k in run(r)} m_k * Z[src_k, :]
+ *                 with the run of cell r walked in CSR order, one f32 multiply and one f32 add per entry
+ *                 (no FMA contraction), as shpl_pull walks it; the two products are MFMA sums over the
+ *                 channels. The result is the 1x1 conv of [a || shpl_pull(SHPL_BY_CELL, ...)] up to summation
+ *                 order -- NOT bitwise: the pooled form sums sum_k m_k (sum_c b W) where the materialised one
+ *                 sums sum_c (sum_k m_k b) W. The runs come from pool->key_range (global entry slots, so no
+ *                 per-frame entry offsets are taken); a CSR without it gets one built in the workspace.
+ * d_weights: [c_a + c_b][c_out] in the feature dtype (the HWIO variable of a 1x1 slim / Network.conv layer),
+ * 1 <= c_out <= 32; d_bias: optional [c_out] f32. Several heads share one call with their weights joined
+ * along c_out. f32: v_mfma_f32_32x32x2_f32; SHPL_BF16: bf16 maps and weights, v_mfma_f32_32x32x16_bf16, f32
+ * accumulation, Z and the run sum in f32, one rounding at the store of d_out ([rows], out_stride elements
+ * per row, feature dtype). Workspace: shpl_head1x1_workspace_bytes (pooled = pool != NULL), which also
+ * covers shpl_head1x1_dgrad.
+ * Replaces: sparse_pool (network.py:243-246), the concat and the two 1x1 convs of
+ *   MV3D_TF_release/lib/networks/MV3D_voxel_train.py:144-178 (keep_prob = 1). */
+int shpl_head1x1_workspace_bytes(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out,
+                                 int pooled, size_t *bytes);
+int shpl_head1x1(int dtype, int64_t rows, const void *d_a, int64_t a_stride, int64_t a_off, int64_t c_a,
+                 const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, int64_t rows_b,
+                 const shpl_csr *pool, const void *d_weights, int64_t c_out, const float *d_bias, void *d_out,
+                 int64_t out_stride, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Input gradients of shpl_head1x1: d_da[r, c] = sum_co gy[r, co] * W[c, co] ([rows], da_stride), and for the
+ * second source d_db = G . W[c_a:, :]^T with G = gy (pool_grad NULL: dense b, rows_b == rows) or
+ * G = _sparse_pool_trans_op(M, gy), the gradient pulled back to the rows_b pixels at c_out channels through
+ * pool_grad, the pixel-keyed CSR of the pooled source's gradient (shpl_build_csr SHPL_BY_PIXEL,
+ * SHPL_ORDER_COL_ENTRY, n_keys == rows_b; shpl_pull's sums, kept in f32 in the workspace; a cell-keyed CSR is
+ * SHPL_ERR_ARG). Either output may be NULL. The sums over co are f32 fused multiply-adds in co order; one
+ * rounding at the store (feature dtype). Workspace: shpl_head1x1_workspace_bytes. */
+int shpl_head1x1_dgrad(int dtype, int64_t rows, const void *d_gy, int64_t gy_stride, int64_t c_out,
+                       const void *d_weights, int64_t c_a, int64_t c_b, void *d_da, int64_t da_stride, void *d_db,
+                       int64_t db_stride, int64_t rows_b, const shpl_csr *pool_grad, void *d_ws, size_t ws_bytes,
+                       void *stream);
+
+/* Weight and bias gradients of shpl_head1x1: d_dw f32 [c_a + c_b][c_out], dw[c, co] = sum_r x[r, c] * G[r, co]
+ * over the rows of `a` with G = gy, and over the rows of `b` with G as in shpl_head1x1_dgrad (pool_grad: the
+ * same pixel-keyed CSR, NULL for dense b); d_dbias (optional, [c_out] f32) = sum_r gy[r, :]. Two stages:
+ * per-row-chunk f32 partials in the workspace (fused multiply-adds in row order), then the partials summed in
+ * chunk order in f64 -- no floating-point atomics, bitwise the same from run to run. */
+int shpl_head1x1_wgrad_workspace_bytes(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b,
+                                       int64_t c_out, int pooled, size_t *bytes);
+int shpl_head1x1_wgrad(int dtype, int64_t rows, const void *d_a, int64_t a_stride, int64_t a_off, int64_t c_a,
+                       const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, int64_t rows_b,
+                       const shpl_csr *pool_grad, const void *d_gy, int64_t gy_stride, int64_t c_out, float *d_dw,
+                       float *d_dbias, void *d_ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

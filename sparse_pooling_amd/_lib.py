@@ -57,6 +57,10 @@ class Csr:
         cap = max(int(nnz_cap), 1)
         self.n_keys, self.nnz_cap = int(n_keys), int(nnz_cap)
         self.ent_dst = torch.empty(cap, **i32)
+        if self.nnz_cap == 0:
+            # an empty map keeps one padding slot, which no builder writes (nnz_cap 0) and which ops._csr counts as
+            # capacity (the tensor's length): mark it empty, or the sparse pass reads whatever the allocator left
+            self.ent_dst.fill_(-1)
         self.ent_src = torch.empty(cap, **i32)
         self.ent_val = torch.empty(cap, dtype=torch.float32, device=device)
         self.ent_col = torch.empty(cap, **i32) if with_col else None
@@ -181,6 +185,14 @@ def _declare(lib):
                                      ctypes.POINTER(ShplCsr), p, p, i64, i64, p, p, sz, p]),
         "shpl_conv3x3_wgrad_reuse": (i32, [i32, i32, i64, i64, p, i64, i64, i64, p, i64, i64, i64,
                                            ctypes.POINTER(ShplCsr), p, p, i64, i64, p, p, sz, p, sz, i32, p]),
+        "shpl_head1x1_workspace_bytes": (i32, [i32, i64, i64, i64, i64, i64, i32, psz]),
+        "shpl_head1x1": (i32, [i32, i64, p, i64, i64, i64, p, i64, i64, i64, i64, ctypes.POINTER(ShplCsr), p, i64,
+                               p, p, i64, p, sz, p]),
+        "shpl_head1x1_dgrad": (i32, [i32, i64, p, i64, i64, p, i64, i64, p, i64, p, i64, i64,
+                                     ctypes.POINTER(ShplCsr), p, sz, p]),
+        "shpl_head1x1_wgrad_workspace_bytes": (i32, [i32, i64, i64, i64, i64, i64, i32, psz]),
+        "shpl_head1x1_wgrad": (i32, [i32, i64, p, i64, i64, i64, p, i64, i64, i64, i64, ctypes.POINTER(ShplCsr), p,
+                                     i64, i64, p, p, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

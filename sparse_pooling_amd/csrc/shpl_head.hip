@@ -1,0 +1,753 @@
+// shpl_head.hip -- 1x1 heads over [a || pooled b] with the SHPL applied after the projection (MV3D's
+// rpn_cls_score / rpn_bbox_pred, MV3D_TF_release/lib/networks/MV3D_voxel_train.py:144-178), forward and backward.
+//
+// A 1x1 conv and the SHPL are both linear, so the head is applied to the image map before the pooling:
+//   Z[p, :]   = b[p, :] . W_b                                   (f32 [rows_b][32], workspace)
+//   out[r, :] = a[r, :] . W_a + bias + sum_{k in run(r)} m_k * Z[src_k, :]
+// k_head_gemm is a skinny MFMA GEMM (32 rows x 32 padded outputs per wave, K = the channels) that runs once per
+// source; over `a` its epilogue walks the cell's run of the cell-keyed CSR (key_range) in CSR order with
+// separate multiplies and adds, as walk_run does. The backward multiplies by K = c_out <= 32: plain fused
+// multiply-adds at the vector rate (the f32 MFMA's rate) with the small operand in scalar registers, over
+// f32 copies of the gradient padded to a multiple of 4 columns so that the pulls and the row loads are whole
+// 16-byte pieces. The weight gradient is two-stage: per-row-chunk partials in the workspace, summed in chunk
+// order -- no floating-point atomics.
+#include "shpl_common.h"
+
+namespace shpl {
+namespace head {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int NP = 32;        // output columns of a GEMM tile: c_out padded
+constexpr int TILE_ROWS = 32; // rows of a GEMM tile (one wave)
+constexpr int GEMM_WAVES = 4; // waves per GEMM workgroup
+constexpr int SUB = 4;        // 16-byte pieces per lane and K step: 64 contiguous bytes of its row
+constexpr int COLS = 4;       // channels per thread of the backward kernels
+constexpr int DGRAD_ROWS = 128;  // rows per wave of the input gradient
+constexpr int WGRAD_MIN_ROWS = 64, WGRAD_MAX_CHUNKS = 256;  // the weight gradient's row chunks (its partials)
+constexpr int WGRAD_WAVES = 4;  // waves per chunk, a quarter of its rows each
+
+template <typename T>
+struct Vec;  // elements of one 16-byte piece
+template <>
+struct Vec<float> {
+    static constexpr int N = 4;
+};
+template <>
+struct Vec<uint16_t> {
+    static constexpr int N = 8;
+};
+
+__device__ __forceinline__ float to_f32(float v) { return v; }
+__device__ __forceinline__ float to_f32(uint16_t v) { return bf16_to_f32(v); }
+__device__ __forceinline__ void from_f32(float v, float *o) { *o = v; }
+__device__ __forceinline__ void from_f32(float v, uint16_t *o) { *o = f32_to_bf16(v); }
+
+// ---------------------------------------------------------------- weights, packed per lane
+// K is walked in steps of SUB * 2 * VEC channels: lane (n = lane % 32, h = lane / 32) holds channels
+// step * SUB * 2 * VEC + h * SUB * VEC + j * VEC + i (j < SUB, i < VEC) of its row -- SUB 16-byte loads of 64
+// contiguous bytes, the two halves of the wave a whole 128-byte line per row -- and of column n of W. Packed:
+// wp[step][j][lane][i], zero past the channels and past c_out. (A sum over K: any assignment of channels to
+// MFMA slots serves, as long as both operands use the same.)
+template <typename T>
+__global__ __launch_bounds__(SHPL_BLOCK) void k_head_pack(const T *__restrict__ w, int64_t w_row0, int64_t c,
+                                                          int c_out, T *__restrict__ wp, int64_t n) {
+    constexpr int VEC = Vec<T>::N;
+    const int64_t t = (int64_t)blockIdx.x * SHPL_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    const int i = (int)(t % VEC), lane = (int)((t / VEC) % 64), j = (int)((t / (VEC * 64)) % SUB);
+    const int64_t step = t / (VEC * 64 * SUB);
+    const int64_t k = (step * 2 + (lane >> 5)) * SUB * VEC + j * VEC + i;
+    const int col = lane & 31;
+    T v = T(0);
+    if (k < c && col < c_out) v = w[(w_row0 + k) * c_out + col];
+    wp[t] = v;
+}
+
+inline int64_t pack_steps(int64_t c, int vec) { return (c + SUB * 2 * vec - 1) / (SUB * 2 * vec); }
+
+struct Src {
+    const void *x;
+    int64_t stride, off, c;
+    const void *wp;
+};
+
+struct GemmArgs {
+    Src s[2];
+    int64_t rows;
+    const float *bias;
+    int c_out;
+    // the run walk (key_range NULL: none)
+    const int32_t *key_range, *ent_src;
+    const float *ent_val, *z;
+    int64_t nnz_cap, z_rows;
+    void *out;  // to_z: f32 [rows][NP]; else the feature dtype, out_stride elements per row
+    int64_t out_stride;
+    int to_z;
+};
+
+__device__ __forceinline__ f32x16 mma(const float (&x)[4], const float (&w)[4], f32x16 acc) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[i], w[i], acc, 0, 0, 0);
+    return acc;
+}
+__device__ __forceinline__ f32x16 mma(const uint16_t (&x)[8], const uint16_t (&w)[8], f32x16 acc) {
+    bf16x8 xa, wb;
+    __builtin_memcpy(&xa, x, 16);
+    __builtin_memcpy(&wb, w, 16);
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa, wb, acc, 0, 0, 0);
+}
+
+// acc += row rl of one source times its packed weights (a source of no channels: nothing). Two register stages:
+// the loads of the next K step are issued before the MFMAs of the current one.
+template <typename T, bool ALIGNED>
+__device__ __forceinline__ f32x16 gemm_source(const Src &src, int64_t rl, int lane, f32x16 acc) {
+    constexpr int VEC = Vec<T>::N;
+    const int64_t c = src.c;
+    const int h = lane >> 5;
+    const T *xr = reinterpret_cast<const T *>(src.x) + rl * src.stride + src.off + h * SUB * VEC;
+    const T *wp = reinterpret_cast<const T *>(src.wp) + lane * VEC;
+    const int64_t steps = (c + SUB * 2 * VEC - 1) / (SUB * 2 * VEC);
+    auto load = [&](int64_t st, T (&xv)[SUB][VEC], T (&wv)[SUB][VEC]) {
+        const int64_t k = st * SUB * 2 * VEC;
+#pragma unroll
+        for (int j = 0; j < SUB; ++j) {
+            if constexpr (ALIGNED) {
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(xr + k + j * VEC);
+                __builtin_memcpy(xv[j], &v, 16);
+            } else {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) xv[j][i] = k + (h * SUB + j) * VEC + i < c ? xr[k + j * VEC + i] : T(0);
+            }
+            const u32x4 wq = *reinterpret_cast<const u32x4 *>(wp + (st * SUB + j) * 64 * VEC);
+            __builtin_memcpy(wv[j], &wq, 16);
+        }
+    };
+    auto mul = [&](const T (&xv)[SUB][VEC], const T (&wv)[SUB][VEC]) {
+#pragma unroll
+        for (int j = 0; j < SUB; ++j) acc = mma(xv[j], wv[j], acc);
+    };
+    if (steps == 0) return acc;
+    T xa[SUB][VEC], wa[SUB][VEC], xb[SUB][VEC], wb[SUB][VEC];
+    load(0, xa, wa);
+    // a branch-free body (a load under a condition makes the wait before the MFMAs drain the loads just issued): the
+    // second load of the last pair of an even count re-reads the last step, unused
+    for (int64_t p = 0; p < steps / 2; ++p) {
+        load(2 * p + 1, xb, wb);
+        mul(xa, wa);
+        load(2 * p + 2 < steps ? 2 * p + 2 : steps - 1, xa, wa);
+        mul(xb, wb);
+    }
+    if (steps & 1) mul(xa, wa);
+    return acc;
+}
+
+// One wave per 32 rows. ALIGNED: every row of both sources starts on a 16-byte boundary and holds whole K steps.
+// The run walk of the epilogue: a lane holds 16 rows of column n; their key ranges are fetched before the K loop,
+// and the runs are walked side by side -- round t takes entry t of every row's run (16 independent loads of the
+// entry, then of Z) -- so that a row's entries are still added in CSR order, one multiply and one add each, while
+// the rows' load latencies overlap instead of queueing up.
+template <typename T, bool ALIGNED>
+__global__ __launch_bounds__(GEMM_WAVES * 64) void k_head_gemm(GemmArgs a) {
+    const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+    const int64_t row0 = ((int64_t)blockIdx.x * GEMM_WAVES + (threadIdx.x >> 6)) * TILE_ROWS;
+    if (row0 >= a.rows) return;
+    const int64_t rl = row0 + n < a.rows ? row0 + n : a.rows - 1;  // the row this lane loads (clamped: not stored)
+    // acc[i]: row 8 * (i / 4) + 4 * h + i % 4 of the tile, column n
+    int32_t first[16], len[16];
+    const bool walk = !a.to_z && a.key_range;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int64_t row = row0 + 8 * (i >> 2) + 4 * h + (i & 3);
+        first[i] = len[i] = 0;
+        if (walk && row < a.rows) {
+            int64_t e = a.key_range[2 * row], end = a.key_range[2 * row + 1];
+            if (e < 0) e = 0;
+            if (end > a.nnz_cap) end = a.nnz_cap;
+            first[i] = (int32_t)e;
+            len[i] = end > e ? (int32_t)(end - e) : 0;
+        }
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+    acc = gemm_source<T, ALIGNED>(a.s[0], rl, lane, acc);
+    acc = gemm_source<T, ALIGNED>(a.s[1], rl, lane, acc);
+    const float bias = (a.bias && n < a.c_out) ? a.bias[n] : 0.0f;
+    float v[16];
+    int32_t longest = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        v[i] = __fadd_rn(acc[i], bias);
+        longest = len[i] > longest ? len[i] : longest;
+    }
+    for (int32_t t = 0; t < longest; ++t) {
+        int64_t src[16];
+        float m[16], z[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            src[i] = -1;
+            m[i] = 0.0f;
+            if (t < len[i]) {
+                src[i] = a.ent_src[first[i] + t];
+                m[i] = a.ent_val[first[i] + t];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            src[i] = (src[i] >= 0 && src[i] < a.z_rows) ? src[i] : -1;
+            z[i] = src[i] >= 0 ? a.z[src[i] * NP + n] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (src[i] >= 0) v[i] = __fadd_rn(v[i], __fmul_rn(m[i], z[i]));
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int64_t row = row0 + 8 * (i >> 2) + 4 * h + (i & 3);
+        if (row < a.rows) {
+            if (a.to_z) {
+                reinterpret_cast<float *>(a.out)[row * NP + n] = v[i];
+            } else if (n < a.c_out) {
+                from_f32(v[i], reinterpret_cast<T *>(a.out) + row * a.out_stride + n);
+            }
+        }
+    }
+}
+
+// key_range [n_keys][2] of a CSR that carries none, over zeros: a destination's run is one stretch of equal
+// ent_dst (the entries are sorted by destination inside every frame, and frames share no destination).
+__global__ __launch_bounds__(SHPL_BLOCK) void k_head_ranges(const int32_t *__restrict__ ent_dst, int64_t nnz_cap,
+                                                            int64_t n_keys, int32_t *__restrict__ kr) {
+    const int64_t e = (int64_t)blockIdx.x * SHPL_BLOCK + threadIdx.x;
+    if (e >= nnz_cap) return;
+    const int32_t d = ent_dst[e];
+    if (d < 0 || d >= n_keys) return;
+    if (e == 0 || ent_dst[e - 1] != d) kr[2 * (int64_t)d] = (int32_t)e;
+    if (e == nnz_cap - 1 || ent_dst[e + 1] != d) kr[2 * (int64_t)d + 1] = (int32_t)(e + 1);
+}
+
+// ---------------------------------------------------------------- backward
+// gp[r][j] = g[r][j] as f32, zero for c_out <= j < CO.
+template <typename T>
+__global__ __launch_bounds__(SHPL_BLOCK) void k_head_gpad(const T *__restrict__ g, int64_t g_stride, int c_out, int co,
+                                                          int64_t n, float *__restrict__ gp) {
+    const int64_t t = (int64_t)blockIdx.x * SHPL_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    const int64_t r = t / co;
+    const int j = (int)(t % co);
+    gp[t] = j < c_out ? to_f32(g[r * g_stride + j]) : 0.0f;
+}
+
+// dx[r][c] = sum_j g[r][j] * W[w_row0 + c][j], j ascending, fused multiply-adds. A thread keeps its COLS
+// channels' weights in registers; g's row is the same for the whole wave.
+template <typename T, int CO, bool ALIGNED>
+__global__ __launch_bounds__(64) void k_head_dgrad(const float *__restrict__ g, int64_t rows, int64_t rows_per,
+                                                   const T *__restrict__ w, int64_t w_row0, int64_t c_n, int c_out,
+                                                   T *__restrict__ dx, int64_t dx_stride) {
+    const int64_t c = ((int64_t)blockIdx.y * 64 + threadIdx.x) * COLS;
+    float wr[COLS][CO];
+#pragma unroll
+    for (int i = 0; i < COLS; ++i)
+#pragma unroll
+        for (int j = 0; j < CO; ++j) wr[i][j] = (c + i < c_n && j < c_out) ? to_f32(w[(w_row0 + c + i) * c_out + j]) : 0.0f;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per, r1 = r0 + rows_per < rows ? r0 + rows_per : rows;
+    for (int64_t r = r0; r < r1; ++r) {
+        const float *gr = g + r * CO;
+        float o[COLS];
+#pragma unroll
+        for (int i = 0; i < COLS; ++i) o[i] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < CO; ++j) {
+            const float gj = gr[j];
+#pragma unroll
+            for (int i = 0; i < COLS; ++i) o[i] = __builtin_fmaf(gj, wr[i][j], o[i]);
+        }
+        if (c >= c_n) continue;
+        T ov[COLS];
+#pragma unroll
+        for (int i = 0; i < COLS; ++i) from_f32(o[i], &ov[i]);
+        T *dst = dx + r * dx_stride + c;
+        if constexpr (ALIGNED) {
+            typedef typename std::conditional<sizeof(T) == 4, f32x4, u16x4>::type V;
+            V v;
+            __builtin_memcpy(&v, ov, sizeof(V));
+            *reinterpret_cast<V *>(dst) = v;
+        } else {
+#pragma unroll
+            for (int i = 0; i < COLS; ++i)
+                if (c + i < c_n) dst[i] = ov[i];
+        }
+    }
+}
+
+// Stage 1 of dw[c][j] = sum_r x[r][c] * g[r][j]: row chunk blockIdx.x, a quarter of it per wave (rows ascending,
+// fused multiply-adds), the four waves' sums added through LDS in a fixed order ((w0 + w3) + w2) + w1, into
+// part[chunk][c][j] ([c_n + 1][CO] per chunk; row c_n: the chunk's sum of g, the bias gradient's partial,
+// written when `bias` is set).
+template <typename T, int CO, bool ALIGNED>
+__global__ __launch_bounds__(WGRAD_WAVES * 64) void k_head_wgrad(const T *__restrict__ x, int64_t x_stride, int64_t x_off,
+                                                                 int64_t c_n, const float *__restrict__ g, int64_t rows,
+                                                                 int64_t rows_per, int bias, float *__restrict__ part) {
+    __shared__ float red[(COLS * CO + 1) * 64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: g's rows load into scalar registers
+    const int64_t c = ((int64_t)blockIdx.y * 64 + lane) * COLS;
+    float acc[COLS][CO];
+#pragma unroll
+    for (int i = 0; i < COLS; ++i)
+#pragma unroll
+        for (int j = 0; j < CO; ++j) acc[i][j] = 0.0f;
+    float bs = 0.0f;
+    const bool sum_g = bias && blockIdx.y == 0;
+    const int64_t b0 = (int64_t)blockIdx.x * rows_per, b1 = b0 + rows_per < rows ? b0 + rows_per : rows;
+    const int64_t quarter = (rows_per + WGRAD_WAVES - 1) / WGRAD_WAVES;
+    const int64_t r0 = b0 + wave * quarter, r1 = r0 + quarter < b1 ? r0 + quarter : b1;
+    for (int64_t r = r0; r < r1; ++r) {
+        const float *gr = g + r * CO;
+        const T *xr = x + r * x_stride + x_off + c;
+        float xv[COLS];
+        if constexpr (ALIGNED) {
+            typedef typename std::conditional<sizeof(T) == 4, f32x4, u16x4>::type V;
+            T raw[COLS];
+            V v = {};
+            if (c < c_n) v = *reinterpret_cast<const V *>(xr);
+            __builtin_memcpy(raw, &v, sizeof(V));
+#pragma unroll
+            for (int i = 0; i < COLS; ++i) xv[i] = to_f32(raw[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < COLS; ++i) xv[i] = c + i < c_n ? to_f32(xr[i]) : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < CO; ++j) {
+            const float gj = gr[j];
+#pragma unroll
+            for (int i = 0; i < COLS; ++i) acc[i][j] = __builtin_fmaf(xv[i], gj, acc[i][j]);
+        }
+        if (sum_g) bs = __fadd_rn(bs, gr[lane % CO]);
+    }
+    for (int w = WGRAD_WAVES - 1; w > 0; --w) {
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < COLS; ++i)
+#pragma unroll
+                for (int j = 0; j < CO; ++j) red[(i * CO + j) * 64 + lane] = acc[i][j];
+            red[COLS * CO * 64 + lane] = bs;
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int i = 0; i < COLS; ++i)
+#pragma unroll
+                for (int j = 0; j < CO; ++j) acc[i][j] = __fadd_rn(acc[i][j], red[(i * CO + j) * 64 + lane]);
+            bs = __fadd_rn(bs, red[COLS * CO * 64 + lane]);
+        }
+        __syncthreads();
+    }
+    if (wave != 0) return;
+    float *p = part + (int64_t)blockIdx.x * (c_n + 1) * CO;
+#pragma unroll
+    for (int i = 0; i < COLS; ++i) {
+        if (c + i >= c_n) continue;
+#pragma unroll
+        for (int j = 0; j < CO; j += 4)
+            *reinterpret_cast<f32x4 *>(p + (c + i) * CO + j) = f32x4{acc[i][j], acc[i][j + 1], acc[i][j + 2], acc[i][j + 3]};
+    }
+    if (sum_g && lane < CO) p[c_n * CO + lane] = bs;
+}
+
+// Stage 2: dw[w_row0 + c][j] = the partials of (c, j) summed in f64 and rounded once; row c_n of the partials is
+// the bias gradient (with_bias). A workgroup sums 32 elements: 8 threads per element take every 8th chunk in
+// chunk order, and their sums are added in thread order -- a fixed order.
+__global__ __launch_bounds__(SHPL_BLOCK) void k_head_wreduce(const float *__restrict__ part, int64_t chunks, int64_t c_n,
+                                                             int co, int c_out, int with_bias, float *__restrict__ dw,
+                                                             int64_t w_row0, float *__restrict__ dbias) {
+    __shared__ double red[8][32];
+    const int el = threadIdx.x & 31, sub = threadIdx.x >> 5;
+    const int64_t t = (int64_t)blockIdx.x * 32 + el;
+    const int64_t n_rows = c_n + (with_bias ? 1 : 0);
+    const bool live = t < n_rows * c_out;
+    const int64_t c = t / c_out;
+    const int j = (int)(t % c_out);
+    double s = 0.0;
+    if (live)
+        for (int64_t k = sub; k < chunks; k += 8) s += (double)part[(k * (c_n + 1) + c) * co + j];
+    red[sub][el] = s;
+    __syncthreads();
+    if (sub != 0 || !live) return;
+    s = 0.0;
+    for (int k = 0; k < 8; ++k) s += red[k][el];
+    if (c < c_n) {
+        dw[(w_row0 + c) * c_out + j] = (float)s;
+    } else {
+        dbias[j] = (float)s;
+    }
+}
+
+// ---------------------------------------------------------------- host side
+inline int pad_cols(int64_t c_out) { return (int)((c_out + 3) / 4 * 4); }  // whole 16-byte pieces of f32
+inline int64_t esize(int dtype) { return dtype == SHPL_F32 ? 4 : 2; }
+
+inline bool pixel_keyed(const shpl_csr *p) { return p->ent_col || (p->flags & SHPL_CSR_IDENTITY_COLS); }
+
+// rows of source `x` in pieces of `vec` elements: whole pieces, each on its own alignment
+inline bool rows_aligned(const void *x, int64_t stride, int64_t off, int64_t c, int64_t vec, int64_t esz) {
+    return c % vec == 0 && stride % vec == 0 && off % vec == 0 && ((uintptr_t)x % (size_t)(vec * esz)) == 0;
+}
+
+struct FwdLayout {
+    size_t wp[2], z, kr, bytes;
+};
+inline FwdLayout fwd_layout(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, bool pooled) {
+    const int vec = (int)(16 / esize(dtype));
+    FwdLayout l = {};
+    size_t o = 0;
+    const int64_t cs[2] = {c_a, c_b};
+    for (int s = 0; s < 2; ++s) {
+        l.wp[s] = o;
+        o = align_up(o + (size_t)pack_steps(cs[s], vec) * SUB * 64 * 16, 256);
+    }
+    l.z = o;
+    if (pooled) o = align_up(o + (size_t)rows_b * NP * 4, 256);
+    l.kr = o;
+    if (pooled) o = align_up(o + (size_t)rows * 8, 256);
+    l.bytes = o;
+    return l;
+}
+
+struct BwdLayout {
+    int co;
+    int64_t chunks[2];  // upper bounds of the weight gradient's row chunks per source
+    size_t gp, gimg, part[2], bytes;
+};
+inline int64_t wgrad_chunks_max(int64_t rows) {
+    const int64_t c = (rows + WGRAD_MIN_ROWS - 1) / WGRAD_MIN_ROWS;
+    return c < 1 ? 1 : c > WGRAD_MAX_CHUNKS ? WGRAD_MAX_CHUNKS : c;
+}
+inline BwdLayout bwd_layout(int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out, bool pooled,
+                            bool wgrad) {
+    BwdLayout l = {};
+    l.co = pad_cols(c_out);
+    size_t o = 0;
+    l.gp = o;
+    o = align_up(o + (size_t)rows * l.co * 4, 256);
+    l.gimg = o;
+    if (pooled) o = align_up(o + (size_t)rows_b * l.co * 4, 256);
+    const int64_t rs[2] = {rows, rows_b}, cs[2] = {c_a, c_b};
+    for (int s = 0; s < 2; ++s) {
+        l.part[s] = o;
+        l.chunks[s] = wgrad_chunks_max(rs[s]);
+        if (wgrad && cs[s] > 0) o = align_up(o + (size_t)l.chunks[s] * (size_t)(cs[s] + 1) * l.co * 4, 256);
+    }
+    l.bytes = o;
+    return l;
+}
+
+// The one published size of the forward's and the input gradient's workspace (shpl_head1x1_workspace_bytes):
+// both calls hold the caller to it.
+inline size_t ws_need(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out, bool pooled) {
+    const size_t f = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled).bytes;
+    const size_t b = bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled, false).bytes;
+    return f > b ? f : b;
+}
+
+// The checks every entry point shares: dtype, channel counts, rows; then the second source's form.
+inline int check_shape(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out) {
+    if (dtype != SHPL_F32 && dtype != SHPL_BF16) return SHPL_ERR_ARG;
+    if (c_out < 1 || c_out > NP) return SHPL_ERR_BAD_SHAPE;
+    const int64_t lim = (int64_t)1 << 31;
+    if (rows < 0 || rows >= lim || rows_b < 0 || rows_b >= lim) return SHPL_ERR_BAD_SHAPE;
+    if (c_a < 1 || c_b < 0 || c_a >= (1 << 22) || c_b >= (1 << 22)) return SHPL_ERR_BAD_SHAPE;  // grid.y, 32-bit rows
+    return SHPL_OK;
+}
+
+// pool: the CSR of the pooled form (NULL: dense b); want_pixel: the gradient's pixel-keyed list.
+inline int check_pool(const shpl_csr *pool, bool want_pixel, int64_t rows, int64_t rows_b, int64_t c_b) {
+    if (!pool) return (c_b > 0 && rows_b != rows) ? SHPL_ERR_BAD_SHAPE : SHPL_OK;
+    if (c_b < 1) return SHPL_ERR_BAD_SHAPE;
+    if (pixel_keyed(pool) != want_pixel) return SHPL_ERR_ARG;
+    if (pool->n_keys != (want_pixel ? rows_b : rows)) return SHPL_ERR_BAD_SHAPE;
+    if (pool->nnz_cap < 0 || pool->nnz_cap >= ((int64_t)1 << 31)) return SHPL_ERR_BAD_SHAPE;
+    if (pool->nnz_cap > 0 && (!pool->ent_dst || !pool->ent_src || !pool->ent_val)) return SHPL_ERR_ARG;
+    return SHPL_OK;
+}
+
+template <typename F>
+int by_dtype(int dtype, F &&fn) {
+    return dtype == SHPL_F32 ? fn(TypeOf<float>()) : fn(TypeOf<uint16_t>());
+}
+template <typename F>
+int by_cols(int co, F &&fn) {
+    switch (co) {
+        case 4: return fn(std::integral_constant<int, 4>());
+        case 8: return fn(std::integral_constant<int, 8>());
+        case 12: return fn(std::integral_constant<int, 12>());
+        case 16: return fn(std::integral_constant<int, 16>());
+        case 20: return fn(std::integral_constant<int, 20>());
+        case 24: return fn(std::integral_constant<int, 24>());
+        case 28: return fn(std::integral_constant<int, 28>());
+        default: return fn(std::integral_constant<int, 32>());
+    }
+}
+
+inline unsigned blocks_for(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
+
+// g (feature dtype) -> gp f32 [rows][co]
+int launch_gpad(int dtype, const void *d_gy, int64_t gy_stride, int64_t c_out, int co, int64_t rows, float *gp,
+                hipStream_t s) {
+    const int64_t n = rows * co;
+    if (n == 0) return SHPL_OK;
+    by_dtype(dtype, [&](auto tt) {
+        typedef typename decltype(tt)::T T;
+        hipLaunchKernelGGL(k_head_gpad<T>, dim3(blocks_for(n, SHPL_BLOCK)), dim3(SHPL_BLOCK), 0, s,
+                           reinterpret_cast<const T *>(d_gy), gy_stride, (int)c_out, co, n, gp);
+        return SHPL_OK;
+    });
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
+
+// the gradient pulled back to the pixels: _sparse_pool_trans_op(M, g) at co channels, f32
+int pull_to_pixels(const shpl_csr *pool_grad, const float *gp, int co, float *gimg, hipStream_t s) {
+    return shpl_pull(SHPL_BY_PIXEL, SHPL_F32, pool_grad, gp, co, 0, co, nullptr, 0, 0, 0, SHPL_OUT_POOL, gimg, co, s);
+}
+
+}  // namespace head
+}  // namespace shpl
+
+using namespace shpl;
+using namespace shpl::head;
+
+extern "C" int shpl_head1x1_workspace_bytes(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b,
+                                            int64_t c_out, int pooled, size_t *bytes) {
+    if (!bytes) return SHPL_ERR_ARG;
+    const int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
+    if (rc != SHPL_OK) return rc;
+    *bytes = ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled != 0);
+    return SHPL_OK;
+}
+
+extern "C" int shpl_head1x1_wgrad_workspace_bytes(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b,
+                                                  int64_t c_out, int pooled, size_t *bytes) {
+    if (!bytes) return SHPL_ERR_ARG;
+    const int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
+    if (rc != SHPL_OK) return rc;
+    *bytes = bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled != 0, true).bytes;
+    return SHPL_OK;
+}
+
+extern "C" int shpl_head1x1(int dtype, int64_t rows, const void *d_a, int64_t a_stride, int64_t a_off, int64_t c_a,
+                            const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, int64_t rows_b,
+                            const shpl_csr *pool, const void *d_weights, int64_t c_out, const float *d_bias,
+                            void *d_out, int64_t out_stride, void *d_ws, size_t ws_bytes, void *stream) {
+    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
+    if (rc != SHPL_OK) return rc;
+    if (!d_a || !d_weights || !d_out || (c_b > 0 && !d_b)) return SHPL_ERR_ARG;
+    if ((rc = check_pool(pool, false, rows, rows_b, c_b)) != SHPL_OK) return rc;
+    if (a_off < 0 || b_off < 0 || a_stride < a_off + c_a || (c_b > 0 && b_stride < b_off + c_b) || out_stride < c_out)
+        return SHPL_ERR_BAD_SHAPE;
+    const bool pooled = pool != nullptr;
+    const FwdLayout l = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled);
+    if (!d_ws) return SHPL_ERR_ARG;
+    if (ws_bytes < ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled)) return SHPL_ERR_WORKSPACE;
+    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
+    if (rows == 0) return SHPL_OK;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(d_ws);
+    const int64_t esz = esize(dtype), vec = 16 / esz;
+    const int64_t cs[2] = {c_a, c_b};
+
+    // the weights of both sources, packed per lane
+    for (int k = 0; k < 2; ++k) {
+        if (cs[k] == 0) continue;
+        const int64_t n = pack_steps(cs[k], (int)vec) * SUB * 64 * vec;
+        by_dtype(dtype, [&](auto tt) {
+            typedef typename decltype(tt)::T T;
+            hipLaunchKernelGGL(k_head_pack<T>, dim3(blocks_for(n, SHPL_BLOCK)), dim3(SHPL_BLOCK), 0, s,
+                               reinterpret_cast<const T *>(d_weights), k == 0 ? (int64_t)0 : c_a, cs[k], (int)c_out,
+                               reinterpret_cast<T *>(ws + l.wp[k]), n);
+            return SHPL_OK;
+        });
+        SHPL_LAUNCH_CHECK();
+    }
+    auto gemm = [&](const GemmArgs &g, bool al) {
+        const unsigned grid = blocks_for(g.rows, (int64_t)TILE_ROWS * GEMM_WAVES);
+        by_dtype(dtype, [&](auto tt) {
+            typedef typename decltype(tt)::T T;
+            if (al) {
+                hipLaunchKernelGGL((k_head_gemm<T, true>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
+            } else {
+                hipLaunchKernelGGL((k_head_gemm<T, false>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
+            }
+            return SHPL_OK;
+        });
+    };
+    const bool al_a = c_a % (SUB * 2 * vec) == 0 && rows_aligned(d_a, a_stride, a_off, c_a, vec, esz);
+    const bool al_b = c_b == 0 || (c_b % (SUB * 2 * vec) == 0 && rows_aligned(d_b, b_stride, b_off, c_b, vec, esz));
+    GemmArgs g = {};
+    g.c_out = (int)c_out;
+    if (pooled) {
+        // Z = b . W_b, no bias
+        g.s[0] = Src{d_b, b_stride, b_off, c_b, ws + l.wp[1]};
+        g.rows = rows_b;
+        g.out = ws + l.z;
+        g.to_z = 1;
+        if (rows_b > 0) {
+            gemm(g, al_b);
+            SHPL_LAUNCH_CHECK();
+        }
+        const int32_t *kr = pool->key_range;
+        if (!kr) {
+            SHPL_HIP_CHECK(zero_fill(ws + l.kr, align_up((size_t)rows * 8, 16), s));
+            if (pool->nnz_cap > 0) {
+                hipLaunchKernelGGL(k_head_ranges, dim3(blocks_for(pool->nnz_cap, SHPL_BLOCK)), dim3(SHPL_BLOCK), 0, s,
+                                   pool->ent_dst, pool->nnz_cap, rows, reinterpret_cast<int32_t *>(ws + l.kr));
+                SHPL_LAUNCH_CHECK();
+            }
+            kr = reinterpret_cast<const int32_t *>(ws + l.kr);
+        }
+        g = GemmArgs{};
+        g.c_out = (int)c_out;
+        g.s[0] = Src{d_a, a_stride, a_off, c_a, ws + l.wp[0]};
+        g.key_range = kr;
+        g.ent_src = pool->ent_src;
+        g.ent_val = pool->ent_val;
+        g.z = reinterpret_cast<const float *>(ws + l.z);
+        g.nnz_cap = pool->nnz_cap;
+        g.z_rows = rows_b;
+    } else {
+        g.s[0] = Src{d_a, a_stride, a_off, c_a, ws + l.wp[0]};
+        g.s[1] = Src{d_b, b_stride, b_off, c_b, ws + l.wp[1]};
+    }
+    g.rows = rows;
+    g.bias = d_bias;
+    g.out = d_out;
+    g.out_stride = out_stride;
+    gemm(g, al_a && (pooled || al_b));
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
+
+extern "C" int shpl_head1x1_dgrad(int dtype, int64_t rows, const void *d_gy, int64_t gy_stride, int64_t c_out,
+                                  const void *d_weights, int64_t c_a, int64_t c_b, void *d_da, int64_t da_stride,
+                                  void *d_db, int64_t db_stride, int64_t rows_b, const shpl_csr *pool_grad,
+                                  void *d_ws, size_t ws_bytes, void *stream) {
+    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
+    if (rc != SHPL_OK) return rc;
+    if (!d_gy || !d_weights || (!d_da && !d_db)) return SHPL_ERR_ARG;
+    if (d_db && c_b < 1) return SHPL_ERR_BAD_SHAPE;
+    if ((rc = check_pool(pool_grad, true, rows, rows_b, c_b)) != SHPL_OK) return rc;
+    if (gy_stride < c_out || (d_da && da_stride < c_a) || (d_db && db_stride < c_b)) return SHPL_ERR_BAD_SHAPE;
+    const bool pooled = pool_grad != nullptr;
+    const BwdLayout l = bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled, false);
+    if (!d_ws) return SHPL_ERR_ARG;
+    if (ws_bytes < ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled)) return SHPL_ERR_WORKSPACE;
+    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
+    if (rows == 0) return SHPL_OK;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(d_ws);
+    float *gp = reinterpret_cast<float *>(ws + l.gp), *gimg = reinterpret_cast<float *>(ws + l.gimg);
+    if ((rc = launch_gpad(dtype, d_gy, gy_stride, c_out, l.co, rows, gp, s)) != SHPL_OK) return rc;
+    const int64_t esz = esize(dtype);
+    auto run = [&](const float *g, int64_t n_rows, int64_t w_row0, int64_t c_n, void *dx, int64_t dx_stride) {
+        if (n_rows == 0) return;
+        const bool al = rows_aligned(dx, dx_stride, 0, c_n, COLS, esz);
+        const dim3 grid(blocks_for(n_rows, DGRAD_ROWS), blocks_for(c_n, 64 * COLS));
+        by_dtype(dtype, [&](auto tt) {
+            typedef typename decltype(tt)::T T;
+            return by_cols(l.co, [&](auto cc) {
+                constexpr int CO = decltype(cc)::value;
+                if (al) {
+                    hipLaunchKernelGGL((k_head_dgrad<T, CO, true>), grid, dim3(64), 0, s, g, n_rows, (int64_t)DGRAD_ROWS,
+                                       reinterpret_cast<const T *>(d_weights), w_row0, c_n, (int)c_out,
+                                       reinterpret_cast<T *>(dx), dx_stride);
+                } else {
+                    hipLaunchKernelGGL((k_head_dgrad<T, CO, false>), grid, dim3(64), 0, s, g, n_rows,
+                                       (int64_t)DGRAD_ROWS, reinterpret_cast<const T *>(d_weights), w_row0, c_n,
+                                       (int)c_out, reinterpret_cast<T *>(dx), dx_stride);
+                }
+                return SHPL_OK;
+            });
+        });
+    };
+    if (d_da) {
+        run(gp, rows, 0, c_a, d_da, da_stride);
+        SHPL_LAUNCH_CHECK();
+    }
+    if (d_db) {
+        const float *g = gp;
+        if (pooled) {
+            if (rows_b > 0 && (rc = pull_to_pixels(pool_grad, gp, l.co, gimg, s)) != SHPL_OK) return rc;
+            g = gimg;
+        }
+        run(g, pooled ? rows_b : rows, c_a, c_b, d_db, db_stride);
+        SHPL_LAUNCH_CHECK();
+    }
+    return SHPL_OK;
+}
+
+extern "C" int shpl_head1x1_wgrad(int dtype, int64_t rows, const void *d_a, int64_t a_stride, int64_t a_off,
+                                  int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b,
+                                  int64_t rows_b, const shpl_csr *pool_grad, const void *d_gy, int64_t gy_stride,
+                                  int64_t c_out, float *d_dw, float *d_dbias, void *d_ws, size_t ws_bytes,
+                                  void *stream) {
+    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
+    if (rc != SHPL_OK) return rc;
+    if (!d_a || !d_gy || !d_dw || (c_b > 0 && !d_b)) return SHPL_ERR_ARG;
+    if ((rc = check_pool(pool_grad, true, rows, rows_b, c_b)) != SHPL_OK) return rc;
+    if (a_off < 0 || b_off < 0 || a_stride < a_off + c_a || (c_b > 0 && b_stride < b_off + c_b) || gy_stride < c_out)
+        return SHPL_ERR_BAD_SHAPE;
+    const bool pooled = pool_grad != nullptr;
+    const BwdLayout l = bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled, true);
+    if (!d_ws) return SHPL_ERR_ARG;
+    if (ws_bytes < l.bytes) return SHPL_ERR_WORKSPACE;
+    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(d_ws);
+    float *gp = reinterpret_cast<float *>(ws + l.gp), *gimg = reinterpret_cast<float *>(ws + l.gimg);
+    if ((rc = launch_gpad(dtype, d_gy, gy_stride, c_out, l.co, rows, gp, s)) != SHPL_OK) return rc;
+    if (pooled && rows > 0 && rows_b > 0 && (rc = pull_to_pixels(pool_grad, gp, l.co, gimg, s)) != SHPL_OK) return rc;
+    const int64_t esz = esize(dtype);
+    // one source: its partials, then their sum into rows [w_row0, w_row0 + c_n) of dw (and the bias gradient)
+    auto run = [&](int k, const void *x, int64_t x_stride, int64_t x_off, int64_t c_n, const float *g, int64_t n_rows,
+                   int64_t w_row0, bool bias) {
+        float *part = reinterpret_cast<float *>(ws + l.part[k]);
+        int64_t per = (n_rows + WGRAD_MAX_CHUNKS - 1) / WGRAD_MAX_CHUNKS;
+        if (per < WGRAD_MIN_ROWS) per = WGRAD_MIN_ROWS;
+        const int64_t chunks = (n_rows + per - 1) / per;  // <= l.chunks[k]; 0 rows: no partial, zeros
+        if (chunks > 0) {
+            const bool al = rows_aligned(x, x_stride, x_off, c_n, COLS, esz);
+            const dim3 grid((unsigned)chunks, blocks_for(c_n, 64 * COLS));
+            by_dtype(dtype, [&](auto tt) {
+                typedef typename decltype(tt)::T T;
+                return by_cols(l.co, [&](auto cc) {
+                    constexpr int CO = decltype(cc)::value;
+                    if (al) {
+                        hipLaunchKernelGGL((k_head_wgrad<T, CO, true>), grid, dim3(WGRAD_WAVES * 64), 0, s,
+                                           reinterpret_cast<const T *>(x), x_stride, x_off, c_n, g, n_rows, per,
+                                           (int)bias, part);
+                    } else {
+                        hipLaunchKernelGGL((k_head_wgrad<T, CO, false>), grid, dim3(WGRAD_WAVES * 64), 0, s,
+                                           reinterpret_cast<const T *>(x), x_stride, x_off, c_n, g, n_rows, per,
+                                           (int)bias, part);
+                    }
+                    return SHPL_OK;
+                });
+            });
+        }
+        const int64_t n = (c_n + (bias ? 1 : 0)) * c_out;
+        hipLaunchKernelGGL(k_head_wreduce, dim3(blocks_for(n, 32)), dim3(SHPL_BLOCK), 0, s, part, chunks, c_n,
+                           l.co, (int)c_out, (int)bias, d_dw, w_row0, d_dbias);
+    };
+    run(0, d_a, a_stride, a_off, c_a, gp, rows, 0, d_dbias != nullptr);
+    SHPL_LAUNCH_CHECK();
+    if (c_b > 0) {
+        run(1, d_b, b_stride, b_off, c_b, pooled ? gimg : gp, pooled ? rows_b : rows, c_a, false);
+        SHPL_LAUNCH_CHECK();
+    }
+    return SHPL_OK;
+}
