@@ -696,6 +696,47 @@ int shpl_conv3x3_wgrad_reuse(int dtype, int n_frames, int64_t h, int64_t w, cons
                              const void *d_fwd_ws, size_t fwd_ws_bytes, int fwd_stats, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * After-VGG upconv3: 3x3 stride-2 transposed conv over the fused conv4 map
+ * ------------------------------------------------------------------------- */
+
+/* TF's conv2d_transpose, SAME, stride 2, 3x3, over n_frames frames of h x w input pixels, 2h x 2w output pixels:
+ *   out[f,oy,ox,co] = epilogue( sum over (i,ky): 2i+ky = oy, (j,kx): 2j+kx = ox, ci of
+ *                               x[f,i,j,ci] * W[ky,kx,co,ci] ),   0 <= i < h, 0 <= j < w, ky, kx in 0..2
+ * -- the input gradient of the SAME stride-2 conv over 2h x 2w, whose padding is pad_total = 1, pad_before =
+ * pad_total // 2 = 0, pad_after = 1 (TF's conv2d_backprop_input). Even oy = 2i takes ky = 0 from row i and ky = 2
+ * from row i-1, odd oy = 2i+1 takes ky = 1 from row i; columns alike: every output pixel reads the window
+ * x[i-1..i, j-1..j] (zeros outside), 9 c_in c_out multiply-adds per input pixel. In torch terms:
+ * conv_transpose2d(x_nchw, W.permute(3,2,0,1), stride=2)[..., :2h, :2w].
+ * x = [a || b] exactly as shpl_conv3x3 takes its sources: channels [0, c_a) row r of d_a (r the input pixel
+ * (f*h + i)*w + j), channels [c_a, c_a + c_b) row r of d_b (pool NULL: a second dense map; c_b = 0: none), or
+ * the pooled map computed in the staging from the pool's CSR over d_b -- cell-keyed (shpl_build_csr
+ * SHPL_BY_CELL, SHPL_ORDER_ENTRY: a the BEV map, b the image map) or pixel-keyed (SHPL_BY_PIXEL,
+ * SHPL_ORDER_COL_ROW, with ent_col or flagged SHPL_CSR_IDENTITY_COLS: a the image map, b the BEV map; per-column
+ * partial sums first under ent_col), n_keys = n_frames*h*w, entry slots of frame f from d_frame_off[f] on, with
+ * shpl_pull's arithmetic: when c_a is a multiple of the staging chunk (8 f32 / 16 bf16 channels) the pooled
+ * call gives bitwise the result of the same call with d_b = the dense map shpl_pull writes (the pooled values
+ * are formed in the pull's order and rounded to the storage dtype once, before the MFMA).
+ * d_weights: slim's conv2d_transpose variable [3][3][c_out][c_a+c_b] ("HWOI") in the feature dtype.
+ * Output rows are NHWC with global id (f*2h + oy)*2w + ox, out_stride elements apart. Everything else is
+ * shpl_conv3x3's contract: the epilogue (acc - center) * scale + shift with one rounding and ReLU on the bit
+ * pattern; d_stats (optional, [2][c_out] f64) = per-channel sum and sum of squares of the pre-epilogue output
+ * over all n_frames*2h*2w rows, deterministic, as shpl_batch_norm takes it; the argument checks, their status
+ * codes and order; stream-ordered, no allocation, no host synchronisation (capturable). f32:
+ * v_mfma_f32_32x32x2_f32 (exact f32 products); SHPL_BF16: v_mfma_f32_32x32x16_bf16; f32 accumulation, one
+ * rounding at the store. One input tile is staged once and feeds the accumulators of all four output parities.
+ * Workspace: shpl_upconv3x3_workspace_bytes, pool_nnz_cap = pool->nnz_cap for a pooled call, -1 without a pool.
+ * Replaces: sparse_pool_layer over conv4 (avod/avod/core/feature_extractors/fusion_vgg_pyramid.py:53-60)
+ *   followed by slim.conv2d_transpose(conv4, vgg_conv3[1], [3,3], stride=2, normalizer_fn=slim.batch_norm)
+ *   (fusion_vgg_pyramid.py:198-206, scope upconv3), both sides. */
+int shpl_upconv3x3_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b,
+                                   int64_t c_out, int64_t pool_nnz_cap, int stats, size_t *bytes);
+int shpl_upconv3x3(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
+                   int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b,
+                   const shpl_csr *pool, const int64_t *d_frame_off, const void *d_weights /* HWOI */,
+                   int64_t c_out, const float *d_center, const float *d_scale, const float *d_shift, int act,
+                   void *d_out, int64_t out_stride, double *d_stats, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * 1x1 heads over the fused map, the SHPL applied after the projection
  * (MV3D's rpn_cls_score / rpn_bbox_pred)
  * ------------------------------------------------------------------------- */
