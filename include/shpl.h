@@ -798,6 +798,87 @@ int shpl_head1x1_wgrad(int dtype, int64_t rows, const void *d_a, int64_t a_strid
                        const shpl_csr *pool_grad, const void *d_gy, int64_t gy_stride, int64_t c_out, float *d_dw,
                        float *d_dbias, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * The same heads under dropout over conv_lidar_fused (MV3D's training step)
+ * ------------------------------------------------------------------------- */
+
+/* The dropout mask: a pure function of (seed, row, channel, keep_prob) -- no state, no stored tensor.
+ *   T = clamp(floor(keep_prob * 65536 + 0.5), 1, 65536) in double; keep_prob outside (0, 1] (NaN included) is
+ *   SHPL_ERR_ARG. The effective keep probability is T / 65536 and scale = (float)(65536.0 / T) (exact for 0.5);
+ *   keep_prob = 1 gives T = 65536: everything kept, scale 1.
+ *   For row r (the global row of the call: the BEV cell over all frames, int64) and concat channel c in
+ *   [0, c_a + c_b) (the channels of `a` first, then the second source's): g = c >> 3, j = c & 7,
+ *     (w0..w3) = Philox4x32-10(counter (r & 0xffffffff, r >> 32, g, 0), key (seed & 0xffffffff, seed >> 32)),
+ *     h = (w[j >> 1] >> (16 * (j & 1))) & 0xffff, and the element is KEPT iff h < T.
+ *   One Philox call covers 8 consecutive channels (one 16-byte bf16 piece, two f32 pieces).
+ *   Philox4x32-10 is Random123's: multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments 0x9E3779B9,
+ *   0xBB67AE85 after each round, ten rounds of
+ *     (c0, c1, c2, c3) <- (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)).
+ *   Known answer: counter 0,0,0,0 key 0,0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ * TF's tf.nn.dropout stream cannot be reproduced and nothing here tries to: parity with the reference is
+ * distributional, iid Bernoulli(T / 65536) per element of the [rows, c_a + c_b] map. TF forms
+ * (x / keep_prob) * mask before the conv; here the scale multiplies the f32 channel sum, which differs only by
+ * where the scale is rounded (identical at 0.5). `seed` is a host scalar passed by value: a captured graph
+ * replays the same mask (a device-side seed is not offered).
+ *
+ * shpl_dropout_mask writes the mask as an array, d_mask u8 [rows][c] (1 kept, 0 dropped) -- for checks and for
+ * callers that need it elsewhere; the head calls below never read or write one. */
+int shpl_dropout_mask(int64_t rows, int64_t c, double keep_prob, uint64_t seed, uint8_t *d_mask, void *stream);
+
+/* shpl_head1x1 under that mask: with x[r, c] = a[r, c] for c < c_a and x[r, c_a + c] = the second source's
+ * channel c (pool == NULL: row r of d_b, or no second source with c_b = 0, the one-map form over a materialised
+ * drop_fused's input; pool != NULL: the img->BEV pooled value through the cell-keyed CSR),
+ *     out[r, co] = scale * sum_c keep(r, c) * x[r, c] * W[c, co] + bias[co].
+ * The mask sits between the pooling and the projection, so the projection cannot move before the pooling as
+ * in shpl_head1x1; the pooling moves into the GEMM's operand staging instead. The pooled value is the f32 run
+ * sum of cell r in CSR order from zero, one multiply and one add per entry (no FMA contraction), exactly as
+ * shpl_pull(SHPL_BY_CELL) sums it, rounded once to the feature dtype: the MFMA operand is bit-equal to the
+ * element of the materialised bv_fused. The channel sum is an f32 MFMA sum (the channels of `a`, then the
+ * second source's; n = c_a + c_b terms); then one f32 multiply by scale, one add of the bias and one rounding
+ * at the store. The result equals the heads of dropout([a || shpl_pull(...)]) with this mask up to the order
+ * of the channel sum -- not bitwise. Neither the pooled map, the concat nor a mask is written anywhere: the
+ * workspace (shpl_head1x1_drop_workspace_bytes, which also covers shpl_head1x1_drop_dgrad) holds the packed
+ * weights, the f32 padded copy of gy and key ranges for a CSR that carries none -- nothing proportional to
+ * rows * c_b, rows * (c_a + c_b) or nnz * c_b. Arguments and errors as shpl_head1x1, plus the keep_prob range.
+ * Replaces: sparse_pool, the concat, dropout and the two 1x1 convs of
+ *   MV3D_TF_release/lib/networks/MV3D_voxel_train.py:144-178 with use_dropout (keep_prob 0.5 in training). */
+int shpl_head1x1_drop_workspace_bytes(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b,
+                                      int64_t c_out, int pooled, size_t *bytes);
+int shpl_head1x1_drop(int dtype, int64_t rows, const void *d_a, int64_t a_stride, int64_t a_off, int64_t c_a,
+                      const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, int64_t rows_b,
+                      const shpl_csr *pool, const void *d_weights, int64_t c_out, const float *d_bias, void *d_out,
+                      int64_t out_stride, double keep_prob, uint64_t seed, void *d_ws, size_t ws_bytes,
+                      void *stream);
+
+/* Input gradients of shpl_head1x1_drop, the autodiff of its expression with the mask computed again:
+ *     d_da[r, c] = keep(r, c) * scale * sum_co gy[r, co] * W[c, co]      (exactly 0 where dropped)
+ *     d_db[p, c] = sum over the entries k = (cell r_k, m_k) of pixel p's run of pool_grad, in CSR order from zero,
+ *                  of m_k * (keep(r_k, c_a + c) * scale * sum_co gy[r_k, co] * W[c_a + c, co])
+ * (pool_grad: the pixel-keyed CSR shpl_head1x1_dgrad takes, a cell-keyed one is SHPL_ERR_ARG; NULL: d_db as
+ * d_da over the dense second source). The sums over co are f32 fused multiply-adds in co order (c_out terms),
+ * then one multiply by scale; per kept entry one multiply by m_k and one add (a dropped entry adds nothing; no
+ * per-column partials); one rounding at the store. Either output may be NULL. */
+int shpl_head1x1_drop_dgrad(int dtype, int64_t rows, const void *d_gy, int64_t gy_stride, int64_t c_out,
+                            const void *d_weights, int64_t c_a, int64_t c_b, void *d_da, int64_t da_stride,
+                            void *d_db, int64_t db_stride, int64_t rows_b, const shpl_csr *pool_grad,
+                            double keep_prob, uint64_t seed, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Weight and bias gradients of shpl_head1x1_drop: d_dw f32 [c_a + c_b][c_out],
+ *     dw[c, co] = scale * sum_r keep(r, c) * x[r, c] * gy[r, co],       d_dbias[co] = sum_r gy[r, co]
+ * with both halves summed over the cells r. `pool` is the forward's CELL-keyed CSR (a pixel-keyed one is
+ * SHPL_ERR_ARG): x[r, c_a + c] is formed again as the forward forms it, the run sum of cell r rounded once to
+ * the feature dtype. Two stages: per-row-chunk f32 partials (rows ascending, fused multiply-adds, eight waves'
+ * sums added in a fixed order, then one multiply by scale) in the workspace, at most 64 chunks, then the
+ * partials summed in chunk order in f64 and rounded once -- no floating-point atomics, bitwise the same from
+ * run to run. Workspace: shpl_head1x1_drop_wgrad_workspace_bytes (partials and key ranges only). */
+int shpl_head1x1_drop_wgrad_workspace_bytes(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b,
+                                            int64_t c_out, int pooled, size_t *bytes);
+int shpl_head1x1_drop_wgrad(int dtype, int64_t rows, const void *d_a, int64_t a_stride, int64_t a_off, int64_t c_a,
+                            const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, int64_t rows_b,
+                            const shpl_csr *pool, const void *d_gy, int64_t gy_stride, int64_t c_out, float *d_dw,
+                            float *d_dbias, double keep_prob, uint64_t seed, void *d_ws, size_t ws_bytes,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

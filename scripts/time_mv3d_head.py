@@ -13,7 +13,20 @@ line per (dtype, step, form): every repeat's time, their median and spread, the 
 ((R c_lidar + P c_img) e + R c_out e + P c_out 4 + nnz 12) with its share of an 8 TB/s floor, the largest
 difference from the fused form's output, and the library's hash. SHPL_LIB selects a variant build.
 
-    python scripts/time_mv3d_head.py [--frames 8] [--reps 10] [--dtypes bf16,f32]
+With --keep-prob P (absent: the three forms above and nothing else) the heads under dropout over the concat, as
+MV3D trains them, are timed instead, again alternated in one process:
+
+  fused_dropout          FusionHead.fused_dropout: pooling, mask and heads in one GEMM (no pooled map, concat or mask);
+  unfused_dropout        shpl_map.pool_op, torch.cat, then FusionHead.dropout over the materialised map;
+  unfused_torch_dropout  the same pooling and concat, torch.nn.functional.dropout, one matmul + bias: nothing of
+                         the dropout kernels at all (the form the code before them could run);
+  fused                  FusionHead.fused at keep 1: what the staging and the generator cost beside it.
+
+The byte model of fused_dropout's forward is (R c_lidar + nnz c_img) e + R c_out e + nnz 12: the image rows are
+gathered per entry, not streamed once per pixel. The largest difference is taken from fused_dropout's output
+for the two forms that share its mask.
+
+    python scripts/time_mv3d_head.py [--frames 8] [--reps 10] [--dtypes bf16,f32] [--keep-prob 0.5]
 """
 import argparse
 import hashlib
@@ -42,6 +55,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtypes", default="bf16,f32")
+    ap.add_argument("--keep-prob", type=float, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_mv3d_head.py measures on the GPU; none found")
@@ -97,11 +111,32 @@ def main():
                     return fn()
             return step
 
-        base = {"fused": fused, "unfused": unfused, "unfused_torch": unfused_torch}
+        kp, seed = args.keep_prob, 20261
+
+        def fused_dropout():
+            return head.fused_dropout(lidar, img, smap, kp, seed=seed)
+
+        def unfused_dropout():
+            return head.dropout(concat(), kp, seed=seed)
+
+        def unfused_torch_dropout():
+            x = torch.nn.functional.dropout(concat(), p=1.0 - kp, training=True)
+            return tuple(torch.matmul(x, w.reshape(cl + ci, n)) + b.to(dtype)
+                         for w, b, n in zip(head.weights, head.biases, HEADS))
+
+        if kp is None:
+            base = {"fused": fused, "unfused": unfused, "unfused_torch": unfused_torch}
+            first, same_mask = "fused", set(base)
+            model = (R * cl + Pn * ci) * esz + R * co * esz + Pn * co * 4 + nnz * 12
+        else:
+            base = {"fused_dropout": fused_dropout, "unfused_dropout": unfused_dropout,
+                    "unfused_torch_dropout": unfused_torch_dropout, "fused": fused}
+            first, same_mask = "fused_dropout", {"fused_dropout", "unfused_dropout"}
+            model = (R * cl + nnz * ci) * esz + R * co * esz + nnz * 12
         with torch.no_grad():
-            ref = torch.cat(fused(), -1).float()
-            diff = {k: float((torch.cat(fn(), -1).float() - ref).abs().max().item()) for k, fn in base.items()}
-        model = (R * cl + Pn * ci) * esz + R * co * esz + Pn * co * 4 + nnz * 12
+            ref = torch.cat(base[first](), -1).float()
+            diff = {k: float((torch.cat(fn(), -1).float() - ref).abs().max().item()) if k in same_mask else None
+                    for k, fn in base.items()}
         for step, wrap in (("forward", inference), ("train", train)):
             forms = {k: wrap(fn) for k, fn in base.items()}
             for _ in range(args.warmup):
@@ -122,12 +157,14 @@ def main():
                 rec = {"step": "mv3d_head_" + step, "form": k, "dtype": name, "frames": F, "bev": [Hb, Wb],
                        "image": [Hi, Wi], "channels": f"{cl}+{ci}->{'+'.join(str(n) for n in HEADS)}", "nnz": nnz,
                        "ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
-                       "ms": [round(v, 4) for v in ms], "max_abs_diff_from_fused": diff[k], "lib_sha256": sha,
+                       "ms": [round(v, 4) for v in ms], "max_abs_diff_from_" + first: diff[k], "lib_sha256": sha,
                        "lib": os.environ.get("SHPL_LIB", "default")}
+                if kp is not None:
+                    rec["keep_prob"] = kp
                 if step == "forward":
-                    rec["fused_model_bytes"] = model
-                    rec["fused_model_ms_at_8TBps"] = round(model / 8e12 * 1e3, 4)
-                    if k == "fused":
+                    rec[first + "_model_bytes"] = model
+                    rec[first + "_model_ms_at_8TBps"] = round(model / 8e12 * 1e3, 4)
+                    if k == first:
                         rec["fraction_of_8TBps_floor"] = round(model / 8e12 * 1e3 / med, 4)
                 print(json.dumps(rec), flush=True)
         del lidar, img, head, params, gy

@@ -126,7 +126,7 @@ def pull_desc(dtype, src, src_stride, src_off, c_pool, pass_, pass_stride, pass_
 
 def _declare(lib):
     p, i32, i64, d, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_size_t
-    psz = ctypes.POINTER(ctypes.c_size_t)
+    psz, u64 = ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint64
     pull_args = [i32, i32, ctypes.POINTER(ShplCsr), p, i64, i64, i64, p, i64, i64, i64, i32, p, i64, p]
     sig = {
         "shpl_version": (ctypes.c_char_p, []),
@@ -196,6 +196,15 @@ def _declare(lib):
         "shpl_head1x1_wgrad_workspace_bytes": (i32, [i32, i64, i64, i64, i64, i64, i32, psz]),
         "shpl_head1x1_wgrad": (i32, [i32, i64, p, i64, i64, i64, p, i64, i64, i64, i64, ctypes.POINTER(ShplCsr), p,
                                      i64, i64, p, p, p, sz, p]),
+        "shpl_dropout_mask": (i32, [i64, i64, d, u64, p, p]),
+        "shpl_head1x1_drop_workspace_bytes": (i32, [i32, i64, i64, i64, i64, i64, i32, psz]),
+        "shpl_head1x1_drop": (i32, [i32, i64, p, i64, i64, i64, p, i64, i64, i64, i64, ctypes.POINTER(ShplCsr), p,
+                                    i64, p, p, i64, d, u64, p, sz, p]),
+        "shpl_head1x1_drop_dgrad": (i32, [i32, i64, p, i64, i64, p, i64, i64, p, i64, p, i64, i64,
+                                          ctypes.POINTER(ShplCsr), d, u64, p, sz, p]),
+        "shpl_head1x1_drop_wgrad_workspace_bytes": (i32, [i32, i64, i64, i64, i64, i64, i32, psz]),
+        "shpl_head1x1_drop_wgrad": (i32, [i32, i64, p, i64, i64, i64, p, i64, i64, i64, i64, ctypes.POINTER(ShplCsr),
+                                          p, i64, i64, p, p, d, u64, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

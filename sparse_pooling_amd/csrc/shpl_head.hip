@@ -11,40 +11,13 @@
 // f32 copies of the gradient padded to a multiple of 4 columns so that the pulls and the row loads are whole
 // 16-byte pieces. The weight gradient is two-stage: per-row-chunk partials in the workspace, summed in chunk
 // order -- no floating-point atomics.
-#include "shpl_common.h"
+#include "shpl_head.h"
 
 namespace shpl {
 namespace head {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int NP = 32;        // output columns of a GEMM tile: c_out padded
-constexpr int TILE_ROWS = 32; // rows of a GEMM tile (one wave)
-constexpr int GEMM_WAVES = 4; // waves per GEMM workgroup
-constexpr int SUB = 4;        // 16-byte pieces per lane and K step: 64 contiguous bytes of its row
-constexpr int COLS = 4;       // channels per thread of the backward kernels
-constexpr int DGRAD_ROWS = 128;  // rows per wave of the input gradient
 constexpr int WGRAD_MIN_ROWS = 64, WGRAD_MAX_CHUNKS = 256;  // the weight gradient's row chunks (its partials)
 constexpr int WGRAD_WAVES = 4;  // waves per chunk, a quarter of its rows each
-
-template <typename T>
-struct Vec;  // elements of one 16-byte piece
-template <>
-struct Vec<float> {
-    static constexpr int N = 4;
-};
-template <>
-struct Vec<uint16_t> {
-    static constexpr int N = 8;
-};
-
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(uint16_t v) { return bf16_to_f32(v); }
-__device__ __forceinline__ void from_f32(float v, float *o) { *o = v; }
-__device__ __forceinline__ void from_f32(float v, uint16_t *o) { *o = f32_to_bf16(v); }
 
 // ---------------------------------------------------------------- weights, packed per lane
 // K is walked in steps of SUB * 2 * VEC channels: lane (n = lane % 32, h = lane / 32) holds channels
@@ -67,8 +40,6 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_head_pack(const T *__restrict__ 
     wp[t] = v;
 }
 
-inline int64_t pack_steps(int64_t c, int vec) { return (c + SUB * 2 * vec - 1) / (SUB * 2 * vec); }
-
 struct Src {
     const void *x;
     int64_t stride, off, c;
@@ -88,18 +59,6 @@ struct GemmArgs {
     int64_t out_stride;
     int to_z;
 };
-
-__device__ __forceinline__ f32x16 mma(const float (&x)[4], const float (&w)[4], f32x16 acc) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[i], w[i], acc, 0, 0, 0);
-    return acc;
-}
-__device__ __forceinline__ f32x16 mma(const uint16_t (&x)[8], const uint16_t (&w)[8], f32x16 acc) {
-    bf16x8 xa, wb;
-    __builtin_memcpy(&xa, x, 16);
-    __builtin_memcpy(&wb, w, 16);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa, wb, acc, 0, 0, 0);
-}
 
 // acc += row rl of one source times its packed weights (a source of no channels: nothing). Two register stages:
 // the loads of the next K step are issued before the MFMAs of the current one.
@@ -389,16 +348,6 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_head_wreduce(const float *__rest
 }
 
 // ---------------------------------------------------------------- host side
-inline int pad_cols(int64_t c_out) { return (int)((c_out + 3) / 4 * 4); }  // whole 16-byte pieces of f32
-inline int64_t esize(int dtype) { return dtype == SHPL_F32 ? 4 : 2; }
-
-inline bool pixel_keyed(const shpl_csr *p) { return p->ent_col || (p->flags & SHPL_CSR_IDENTITY_COLS); }
-
-// rows of source `x` in pieces of `vec` elements: whole pieces, each on its own alignment
-inline bool rows_aligned(const void *x, int64_t stride, int64_t off, int64_t c, int64_t vec, int64_t esz) {
-    return c % vec == 0 && stride % vec == 0 && off % vec == 0 && ((uintptr_t)x % (size_t)(vec * esz)) == 0;
-}
-
 struct FwdLayout {
     size_t wp[2], z, kr, bytes;
 };
@@ -455,46 +404,37 @@ inline size_t ws_need(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int6
     return f > b ? f : b;
 }
 
-// The checks every entry point shares: dtype, channel counts, rows; then the second source's form.
-inline int check_shape(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out) {
-    if (dtype != SHPL_F32 && dtype != SHPL_BF16) return SHPL_ERR_ARG;
-    if (c_out < 1 || c_out > NP) return SHPL_ERR_BAD_SHAPE;
-    const int64_t lim = (int64_t)1 << 31;
-    if (rows < 0 || rows >= lim || rows_b < 0 || rows_b >= lim) return SHPL_ERR_BAD_SHAPE;
-    if (c_a < 1 || c_b < 0 || c_a >= (1 << 22) || c_b >= (1 << 22)) return SHPL_ERR_BAD_SHAPE;  // grid.y, 32-bit rows
+int launch_pack(int dtype, const void *d_weights, int64_t w_row0, int64_t c, int64_t c_out, void *wp, hipStream_t s) {
+    const int64_t vec = 16 / esize(dtype), n = pack_steps(c, (int)vec) * SUB * 64 * vec;
+    if (n == 0) return SHPL_OK;
+    by_dtype(dtype, [&](auto tt) {
+        typedef typename decltype(tt)::T T;
+        hipLaunchKernelGGL(k_head_pack<T>, dim3(blocks_for(n, SHPL_BLOCK)), dim3(SHPL_BLOCK), 0, s,
+                           reinterpret_cast<const T *>(d_weights), w_row0, c, (int)c_out, reinterpret_cast<T *>(wp), n);
+        return SHPL_OK;
+    });
+    SHPL_LAUNCH_CHECK();
     return SHPL_OK;
 }
 
-// pool: the CSR of the pooled form (NULL: dense b); want_pixel: the gradient's pixel-keyed list.
-inline int check_pool(const shpl_csr *pool, bool want_pixel, int64_t rows, int64_t rows_b, int64_t c_b) {
-    if (!pool) return (c_b > 0 && rows_b != rows) ? SHPL_ERR_BAD_SHAPE : SHPL_OK;
-    if (c_b < 1) return SHPL_ERR_BAD_SHAPE;
-    if (pixel_keyed(pool) != want_pixel) return SHPL_ERR_ARG;
-    if (pool->n_keys != (want_pixel ? rows_b : rows)) return SHPL_ERR_BAD_SHAPE;
-    if (pool->nnz_cap < 0 || pool->nnz_cap >= ((int64_t)1 << 31)) return SHPL_ERR_BAD_SHAPE;
-    if (pool->nnz_cap > 0 && (!pool->ent_dst || !pool->ent_src || !pool->ent_val)) return SHPL_ERR_ARG;
-    return SHPL_OK;
-}
-
-template <typename F>
-int by_dtype(int dtype, F &&fn) {
-    return dtype == SHPL_F32 ? fn(TypeOf<float>()) : fn(TypeOf<uint16_t>());
-}
-template <typename F>
-int by_cols(int co, F &&fn) {
-    switch (co) {
-        case 4: return fn(std::integral_constant<int, 4>());
-        case 8: return fn(std::integral_constant<int, 8>());
-        case 12: return fn(std::integral_constant<int, 12>());
-        case 16: return fn(std::integral_constant<int, 16>());
-        case 20: return fn(std::integral_constant<int, 20>());
-        case 24: return fn(std::integral_constant<int, 24>());
-        case 28: return fn(std::integral_constant<int, 28>());
-        default: return fn(std::integral_constant<int, 32>());
+int launch_ranges(const shpl_csr *csr, int64_t n_keys, int32_t *kr, hipStream_t s) {
+    SHPL_HIP_CHECK(zero_fill(kr, align_up((size_t)n_keys * 8, 16), s));
+    if (csr->nnz_cap > 0) {
+        hipLaunchKernelGGL(k_head_ranges, dim3(blocks_for(csr->nnz_cap, SHPL_BLOCK)), dim3(SHPL_BLOCK), 0, s,
+                           csr->ent_dst, csr->nnz_cap, n_keys, kr);
+        SHPL_LAUNCH_CHECK();
     }
+    return SHPL_OK;
 }
 
-inline unsigned blocks_for(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
+int launch_wreduce(const float *part, int64_t chunks, int64_t c_n, int co, int64_t c_out, bool with_bias, float *dw,
+                   int64_t w_row0, float *dbias, hipStream_t s) {
+    const int64_t n = (c_n + (with_bias ? 1 : 0)) * c_out;
+    hipLaunchKernelGGL(k_head_wreduce, dim3(blocks_for(n, 32)), dim3(SHPL_BLOCK), 0, s, part, chunks, c_n, co,
+                       (int)c_out, (int)with_bias, dw, w_row0, dbias);
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
 
 // g (feature dtype) -> gp f32 [rows][co]
 int launch_gpad(int dtype, const void *d_gy, int64_t gy_stride, int64_t c_out, int co, int64_t rows, float *gp,
@@ -562,18 +502,9 @@ extern "C" int shpl_head1x1(int dtype, int64_t rows, const void *d_a, int64_t a_
     const int64_t cs[2] = {c_a, c_b};
 
     // the weights of both sources, packed per lane
-    for (int k = 0; k < 2; ++k) {
-        if (cs[k] == 0) continue;
-        const int64_t n = pack_steps(cs[k], (int)vec) * SUB * 64 * vec;
-        by_dtype(dtype, [&](auto tt) {
-            typedef typename decltype(tt)::T T;
-            hipLaunchKernelGGL(k_head_pack<T>, dim3(blocks_for(n, SHPL_BLOCK)), dim3(SHPL_BLOCK), 0, s,
-                               reinterpret_cast<const T *>(d_weights), k == 0 ? (int64_t)0 : c_a, cs[k], (int)c_out,
-                               reinterpret_cast<T *>(ws + l.wp[k]), n);
-            return SHPL_OK;
-        });
-        SHPL_LAUNCH_CHECK();
-    }
+    for (int k = 0; k < 2; ++k)
+        if ((rc = launch_pack(dtype, d_weights, k == 0 ? (int64_t)0 : c_a, cs[k], c_out, ws + l.wp[k], s)) != SHPL_OK)
+            return rc;
     auto gemm = [&](const GemmArgs &g, bool al) {
         const unsigned grid = blocks_for(g.rows, (int64_t)TILE_ROWS * GEMM_WAVES);
         by_dtype(dtype, [&](auto tt) {
@@ -602,13 +533,8 @@ extern "C" int shpl_head1x1(int dtype, int64_t rows, const void *d_a, int64_t a_
         }
         const int32_t *kr = pool->key_range;
         if (!kr) {
-            SHPL_HIP_CHECK(zero_fill(ws + l.kr, align_up((size_t)rows * 8, 16), s));
-            if (pool->nnz_cap > 0) {
-                hipLaunchKernelGGL(k_head_ranges, dim3(blocks_for(pool->nnz_cap, SHPL_BLOCK)), dim3(SHPL_BLOCK), 0, s,
-                                   pool->ent_dst, pool->nnz_cap, rows, reinterpret_cast<int32_t *>(ws + l.kr));
-                SHPL_LAUNCH_CHECK();
-            }
-            kr = reinterpret_cast<const int32_t *>(ws + l.kr);
+            if ((rc = launch_ranges(pool, rows, reinterpret_cast<int32_t *>(ws + l.kr), s)) != SHPL_OK) return rc;
+            kr =reinterpret_cast<const int32_t *>(ws + l.kr);
         }
         g = GemmArgs{};
         g.c_out = (int)c_out;
@@ -739,9 +665,7 @@ extern "C" int shpl_head1x1_wgrad(int dtype, int64_t rows, const void *d_a, int6
                 });
             });
         }
-        const int64_t n = (c_n + (bias ? 1 : 0)) * c_out;
-        hipLaunchKernelGGL(k_head_wreduce, dim3(blocks_for(n, 32)), dim3(SHPL_BLOCK), 0, s, part, chunks, c_n,
-                           l.co, (int)c_out, (int)bias, d_dw, w_row0, d_dbias);
+        launch_wreduce(part, chunks, c_n, l.co, c_out, bias, d_dw, w_row0, d_dbias, s);
     };
     run(0, d_a, a_stride, a_off, c_a, gp, rows, 0, d_dbias != nullptr);
     SHPL_LAUNCH_CHECK();
