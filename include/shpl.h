@@ -411,6 +411,16 @@ int shpl_pull_sparse(int direction, int dtype, const shpl_csr *csr, const void *
 int shpl_pull_once(int direction, int dtype, const shpl_csr *csr, const void *d_src, int64_t src_stride,
                    int64_t src_off, int64_t c_pool, const void *d_pass, int64_t pass_stride, int64_t pass_off,
                    int64_t c_pass, int mode, void *d_out, int64_t out_stride, void *stream);
+/* Zeros (+0, k_dense's bits) into the pooled columns out[d*out_stride + out_off + c], c < c_pool, of every
+ * destination d that has an entry in csr -- the rows shpl_pull_sparse over the same CSR wrote -- and nothing
+ * else: ONE launch over the capacity, a thread per (sorted entry, 16-byte chunk), the thread on a run's first
+ * entry stores; it reads ent_dst only, and a destination outside [0, n_keys) is never stored to. For an output
+ * whose pooled columns are kept zero between steps: cleared here at the previous step's cells (call it before
+ * the CSR is rebuilt) they are all zero again, and the next shpl_pull_sparse over the new CSR gives the whole
+ * pooled half with no k_dense zeros. 16-byte chunks when c_pool, out_stride, out_off and d_out allow them
+ * (shpl_pull's rule), else one element per thread. No frame-layout (live entries) form. */
+int shpl_pull_clear(int dtype, const shpl_csr *csr, int64_t c_pool, void *d_out, int64_t out_stride,
+                    int64_t out_off, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Bucketed pulls: the index build hands the pulls M already cut by

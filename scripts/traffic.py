@@ -21,7 +21,7 @@ SHORT = (("k_conv_wide", "k_conv_wide"), ("k_pool_runs_wide", "k_pool_runs_wide"
          ("k_conv3x3<float, true", "k_conv3x3_pooled_f32"), ("k_conv3x3<float, false", "k_conv3x3_dense_f32"),
          ("k_conv3x3<unsigned short, true", "k_conv3x3_pooled_bf16"),
          ("k_conv3x3<unsigned short, false", "k_conv3x3_dense_bf16"),
-         ("k_dense", "k_dense"), ("k_sparse_long", "k_sparse_long"), ("k_sparse", "k_sparse"), ("k_csr_frame", "k_csr_frame"), ("k_compact", "k_compact"),
+         ("k_dense", "k_dense"), ("k_clear", "k_clear"), ("k_sparse_long", "k_sparse_long"), ("k_sparse", "k_sparse"), ("k_csr_frame", "k_csr_frame"), ("k_compact", "k_compact"),
          ("k_count", "k_count"))
 
 
@@ -114,27 +114,41 @@ def main(key):
     print(json.dumps(tj[key], indent=1))
 
 
-LAYER = ("k_dense", "k_sparse", "k_sparse_long", "k_rows", "k_bpull", "k_once")
+LAYER = ("k_dense", "k_clear", "k_sparse", "k_sparse_long", "k_rows", "k_bpull", "k_once")
 
 
-def step_traffic(key, tag, layer_kernels=LAYER, anchor="k_count"):
+def step_traffic(key, tag, layer_kernels=LAYER, anchor="k_count", skip_after=None):
     """Per-step HBM bytes of the layer kernels of one bench workload from the
     scripts/r02_pmc.sh passes (gpurun_out/pmc_<tag>_FETCH_SIZE, _WRITE_SIZE):
     every launch's counters summed, divided by the steps profiled (the number of
-    k_count launches: one index build per step)."""
+    k_count launches: one index build per step).
+    skip_after "KERNEL:N": the launches up to and including KERNEL's N-th (by Dispatch_Id) are left out --
+    the first, full step of a kept-zeros pipeline ends with k_sparse_long's first launch ("k_sparse_long:1"),
+    so the entry is the kept-zeros step's own traffic."""
+    def short_of(name):
+        short = next((s for k, s in SHORT if k in name), None)
+        if short is None:
+            m = re.search(r"(k_[A-Za-z0-9_]+)", name)
+            short = m.group(1) if m else name[:40]
+        return short
+
     def launches(counter):
         files = glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}_{counter}", "**", "*counter_collection.csv"),
                           recursive=True)
         acc = defaultdict(lambda: [0.0, 0])
         for f in files:
-            for r in csv.DictReader(open(f)):
-                if r.get("Counter_Name") != counter:
+            rows = [r for r in csv.DictReader(open(f)) if r.get("Counter_Name") == counter]
+            first = -1
+            if skip_after:
+                kern, nth = skip_after.split(":")
+                ids = sorted(int(r["Dispatch_Id"]) for r in rows if short_of(r["Kernel_Name"]) == kern)
+                if len(ids) < int(nth):
+                    sys.exit(f"traffic.py: fewer than {nth} launches of {kern} in {f}")
+                first = ids[int(nth) - 1]
+            for r in rows:
+                if int(r.get("Dispatch_Id", 0)) <= first:
                     continue
-                name = r["Kernel_Name"]
-                short = next((s for k, s in SHORT if k in name), None)
-                if short is None:
-                    m = re.search(r"(k_[A-Za-z0-9_]+)", name)
-                    short = m.group(1) if m else name[:40]
+                short = short_of(r["Kernel_Name"])
                 acc[short][0] += float(r["Counter_Value"])
                 acc[short][1] += 1
         return acc
@@ -155,7 +169,8 @@ def step_traffic(key, tag, layer_kernels=LAYER, anchor="k_count"):
                **stamp(f"pmc_{tag}_FETCH_SIZE.log", f"pmc_{tag}_WRITE_SIZE.log"), "kernels": out,
                "note": ("layer = " + (" + ".join(layer_kernels) if layer_kernels else "every profiled kernel")
                         + " per step (every launch of the step summed); FETCH_SIZE x2 (gfx950 wide-read "
-                        "correction), KiB -> bytes; scripts/r03_pmc.sh")}
+                        "correction), KiB -> bytes; scripts/r03_pmc.sh"
+                        + (f"; launches through {skip_after} left out (the first, full step)" if skip_after else ""))}
     json.dump(tj, open(path, "w"), indent=1)
     print(key, f"{layer / 1e9:.4f} GB per step", {k: round((v['fetch_bytes_per_step'] + v['write_bytes_per_step']) / 1e6, 2)
                                                    for k, v in out.items()})
@@ -163,9 +178,10 @@ def step_traffic(key, tag, layer_kernels=LAYER, anchor="k_count"):
 
 if __name__ == "__main__":
     key = sys.argv[1] if len(sys.argv) > 1 else "config2_F64"
-    if key == "step":  # traffic.py step KEY TAG [all] [ANCHOR]: per-step bytes of a bench workload's PMC passes
+    if key == "step":  # traffic.py step KEY TAG [all|layer] [ANCHOR] [KERNEL:N]: per-step bytes of a bench workload's PMC passes
         every = len(sys.argv) > 4 and sys.argv[4] == "all"
-        step_traffic(sys.argv[2], sys.argv[3], None if every else LAYER, sys.argv[5] if len(sys.argv) > 5 else "k_count")
+        step_traffic(sys.argv[2], sys.argv[3], None if every else LAYER, sys.argv[5] if len(sys.argv) > 5 else "k_count",
+                     sys.argv[6] if len(sys.argv) > 6 else None)
         sys.exit(0)
     if key.startswith("conv_c6_"):  # conv_c6_<dt>_F64: the RetinaNet conv (gpu_conv_prof.sh CFG=6)
         conv(key, key.split("_")[2], "c6_" + key.split("_")[2])

@@ -349,6 +349,24 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_sparse(const Feat f, const Ents 
     sparse_body<T, VEC, GROUP, SPLIT, POW2, LIVE>(f, e, cpool_shift, blockIdx.x, gridDim.x);
 }
 
+// shpl_pull_clear: k_sparse's thread shape and head test, every run short or long; the thread on a run's first
+// entry stores k_dense's zero chunk where k_sparse stored the run's sum. Reads ent_dst only. A destination
+// outside [0, n_keys) (a CSR never built) is skipped: nothing is stored outside out's rows.
+template <typename T, int VEC, bool POW2>
+__global__ __launch_bounds__(SHPL_BLOCK) void k_clear(const int32_t *dst, int64_t nnz, uint32_t n_keys, T *out,
+                                                      int64_t out_stride, uint32_t cpool, int cpool_shift) {
+    typedef Chunk<T, VEC> C;
+    const int64_t total = nnz * (int64_t)cpool;
+    for (int64_t t = (int64_t)blockIdx.x * SHPL_BLOCK + threadIdx.x; t < total; t += (int64_t)gridDim.x * SHPL_BLOCK) {
+        const int64_t s = POW2 ? t >> cpool_shift : t / cpool;
+        const uint32_t c = (uint32_t)(t - s * cpool);
+        const int32_t key = dst[s];
+        const int32_t prev = s > 0 ? dst[s - 1] : -1;
+        if ((uint32_t)key >= n_keys || prev == key) continue;  // empty or out of range, or not the first entry of key
+        C::store_nt(out + ((int64_t)key * out_stride + (int64_t)c * VEC), C::zero());
+    }
+}
+
 // shpl_pull_once: the pooled part of every destination row written exactly once, in ONE launch and with no
 // streaming pass before it. The sblocks run-walking blocks write the occupied rows: seg_window's wave per 64
 // sorted entries for wide cell-keyed rows (once_seg), else k_sparse's (entry, chunk) walk over every run; the
@@ -1092,6 +1110,34 @@ extern "C" int shpl_pull_once(SHPL_PULL_ARGS) {
     if (mode != SHPL_OUT_POOL || !csr->key_range) return SHPL_ERR_ARG;
     if (pl.n_dst == 0 || pl.f.cpool == 0) return SHPL_OK;
     return once(pl, csr, direction, (hipStream_t)stream);
+}
+
+extern "C" int shpl_pull_clear(int dtype, const shpl_csr *csr, int64_t c_pool, void *d_out, int64_t out_stride,
+                               int64_t out_off, void *stream) {
+    if (!csr) return SHPL_ERR_ARG;
+    if (dtype != SHPL_F32 && dtype != SHPL_BF16) return SHPL_ERR_ARG;
+    const int64_t n_dst = csr->n_keys, nnz_cap = csr->nnz_cap;
+    if (n_dst < 0 || n_dst >= 2147483647LL || nnz_cap < 0 || c_pool < 0 || out_off < 0) return SHPL_ERR_BAD_SHAPE;
+    if (n_dst > 0 && !d_out) return SHPL_ERR_ARG;
+    if (nnz_cap > 0 && !csr->ent_dst) return SHPL_ERR_ARG;
+    if (out_stride < out_off + c_pool || out_stride >= ((int64_t)1 << 31)) return SHPL_ERR_BAD_SHAPE;
+    if (n_dst == 0 || nnz_cap == 0 || c_pool == 0) return SHPL_OK;
+    const int64_t esz = dtype == SHPL_F32 ? 4 : 2, vec = 16 / esz;
+    // 16-byte chunks need every row start and the pooled columns on a 16-byte boundary (plan()'s rule)
+    const bool v16 = c_pool % vec == 0 && out_stride % vec == 0 && out_off % vec == 0 && aligned16(d_out);
+    const uint32_t cpool = (uint32_t)(c_pool / (v16 ? vec : 1));
+    const int grid = grid_for(nnz_cap * (int64_t)cpool, SHPL_BLOCK, 1 << 20);
+    const int shift = pow2_shift(cpool);
+    by_elems(dtype, v16, [&](auto el) {
+        typedef decltype(el) E;
+        by_bools([&](auto POW2) {
+            hipLaunchKernelGGL((k_clear<typename E::T, E::VEC, POW2.value>), dim3(grid), dim3(SHPL_BLOCK), 0,
+                               (hipStream_t)stream, (const int32_t *)csr->ent_dst, nnz_cap, (uint32_t)n_dst,
+                               reinterpret_cast<typename E::T *>(d_out) + out_off, out_stride, cpool, shift);
+        }, shift >= 0);
+    });
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
 }
 
 extern "C" int shpl_pull_pair(const shpl_csr *by_cell, const shpl_pull_desc *d_cell, const shpl_csr *by_pixel,

@@ -23,6 +23,22 @@ from .shpl_map import ShplMap, raise_for_bits
 
 
 class FusedPipeline:
+    """The batched step over preallocated buffers (module docstring).
+
+    Kept zeros (KEEP_ZEROS; img->BEV pipelines that are not dual, split, row-keyed or live): the pooled half
+    ``bv_fused[..., Cb:]`` belongs to the pipeline between steps. After one full step issued eagerly it is zero
+    everywhere but at the cells of ``self.csr``; ``step`` / ``step_overlapped`` then clear those cells
+    (shpl_pull_clear, before the CSR is rebuilt), copy the pass-through half and pool: no zeros are streamed.
+    Consumers read ``bv_fused``. Whoever writes into its pooled half calls ``invalidate()``: the next step is the
+    full one again (k_dense over every row, then k_sparse). A graph captured while the pipeline was clean holds
+    the kept-zeros step and must be captured again after ``invalidate()`` (or after ``check()`` raised). Every
+    other pipeline, and layer_dense / layer_sparse / layer, write every element on every step as before."""
+    # the kept-zeros form of step / step_overlapped where the pipeline qualifies (False: the full stream
+    # everywhere; A/B)
+    KEEP_ZEROS = True
+    # kept zeros in step_overlapped: the sparse pass after the side stream's copy (True) or beside it (False;
+    # disjoint columns, so it need not wait)
+    KEEP_ZEROS_SERIAL = False
     # row-keyed pulls (one launch per pull, shpl_csr.key_range) for batches under this many frames whose
     # maps have at most ROWS_MAX_KEYS destinations per frame: latency-bound layers (config 3)
     ROWS_FRAMES, ROWS_MAX_KEYS, ROWS_MAX_CAP = 32, 65536, 1 << 24
@@ -102,6 +118,10 @@ class FusedPipeline:
             for c in (self.csr, self.pcsr if dual else None):
                 if c is not None:
                     c.live_frames(self.frame_off, self.frame_nnz)
+        self.live = bool(live)
+        # kept zeros: bv_fused's pooled half is zero except at self.csr's cells (class docstring); only an
+        # eagerly issued full step makes it so
+        self._pooled_clean = False
         self._lib = L.lib()
         if self.buckets:
             # zeroed once: its frame barrier words start at zero (every call leaves them so)
@@ -143,6 +163,10 @@ class FusedPipeline:
     csr_path = L.CSR_AUTO
 
     def build_csr(self, which=("cell", "pixel")):
+        if "cell" in which:
+            # the kept zeros are known by self.csr's cells: a caller building it outside the steps below gets
+            # the full step next (the steps themselves put the flag back)
+            self._pooled_clean = False
         st = L.stream_of(self.dev)
         if self.buckets:  # both CSRs from the index build's buckets, one launch
             L.check(self._lib.shpl_build_csr_buckets(
@@ -266,10 +290,38 @@ class FusedPipeline:
         self.layer_dense(bev, img)
         self.layer_sparse(bev, img)
 
+    # ------------------------------------------------------------------ kept zeros
+    def _keeps_zeros(self):
+        """The pipelines whose steps may take the kept-zeros form."""
+        return self.KEEP_ZEROS and not (self.dual or self.split or self.rows or self.live)
+
+    def invalidate(self):
+        """bv_fused's pooled half was written by someone else: the next step is the full one (class docstring)."""
+        self._pooled_clean = False
+
+    def _clear_pooled(self):
+        """Zeros at the pooled chunks of self.csr's cells (the previous step's): before the CSR is rebuilt."""
+        L.check(self._lib.shpl_pull_clear(L.dtype_code(self.bv_fused), self.csr.ref(), self.Ci, L.ptr(self.bv_fused),
+                                          self.Cb + self.Ci, self.Cb, L.stream_of(self.dev)), "shpl_pull_clear")
+
+    def _full_step_done(self):
+        """After a full step (every element written, self.csr the pooled cells): clean only when it really ran
+        -- a dirty pipeline under stream capture captures the full form and stays dirty."""
+        self._pooled_clean = self._keeps_zeros() and not torch.cuda.is_current_stream_capturing()
+
     def step(self, points, voxels, point_offsets, P, bev, img, mval=None):
+        if self._keeps_zeros() and self._pooled_clean:
+            self._clear_pooled()
+            self.build_index(points, voxels, point_offsets, P, mval)
+            self.build_csr()
+            self._pass_copies(bev, img, ("cell",))
+            self.layer_sparse(bev, img, ("cell",))
+            self._pooled_clean = True
+            return
         self.build_index(points, voxels, point_offsets, P, mval)
         self.build_csr()
         self.layer(bev, img)
+        self._full_step_done()
 
     def _pooled_half(self, img):
         """split: bv_fused[..., Cb:] = pool(img), every row written once (zeros where no entry lands): the
@@ -331,7 +383,9 @@ class FusedPipeline:
         current stream builds M and its CSR; the sparse half then waits for it.
         Dual layers with `side2`: the pixel-keyed CSR and pull run on side2,
         beside the cell-keyed ones (they share only M).
-        `events` (4 timing events) bracket the dense and the sparse launches."""
+        `events` (4 timing events) bracket the dense and the sparse launches.
+        A clean kept-zeros pipeline (class docstring): the copy alone on `side`, the clear, the index chain
+        and the sparse pass on the current stream."""
         if self.buckets:
             # one stream: index + buckets with the pass-through halves riding its two launches, both CSRs
             # (1 launch), both pooled halves (1 launch). (The copies on `side` beside the index chain instead
@@ -351,6 +405,29 @@ class FusedPipeline:
             return
         main = torch.cuda.current_stream(self.dev)
         side.wait_stream(main)            # inputs / previous step done
+        if self._keeps_zeros() and self._pooled_clean:
+            # kept zeros: the pass-through copy alone on `side`; here the previous step's cells cleared, then
+            # the index chain and the sparse pass. The two streams write disjoint columns of bv_fused, so the
+            # sparse pass waits for the copy only with KEEP_ZEROS_SERIAL.
+            with torch.cuda.stream(side):
+                if events:
+                    events[0].record(side)
+                self._pass_copies(bev, img, ("cell",))
+                if events:
+                    events[1].record(side)
+            self._clear_pooled()
+            self.build_index(points, voxels, point_offsets, P, mval)
+            self.build_csr(("cell",))
+            if self.KEEP_ZEROS_SERIAL:
+                main.wait_stream(side)
+            if events:
+                events[2].record(main)
+            self.layer_sparse(bev, img, ("cell",))
+            main.wait_stream(side)
+            if events:
+                events[3].record(main)
+            self._pooled_clean = True
+            return
         split = self.dual and side2 is not None
         # dual layers: the cell-keyed sparse pass needs only bv_fused's stream, so it runs
         # beside img_fused's stream (the gathers overlap the second dense pass)
@@ -384,6 +461,7 @@ class FusedPipeline:
         main.wait_stream(side)
         if events:
             events[3].record(main)
+        self._full_step_done()
 
     def backward(self, g_bv, g_img, d_bev, d_img, side2=None):
         """TF gradient of the dual layer with the concat split and add_n fused:
@@ -422,10 +500,11 @@ class FusedPipeline:
         call it outside timed or captured regions). The steps never read it themselves. SHPL_EBIT_BARRIER (the
         one-launch index build gave up at a frame barrier, or found its words not zeroed) raises RuntimeError
         after the word and the barrier words are reset, so the next step can run; an input bit raises
-        ShplMap.check's InvalidArgumentError."""
+        ShplMap.check's InvalidArgumentError. Either way a kept-zeros pipeline is dirty afterwards."""
         bits = int(self.err.item()) & 0xFFFFFFFF
         if not bits:
             return
+        self._pooled_clean = False  # a flagged step's CSR need not name the cells it wrote: the full step next
         self.err.zero_()
         if bits & L.EBIT_BARRIER and self.buckets:
             L.bucket_workspace_reset(self.B, self.bkt_ws, self.dev)
