@@ -40,69 +40,17 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_head_pack(const T *__restrict__ 
     wp[t] = v;
 }
 
-struct Src {
-    const void *x;
-    int64_t stride, off, c;
-    const void *wp;
-};
-
 struct GemmArgs {
     Src s[2];
     int64_t rows;
     const float *bias;
     int c_out;
-    // the run walk (key_range NULL: none)
-    const int32_t *key_range, *ent_src;
-    const float *ent_val, *z;
-    int64_t nnz_cap, z_rows;
+    PoolRef pool;  // the run walk over z [pool.n_src][NP] (key_range NULL: none)
+    const float *z;
     void *out;  // to_z: f32 [rows][NP]; else the feature dtype, out_stride elements per row
     int64_t out_stride;
     int to_z;
 };
-
-// acc += row rl of one source times its packed weights (a source of no channels: nothing). Two register stages:
-// the loads of the next K step are issued before the MFMAs of the current one.
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ f32x16 gemm_source(const Src &src, int64_t rl, int lane, f32x16 acc) {
-    constexpr int VEC = Vec<T>::N;
-    const int64_t c = src.c;
-    const int h = lane >> 5;
-    const T *xr = reinterpret_cast<const T *>(src.x) + rl * src.stride + src.off + h * SUB * VEC;
-    const T *wp = reinterpret_cast<const T *>(src.wp) + lane * VEC;
-    const int64_t steps = (c + SUB * 2 * VEC - 1) / (SUB * 2 * VEC);
-    auto load = [&](int64_t st, T (&xv)[SUB][VEC], T (&wv)[SUB][VEC]) {
-        const int64_t k = st * SUB * 2 * VEC;
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) {
-            if constexpr (ALIGNED) {
-                const u32x4 v = *reinterpret_cast<const u32x4 *>(xr + k + j * VEC);
-                __builtin_memcpy(xv[j], &v, 16);
-            } else {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) xv[j][i] = k + (h * SUB + j) * VEC + i < c ? xr[k + j * VEC + i] : T(0);
-            }
-            const u32x4 wq = *reinterpret_cast<const u32x4 *>(wp + (st * SUB + j) * 64 * VEC);
-            __builtin_memcpy(wv[j], &wq, 16);
-        }
-    };
-    auto mul = [&](const T (&xv)[SUB][VEC], const T (&wv)[SUB][VEC]) {
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) acc = mma(xv[j], wv[j], acc);
-    };
-    if (steps == 0) return acc;
-    T xa[SUB][VEC], wa[SUB][VEC], xb[SUB][VEC], wb[SUB][VEC];
-    load(0, xa, wa);
-    // a branch-free body (a load under a condition makes the wait before the MFMAs drain the loads just issued): the
-    // second load of the last pair of an even count re-reads the last step, unused
-    for (int64_t p = 0; p < steps / 2; ++p) {
-        load(2 * p + 1, xb, wb);
-        mul(xa, wa);
-        load(2 * p + 2 < steps ? 2 * p + 2 : steps - 1, xa, wa);
-        mul(xb, wb);
-    }
-    if (steps & 1) mul(xa, wa);
-    return acc;
-}
 
 // One wave per 32 rows. ALIGNED: every row of both sources starts on a 16-byte boundary and holds whole K steps.
 // The run walk of the epilogue: a lane holds 16 rows of column n; their key ranges are fetched before the K loop,
@@ -117,15 +65,14 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_head_gemm(GemmArgs a) {
     const int64_t rl = row0 + n < a.rows ? row0 + n : a.rows - 1;  // the row this lane loads (clamped: not stored)
     // acc[i]: row 8 * (i / 4) + 4 * h + i % 4 of the tile, column n
     int32_t first[16], len[16];
-    const bool walk = !a.to_z && a.key_range;
+    const bool walk = !a.to_z && a.pool.key_range;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int64_t row = row0 + 8 * (i >> 2) + 4 * h + (i & 3);
         first[i] = len[i] = 0;
         if (walk && row < a.rows) {
-            int64_t e = a.key_range[2 * row], end = a.key_range[2 * row + 1];
-            if (e < 0) e = 0;
-            if (end > a.nnz_cap) end = a.nnz_cap;
+            int64_t e, end;
+            run_of(a.pool, row, e, end);
             first[i] = (int32_t)e;
             len[i] = end > e ? (int32_t)(end - e) : 0;
         }
@@ -133,8 +80,8 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_head_gemm(GemmArgs a) {
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    acc = gemm_source<T, ALIGNED>(a.s[0], rl, lane, acc);
-    acc = gemm_source<T, ALIGNED>(a.s[1], rl, lane, acc);
+    acc = source<T, ALIGNED, false>(a.s[0], rl, lane, acc);
+    acc = source<T, ALIGNED, false>(a.s[1], rl, lane, acc);
     const float bias = (a.bias && n < a.c_out) ? a.bias[n] : 0.0f;
     float v[16];
     int32_t longest = 0;
@@ -151,13 +98,13 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_head_gemm(GemmArgs a) {
             src[i] = -1;
             m[i] = 0.0f;
             if (t < len[i]) {
-                src[i] = a.ent_src[first[i] + t];
-                m[i] = a.ent_val[first[i] + t];
+                src[i] = a.pool.ent_src[first[i] + t];
+                m[i] = a.pool.ent_val[first[i] + t];
             }
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            src[i] = (src[i] >= 0 && src[i] < a.z_rows) ? src[i] : -1;
+            src[i] = (src[i] >= 0 && src[i] < a.pool.n_src) ? src[i] : -1;
             z[i] = src[i] >= 0 ? a.z[src[i] * NP + n] : 0.0f;
         }
 #pragma unroll
@@ -209,29 +156,19 @@ __global__ __launch_bounds__(64) void k_head_dgrad(const float *__restrict__ g, 
                                                    T *__restrict__ dx, int64_t dx_stride) {
     const int64_t c = ((int64_t)blockIdx.y * 64 + threadIdx.x) * COLS;
     float wr[COLS][CO];
-#pragma unroll
-    for (int i = 0; i < COLS; ++i)
-#pragma unroll
-        for (int j = 0; j < CO; ++j) wr[i][j] = (c + i < c_n && j < c_out) ? to_f32(w[(w_row0 + c + i) * c_out + j]) : 0.0f;
+    load_weights<T, CO>(w, w_row0, c, c_n, c_out, wr);
     const int64_t r0 = (int64_t)blockIdx.x * rows_per, r1 = r0 + rows_per < rows ? r0 + rows_per : rows;
     for (int64_t r = r0; r < r1; ++r) {
-        const float *gr = g + r * CO;
         float o[COLS];
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) o[i] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < CO; ++j) {
-            const float gj = gr[j];
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) o[i] = __builtin_fmaf(gj, wr[i][j], o[i]);
-        }
+        project<CO>(g + r * CO, wr, o);
         if (c >= c_n) continue;
+        // store_cols, written out: through the helper the unaligned forms took 5 more VGPRs (docs/HISTORY.md §13)
         T ov[COLS];
 #pragma unroll
         for (int i = 0; i < COLS; ++i) from_f32(o[i], &ov[i]);
         T *dst = dx + r * dx_stride + c;
         if constexpr (ALIGNED) {
-            typedef typename std::conditional<sizeof(T) == 4, f32x4, u16x4>::type V;
+            typedef typename Cols<T>::V V;
             V v;
             __builtin_memcpy(&v, ov, sizeof(V));
             *reinterpret_cast<V *>(dst) = v;
@@ -269,18 +206,7 @@ __global__ __launch_bounds__(WGRAD_WAVES * 64) void k_head_wgrad(const T *__rest
         const float *gr = g + r * CO;
         const T *xr = x + r * x_stride + x_off + c;
         float xv[COLS];
-        if constexpr (ALIGNED) {
-            typedef typename std::conditional<sizeof(T) == 4, f32x4, u16x4>::type V;
-            T raw[COLS];
-            V v = {};
-            if (c < c_n) v = *reinterpret_cast<const V *>(xr);
-            __builtin_memcpy(raw, &v, sizeof(V));
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) xv[i] = to_f32(raw[i]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) xv[i] = c + i < c_n ? to_f32(xr[i]) : 0.0f;
-        }
+        load_cols<T, ALIGNED>(xr, c, c_n, xv);
 #pragma unroll
         for (int j = 0; j < CO; ++j) {
             const float gj = gr[j];
@@ -348,35 +274,11 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_head_wreduce(const float *__rest
 }
 
 // ---------------------------------------------------------------- host side
-struct FwdLayout {
-    size_t wp[2], z, kr, bytes;
-};
-inline FwdLayout fwd_layout(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, bool pooled) {
-    const int vec = (int)(16 / esize(dtype));
-    FwdLayout l = {};
-    size_t o = 0;
-    const int64_t cs[2] = {c_a, c_b};
-    for (int s = 0; s < 2; ++s) {
-        l.wp[s] = o;
-        o = align_up(o + (size_t)pack_steps(cs[s], vec) * SUB * 64 * 16, 256);
-    }
-    l.z = o;
-    if (pooled) o = align_up(o + (size_t)rows_b * NP * 4, 256);
-    l.kr = o;
-    if (pooled) o = align_up(o + (size_t)rows * 8, 256);
-    l.bytes = o;
-    return l;
-}
-
 struct BwdLayout {
     int co;
     int64_t chunks[2];  // upper bounds of the weight gradient's row chunks per source
     size_t gp, gimg, part[2], bytes;
 };
-inline int64_t wgrad_chunks_max(int64_t rows) {
-    const int64_t c = (rows + WGRAD_MIN_ROWS - 1) / WGRAD_MIN_ROWS;
-    return c < 1 ? 1 : c > WGRAD_MAX_CHUNKS ? WGRAD_MAX_CHUNKS : c;
-}
 inline BwdLayout bwd_layout(int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out, bool pooled,
                             bool wgrad) {
     BwdLayout l = {};
@@ -389,7 +291,7 @@ inline BwdLayout bwd_layout(int64_t rows, int64_t c_a, int64_t rows_b, int64_t c
     const int64_t rs[2] = {rows, rows_b}, cs[2] = {c_a, c_b};
     for (int s = 0; s < 2; ++s) {
         l.part[s] = o;
-        l.chunks[s] = wgrad_chunks_max(rs[s]);
+        l.chunks[s] = chunking(rs[s], WGRAD_MIN_ROWS, WGRAD_MAX_CHUNKS).chunks_max;
         if (wgrad && cs[s] > 0) o = align_up(o + (size_t)l.chunks[s] * (size_t)(cs[s] + 1) * l.co * 4, 256);
     }
     l.bytes = o;
@@ -399,7 +301,7 @@ inline BwdLayout bwd_layout(int64_t rows, int64_t c_a, int64_t rows_b, int64_t c
 // The one published size of the forward's and the input gradient's workspace (shpl_head1x1_workspace_bytes):
 // both calls hold the caller to it.
 inline size_t ws_need(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out, bool pooled) {
-    const size_t f = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled).bytes;
+    const size_t f = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled, true).bytes;
     const size_t b = bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled, false).bytes;
     return f > b ? f : b;
 }
@@ -484,18 +386,12 @@ extern "C" int shpl_head1x1(int dtype, int64_t rows, const void *d_a, int64_t a_
                             const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b, int64_t rows_b,
                             const shpl_csr *pool, const void *d_weights, int64_t c_out, const float *d_bias,
                             void *d_out, int64_t out_stride, void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
-    if (rc != SHPL_OK) return rc;
-    if (!d_a || !d_weights || !d_out || (c_b > 0 && !d_b)) return SHPL_ERR_ARG;
-    if ((rc = check_pool(pool, false, rows, rows_b, c_b)) != SHPL_OK) return rc;
-    if (a_off < 0 || b_off < 0 || a_stride < a_off + c_a || (c_b > 0 && b_stride < b_off + c_b) || out_stride < c_out)
-        return SHPL_ERR_BAD_SHAPE;
     const bool pooled = pool != nullptr;
-    const FwdLayout l = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled);
-    if (!d_ws) return SHPL_ERR_ARG;
-    if (ws_bytes < ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled)) return SHPL_ERR_WORKSPACE;
-    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
-    if (rows == 0) return SHPL_OK;
+    int rc = check_sources(dtype, rows, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, rows_b, pool, false,
+                           d_weights, d_out, c_out, out_stride, true, d_ws, ws_bytes,
+                           [&] { return ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled); });
+    if (rc != SHPL_OK || rows == 0) return rc;
+    const FwdLayout l = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled, true);
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(d_ws);
     const int64_t esz = esize(dtype), vec = 16 / esz;
@@ -509,11 +405,9 @@ extern "C" int shpl_head1x1(int dtype, int64_t rows, const void *d_a, int64_t a_
         const unsigned grid = blocks_for(g.rows, (int64_t)TILE_ROWS * GEMM_WAVES);
         by_dtype(dtype, [&](auto tt) {
             typedef typename decltype(tt)::T T;
-            if (al) {
-                hipLaunchKernelGGL((k_head_gemm<T, true>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
-            } else {
-                hipLaunchKernelGGL((k_head_gemm<T, false>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
-            }
+            by_bools([&](auto al_) {
+                hipLaunchKernelGGL((k_head_gemm<T, decltype(al_)::value>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
+            }, al);
             return SHPL_OK;
         });
     };
@@ -531,20 +425,11 @@ extern "C" int shpl_head1x1(int dtype, int64_t rows, const void *d_a, int64_t a_
             gemm(g, al_b);
             SHPL_LAUNCH_CHECK();
         }
-        const int32_t *kr = pool->key_range;
-        if (!kr) {
-            if ((rc = launch_ranges(pool, rows, reinterpret_cast<int32_t *>(ws + l.kr), s)) != SHPL_OK) return rc;
-            kr =reinterpret_cast<const int32_t *>(ws + l.kr);
-        }
         g = GemmArgs{};
         g.c_out = (int)c_out;
         g.s[0] = Src{d_a, a_stride, a_off, c_a, ws + l.wp[0]};
-        g.key_range = kr;
-        g.ent_src = pool->ent_src;
-        g.ent_val = pool->ent_val;
+        if ((rc = pool_ref(pool, rows, rows_b, reinterpret_cast<int32_t *>(ws + l.kr), s, &g.pool)) != SHPL_OK) return rc;
         g.z = reinterpret_cast<const float *>(ws + l.z);
-        g.nnz_cap = pool->nnz_cap;
-        g.z_rows = rows_b;
     } else {
         g.s[0] = Src{d_a, a_stride, a_off, c_a, ws + l.wp[0]};
         g.s[1] = Src{d_b, b_stride, b_off, c_b, ws + l.wp[1]};
@@ -562,18 +447,12 @@ extern "C" int shpl_head1x1_dgrad(int dtype, int64_t rows, const void *d_gy, int
                                   const void *d_weights, int64_t c_a, int64_t c_b, void *d_da, int64_t da_stride,
                                   void *d_db, int64_t db_stride, int64_t rows_b, const shpl_csr *pool_grad,
                                   void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
-    if (rc != SHPL_OK) return rc;
-    if (!d_gy || !d_weights || (!d_da && !d_db)) return SHPL_ERR_ARG;
-    if (d_db && c_b < 1) return SHPL_ERR_BAD_SHAPE;
-    if ((rc = check_pool(pool_grad, true, rows, rows_b, c_b)) != SHPL_OK) return rc;
-    if (gy_stride < c_out || (d_da && da_stride < c_a) || (d_db && db_stride < c_b)) return SHPL_ERR_BAD_SHAPE;
     const bool pooled = pool_grad != nullptr;
+    int rc = check_dgrad(dtype, rows, d_gy, gy_stride, c_out, d_weights, c_a, c_b, d_da, da_stride, d_db, db_stride,
+                         rows_b, pool_grad, true, d_ws, ws_bytes,
+                         [&] { return ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled); });
+    if (rc != SHPL_OK || rows == 0) return rc;
     const BwdLayout l = bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled, false);
-    if (!d_ws) return SHPL_ERR_ARG;
-    if (ws_bytes < ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled)) return SHPL_ERR_WORKSPACE;
-    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
-    if (rows == 0) return SHPL_OK;
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(d_ws);
     float *gp = reinterpret_cast<float *>(ws + l.gp), *gimg = reinterpret_cast<float *>(ws + l.gimg);
@@ -587,15 +466,11 @@ extern "C" int shpl_head1x1_dgrad(int dtype, int64_t rows, const void *d_gy, int
             typedef typename decltype(tt)::T T;
             return by_cols(l.co, [&](auto cc) {
                 constexpr int CO = decltype(cc)::value;
-                if (al) {
-                    hipLaunchKernelGGL((k_head_dgrad<T, CO, true>), grid, dim3(64), 0, s, g, n_rows, (int64_t)DGRAD_ROWS,
-                                       reinterpret_cast<const T *>(d_weights), w_row0, c_n, (int)c_out,
-                                       reinterpret_cast<T *>(dx), dx_stride);
-                } else {
-                    hipLaunchKernelGGL((k_head_dgrad<T, CO, false>), grid, dim3(64), 0, s, g, n_rows,
+                by_bools([&](auto al_) {
+                    hipLaunchKernelGGL((k_head_dgrad<T, CO, decltype(al_)::value>), grid, dim3(64), 0, s, g, n_rows,
                                        (int64_t)DGRAD_ROWS, reinterpret_cast<const T *>(d_weights), w_row0, c_n,
                                        (int)c_out, reinterpret_cast<T *>(dx), dx_stride);
-                }
+                }, al);
                 return SHPL_OK;
             });
         });
@@ -621,17 +496,12 @@ extern "C" int shpl_head1x1_wgrad(int dtype, int64_t rows, const void *d_a, int6
                                   int64_t rows_b, const shpl_csr *pool_grad, const void *d_gy, int64_t gy_stride,
                                   int64_t c_out, float *d_dw, float *d_dbias, void *d_ws, size_t ws_bytes,
                                   void *stream) {
-    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
-    if (rc != SHPL_OK) return rc;
-    if (!d_a || !d_gy || !d_dw || (c_b > 0 && !d_b)) return SHPL_ERR_ARG;
-    if ((rc = check_pool(pool_grad, true, rows, rows_b, c_b)) != SHPL_OK) return rc;
-    if (a_off < 0 || b_off < 0 || a_stride < a_off + c_a || (c_b > 0 && b_stride < b_off + c_b) || gy_stride < c_out)
-        return SHPL_ERR_BAD_SHAPE;
     const bool pooled = pool_grad != nullptr;
+    int rc = check_sources(dtype, rows, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, rows_b, pool_grad, true,
+                           d_gy, d_dw, c_out, gy_stride, true, d_ws, ws_bytes,
+                           [&] { return bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled, true).bytes; });
+    if (rc != SHPL_OK) return rc;
     const BwdLayout l = bwd_layout(rows, c_a, rows_b, c_b, c_out, pooled, true);
-    if (!d_ws) return SHPL_ERR_ARG;
-    if (ws_bytes < l.bytes) return SHPL_ERR_WORKSPACE;
-    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(d_ws);
     float *gp = reinterpret_cast<float *>(ws + l.gp), *gimg = reinterpret_cast<float *>(ws + l.gimg);
@@ -642,30 +512,24 @@ extern "C" int shpl_head1x1_wgrad(int dtype, int64_t rows, const void *d_a, int6
     auto run = [&](int k, const void *x, int64_t x_stride, int64_t x_off, int64_t c_n, const float *g, int64_t n_rows,
                    int64_t w_row0, bool bias) {
         float *part = reinterpret_cast<float *>(ws + l.part[k]);
-        int64_t per = (n_rows + WGRAD_MAX_CHUNKS - 1) / WGRAD_MAX_CHUNKS;
-        if (per < WGRAD_MIN_ROWS) per = WGRAD_MIN_ROWS;
-        const int64_t chunks = (n_rows + per - 1) / per;  // <= l.chunks[k]; 0 rows: no partial, zeros
-        if (chunks > 0) {
+        const Chunking ch = chunking(n_rows, WGRAD_MIN_ROWS, WGRAD_MAX_CHUNKS);  // 0 rows: no partial, zeros
+        if (ch.chunks > 0) {
             const bool al = rows_aligned(x, x_stride, x_off, c_n, COLS, esz);
-            const dim3 grid((unsigned)chunks, blocks_for(c_n, 64 * COLS));
+            const dim3 grid((unsigned)ch.chunks, blocks_for(c_n, 64 * COLS));
             by_dtype(dtype, [&](auto tt) {
                 typedef typename decltype(tt)::T T;
                 return by_cols(l.co, [&](auto cc) {
                     constexpr int CO = decltype(cc)::value;
-                    if (al) {
-                        hipLaunchKernelGGL((k_head_wgrad<T, CO, true>), grid, dim3(WGRAD_WAVES * 64), 0, s,
-                                           reinterpret_cast<const T *>(x), x_stride, x_off, c_n, g, n_rows, per,
+                    by_bools([&](auto al_) {
+                        hipLaunchKernelGGL((k_head_wgrad<T, CO, decltype(al_)::value>), grid, dim3(WGRAD_WAVES * 64), 0,
+                                           s, reinterpret_cast<const T *>(x), x_stride, x_off, c_n, g, n_rows, ch.per,
                                            (int)bias, part);
-                    } else {
-                        hipLaunchKernelGGL((k_head_wgrad<T, CO, false>), grid, dim3(WGRAD_WAVES * 64), 0, s,
-                                           reinterpret_cast<const T *>(x), x_stride, x_off, c_n, g, n_rows, per,
-                                           (int)bias, part);
-                    }
+                    }, al);
                     return SHPL_OK;
                 });
             });
         }
-        launch_wreduce(part, chunks, c_n, l.co, c_out, bias, d_dw, w_row0, d_dbias, s);
+        launch_wreduce(part, ch.chunks, c_n, l.co, c_out, bias, d_dw, w_row0, d_dbias, s);
     };
     run(0, d_a, a_stride, a_off, c_a, gp, rows, 0, d_dbias != nullptr);
     SHPL_LAUNCH_CHECK();

@@ -100,85 +100,32 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_dropout_mask(int64_t rows, int64
 }
 
 // ---------------------------------------------------------------- forward
-struct Src {
-    const void *x;
-    int64_t stride, off, c;
-    const void *wp;
+struct MaskedSrc : Src {
     int64_t moff;  // the source's first channel in the concat: the mask's channel index
 };
 
 struct FwdArgs {
-    Src s[2];
+    MaskedSrc s[2];
     int64_t rows;
     const float *bias;
     int c_out;
-    // the pooled form (key_range NULL: s[1] is a dense map, or none)
-    const int32_t *key_range, *ent_src;
-    const float *ent_val;
-    int64_t nnz_cap, rows_b;
+    PoolRef pool;  // the pooled form (key_range NULL: s[1] is a dense map, or none)
     void *out;
     int64_t out_stride;
     Mask m;
 };
 
-// one 16-byte piece of a row: channels [k, k + VEC) of the c the row holds
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void load_piece(const T *p, int64_t k, int64_t c, T (&v)[Vec<T>::N]) {
-    constexpr int VEC = Vec<T>::N;
-    if constexpr (ALIGNED) {
-        const u32x4 q = *reinterpret_cast<const u32x4 *>(p);
-        __builtin_memcpy(v, &q, 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) v[i] = k + i < c ? p[i] : T(0);
-    }
-}
-
+// source<DROP>'s step (shpl_head.h): zero the dropped ones of the lane's SUB pieces, channels [c0, c0 + SUB * VEC) of
+// row r of the concat
 template <typename T>
-__device__ __forceinline__ void drop(T (&xv)[SUB][Vec<T>::N], uint32_t bits) {
+__device__ __forceinline__ void drop_step(T (&xv)[SUB][Vec<T>::N], const Mask &m, int64_t r, int64_t c0) {
     constexpr int VEC = Vec<T>::N;
+    const uint32_t bits = keep_bits<SUB * VEC>(m, r, c0);
 #pragma unroll
     for (int j = 0; j < SUB; ++j)
 #pragma unroll
         for (int i = 0; i < VEC; ++i)
             if (!((bits >> (j * VEC + i)) & 1u)) xv[j][i] = T(0);
-}
-
-// acc += the kept elements of row rl of a dense source times its packed weights: gemm_source of shpl_head.hip
-// (two register stages) with the lane's slice of the mask computed while the next step's loads are in flight.
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ f32x16 dense_source(const Src &src, const Mask &m, int64_t rl, int lane, f32x16 acc) {
-    constexpr int VEC = Vec<T>::N, NCH = SUB * VEC;
-    const int64_t c = src.c;
-    const int h = lane >> 5;
-    const T *xr = reinterpret_cast<const T *>(src.x) + rl * src.stride + src.off + h * NCH;
-    const T *wp = reinterpret_cast<const T *>(src.wp) + lane * VEC;
-    const int64_t steps = (c + 2 * NCH - 1) / (2 * NCH);
-    auto load = [&](int64_t st, T (&xv)[SUB][VEC], T (&wv)[SUB][VEC]) {
-        const int64_t k = st * 2 * NCH;
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) {
-            load_piece<T, ALIGNED>(xr + k + j * VEC, k + h * NCH + j * VEC, c, xv[j]);
-            const u32x4 wq = *reinterpret_cast<const u32x4 *>(wp + (st * SUB + j) * 64 * VEC);
-            __builtin_memcpy(wv[j], &wq, 16);
-        }
-    };
-    auto mul = [&](int64_t st, T (&xv)[SUB][VEC], const T (&wv)[SUB][VEC]) {
-        drop<T>(xv, keep_bits<NCH>(m, rl, src.moff + st * 2 * NCH + h * NCH));
-#pragma unroll
-        for (int j = 0; j < SUB; ++j) acc = mma(xv[j], wv[j], acc);
-    };
-    if (steps == 0) return acc;
-    T xa[SUB][VEC], wa[SUB][VEC], xb[SUB][VEC], wb[SUB][VEC];
-    load(0, xa, wa);
-    for (int64_t p = 0; p < steps / 2; ++p) {
-        load(2 * p + 1, xb, wb);
-        mul(2 * p, xa, wa);
-        load(2 * p + 2 < steps ? 2 * p + 2 : steps - 1, xa, wa);
-        mul(2 * p + 1, xb, wb);
-    }
-    if (steps & 1) mul(steps - 1, xa, wa);
-    return acc;
 }
 
 // acc += the kept elements of the pooled row of cell rl times the second source's packed weights. K step outer,
@@ -189,7 +136,7 @@ template <typename T, bool ALIGNED>
 __device__ __forceinline__ f32x16 pooled_source(const FwdArgs &a, int64_t rl, int32_t first, int32_t len, int lane,
                                                 f32x16 acc) {
     constexpr int VEC = Vec<T>::N, NCH = SUB * VEC;
-    const Src &src = a.s[1];
+    const MaskedSrc &src = a.s[1];
     const int64_t c = src.c;
     const int h = lane >> 5;
     const T *xb = reinterpret_cast<const T *>(src.x) + src.off + h * NCH;
@@ -209,9 +156,9 @@ __device__ __forceinline__ f32x16 pooled_source(const FwdArgs &a, int64_t rl, in
 #pragma unroll
             for (int i = 0; i < VEC; ++i) sum[j][i] = 0.0f;
         for (int32_t t = 0; t < len; ++t) {
-            const int64_t p = a.ent_src[first + t];
-            const float mv = a.ent_val[first + t];
-            if (p < 0 || p >= a.rows_b) continue;  // a malformed map addresses nothing outside b
+            const int64_t p = a.pool.ent_src[first + t];
+            const float mv = a.pool.ent_val[first + t];
+            if (p < 0 || p >= a.pool.n_src) continue;  // a malformed map addresses nothing outside b
             T xv[SUB][VEC];
 #pragma unroll
             for (int j = 0; j < SUB; ++j)
@@ -226,7 +173,7 @@ __device__ __forceinline__ f32x16 pooled_source(const FwdArgs &a, int64_t rl, in
         for (int j = 0; j < SUB; ++j)
 #pragma unroll
             for (int i = 0; i < VEC; ++i) from_f32(sum[j][i], &xq[j][i]);
-        drop<T>(xq, keep_bits<NCH>(a.m, rl, src.moff + k + h * NCH));
+        drop_step(xq, a.m, rl, src.moff + k + h * NCH);
 #pragma unroll
         for (int j = 0; j < SUB; ++j) acc = mma(xq[j], wv[j], acc);
     }
@@ -244,15 +191,14 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_head_drop_gemm(FwdArgs a) {
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    acc = dense_source<T, ALIGNED>(a.s[0], a.m, rl, lane, acc);
-    if (a.key_range) {
-        int64_t e = a.key_range[2 * rl], end = a.key_range[2 * rl + 1];
-        if (e < 0) e = 0;
-        if (end > a.nnz_cap) end = a.nnz_cap;
+    acc = source<T, ALIGNED, true>(a.s[0], rl, lane, acc, a.m, a.s[0].moff);
+    if (a.pool.key_range) {
+        int64_t e, end;
+        run_of(a.pool, rl, e, end);
         const int32_t len = (end > e && row0 + n < a.rows) ? (int32_t)(end - e) : 0;
         if (__ballot(len > 0) != 0) acc = pooled_source<T, ALIGNED>(a, rl, (int32_t)e, len, lane, acc);
     } else {
-        acc = dense_source<T, ALIGNED>(a.s[1], a.m, rl, lane, acc);
+        acc = source<T, ALIGNED, true>(a.s[1], rl, lane, acc, a.m, a.s[1].moff);
     }
     const float bias = (a.bias && n < a.c_out) ? a.bias[n] : 0.0f;
     // acc[i]: row 8 * (i / 4) + 4 * h + i % 4 of the tile, column n
@@ -265,81 +211,6 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_head_drop_gemm(FwdArgs a) {
 }
 
 // ---------------------------------------------------------------- backward
-template <typename T>
-struct Cols {  // COLS elements as one vector
-    typedef typename std::conditional<sizeof(T) == 4, f32x4, u16x4>::type V;
-};
-
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void load_cols(const T *p, int64_t c, int64_t c_n, float (&xv)[COLS]) {
-    if constexpr (ALIGNED) {
-        typedef typename Cols<T>::V V;
-        T raw[COLS];
-        V v = {};
-        if (c < c_n) v = *reinterpret_cast<const V *>(p);
-        __builtin_memcpy(raw, &v, sizeof(V));
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) xv[i] = to_f32(raw[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) xv[i] = c + i < c_n ? to_f32(p[i]) : 0.0f;
-    }
-}
-
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void store_cols(T *dst, int64_t c, int64_t c_n, const float (&o)[COLS]) {
-    if (c >= c_n) return;
-    T ov[COLS];
-#pragma unroll
-    for (int i = 0; i < COLS; ++i) from_f32(o[i], &ov[i]);
-    if constexpr (ALIGNED) {
-        typedef typename Cols<T>::V V;
-        V v;
-        __builtin_memcpy(&v, ov, sizeof(V));
-        *reinterpret_cast<V *>(dst) = v;
-    } else {
-#pragma unroll
-        for (int i = 0; i < COLS; ++i)
-            if (c + i < c_n) dst[i] = ov[i];
-    }
-}
-
-// a thread's COLS channels of W[w_row0 + c .. ][.] in registers
-template <typename T, int CO>
-__device__ __forceinline__ void load_weights(const T *w, int64_t w_row0, int64_t c, int64_t c_n, int c_out,
-                                             float (&wr)[COLS][CO]) {
-#pragma unroll
-    for (int i = 0; i < COLS; ++i)
-#pragma unroll
-        for (int j = 0; j < CO; ++j) wr[i][j] = (c + i < c_n && j < c_out) ? to_f32(w[(w_row0 + c + i) * c_out + j]) : 0.0f;
-}
-
-// o[i] = sum_j gr[j] * wr[i][j], j ascending, fused multiply-adds
-template <int CO>
-__device__ __forceinline__ void project(const float *gr, const float (&wr)[COLS][CO], float (&o)[COLS]) {
-#pragma unroll
-    for (int i = 0; i < COLS; ++i) o[i] = 0.0f;
-#pragma unroll
-    for (int j = 0; j < CO; ++j) {
-        const float gj = gr[j];
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) o[i] = __builtin_fmaf(gj, wr[i][j], o[i]);
-    }
-}
-
-struct PoolRef {  // a CSR's runs, as the kernels read them
-    const int32_t *key_range, *ent_src;
-    const float *ent_val;
-    int64_t nnz_cap, n_src;  // entries; rows of the source the entries name
-};
-
-__device__ __forceinline__ void run_of(const PoolRef &p, int64_t key, int64_t &e, int64_t &end) {
-    e = p.key_range[2 * key];
-    end = p.key_range[2 * key + 1];
-    if (e < 0) e = 0;
-    if (end > p.nnz_cap) end = p.nnz_cap;
-}
-
 // dx[r][c] = keep(r, w_row0 + c) * scale * sum_j g[r][j] * W[w_row0 + c][j] over a dense map's rows: k_head_dgrad
 // with the mask at the store (a dropped element is exactly 0).
 template <typename T, int CO, bool ALIGNED>
@@ -545,6 +416,8 @@ __global__ __launch_bounds__(WG_WAVES * 64) void k_head_drop_wgrad(WgradArgs a) 
         }
     }
     __syncthreads();  // gy's rows are done with: the same LDS takes the waves' sums
+    // k_head_wgrad's reduction over eight waves, times scale at the store; one helper for both raised the
+    // VGPR count of forms of both kernels (docs/HISTORY.md §13), so each keeps its own
     for (int w = WG_WAVES - 1; w > 0; --w) {
         if (wave == w) {
 #pragma unroll
@@ -592,24 +465,6 @@ inline bool make_mask(double keep_prob, uint64_t seed, Mask *m) {
 
 // The workspaces hold packed weights, key ranges (for a CSR that carries none), the f32 padded copy of gy and
 // the weight gradient's partials: nothing of the size of a map or of the entries times the channels.
-struct FwdLayout {
-    size_t wp[2], kr, bytes;
-};
-inline FwdLayout fwd_layout(int dtype, int64_t rows, int64_t c_a, int64_t c_b, bool pooled) {
-    const int vec = (int)(16 / esize(dtype));
-    FwdLayout l = {};
-    size_t o = 0;
-    const int64_t cs[2] = {c_a, c_b};
-    for (int s = 0; s < 2; ++s) {
-        l.wp[s] = o;
-        o = align_up(o + (size_t)pack_steps(cs[s], vec) * SUB * 64 * 16, 256);
-    }
-    l.kr = o;
-    if (pooled) o = align_up(o + (size_t)rows * 8, 256);
-    l.bytes = o;
-    return l;
-}
-
 struct DgradLayout {
     int co;
     size_t gp, kr, bytes;
@@ -628,43 +483,30 @@ inline DgradLayout dgrad_layout(int64_t rows, int64_t rows_b, int64_t c_out, boo
 
 // The one published size of the forward's and the input gradient's workspace.
 inline size_t ws_need(int dtype, int64_t rows, int64_t c_a, int64_t rows_b, int64_t c_b, int64_t c_out, bool pooled) {
-    const size_t f = fwd_layout(dtype, rows, c_a, c_b, pooled).bytes;
+    const size_t f = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled, false).bytes;
     const size_t b = dgrad_layout(rows, rows_b, c_out, pooled).bytes;
     return f > b ? f : b;
 }
 
 struct WgradLayout {
     int co;
-    int64_t chunks;  // upper bound of the row chunks (both sources run over the cells)
+    Chunking ch;  // the row chunks (both sources run over the cells)
     size_t kr, part[2], bytes;
 };
 inline WgradLayout wgrad_layout(int64_t rows, int64_t c_a, int64_t c_b, int64_t c_out, bool pooled) {
     WgradLayout l = {};
     l.co = pad_cols(c_out);
-    const int64_t n = (rows + WG_MIN_ROWS - 1) / WG_MIN_ROWS;
-    l.chunks = n < 1 ? 1 : n > WG_MAX_CHUNKS ? WG_MAX_CHUNKS : n;
+    l.ch = chunking(rows, WG_MIN_ROWS, WG_MAX_CHUNKS);
     size_t o = 0;
     l.kr = o;
     if (pooled) o = align_up(o + (size_t)rows * 8, 256);
     const int64_t cs[2] = {c_a, c_b};
     for (int s = 0; s < 2; ++s) {
         l.part[s] = o;
-        if (cs[s] > 0) o = align_up(o + (size_t)l.chunks * (size_t)(cs[s] + 1) * l.co * 4, 256);
+        if (cs[s] > 0) o = align_up(o + (size_t)l.ch.chunks_max * (size_t)(cs[s] + 1) * l.co * 4, 256);
     }
     l.bytes = o;
     return l;
-}
-
-// the runs of `csr` over n_keys keys: its own key ranges, or ones built at kr
-inline int pool_ref(const shpl_csr *csr, int64_t n_keys, int64_t n_src, int32_t *kr, hipStream_t s, PoolRef *out) {
-    const int32_t *ranges = csr->key_range;
-    if (!ranges) {
-        const int rc = launch_ranges(csr, n_keys, kr, s);
-        if (rc != SHPL_OK) return rc;
-        ranges = kr;
-    }
-    *out = PoolRef{ranges, csr->ent_src, csr->ent_val, csr->nnz_cap, n_src};
-    return SHPL_OK;
 }
 
 }  // namespace head_drop
@@ -711,40 +553,26 @@ extern "C" int shpl_head1x1_drop(int dtype, int64_t rows, const void *d_a, int64
                                  int64_t rows_b, const shpl_csr *pool, const void *d_weights, int64_t c_out,
                                  const float *d_bias, void *d_out, int64_t out_stride, double keep_prob, uint64_t seed,
                                  void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
-    if (rc != SHPL_OK) return rc;
     Mask m;
-    if (!make_mask(keep_prob, seed, &m)) return SHPL_ERR_ARG;
-    if (!d_a || !d_weights || !d_out || (c_b > 0 && !d_b)) return SHPL_ERR_ARG;
-    if ((rc = check_pool(pool, false, rows, rows_b, c_b)) != SHPL_OK) return rc;
-    if (a_off < 0 || b_off < 0 || a_stride < a_off + c_a || (c_b > 0 && b_stride < b_off + c_b) || out_stride < c_out)
-        return SHPL_ERR_BAD_SHAPE;
-    const bool pooled = pool != nullptr;
-    const FwdLayout l = fwd_layout(dtype, rows, c_a, c_b, pooled);
-    if (!d_ws) return SHPL_ERR_ARG;
-    if (ws_bytes < ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled)) return SHPL_ERR_WORKSPACE;
-    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
-    if (rows == 0) return SHPL_OK;
+    const bool mask_ok = make_mask(keep_prob, seed, &m), pooled = pool != nullptr;
+    int rc = check_sources(dtype, rows, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, rows_b, pool, false,
+                           d_weights, d_out, c_out, out_stride, mask_ok, d_ws, ws_bytes,
+                           [&] { return ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled); });
+    if (rc != SHPL_OK || rows == 0) return rc;
+    const FwdLayout l = fwd_layout(dtype, rows, c_a, rows_b, c_b, pooled, false);
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(d_ws);
     const int64_t esz = esize(dtype), vec = 16 / esz;
     if ((rc = launch_pack(dtype, d_weights, 0, c_a, c_out, ws + l.wp[0], s)) != SHPL_OK) return rc;
     if ((rc = launch_pack(dtype, d_weights, c_a, c_b, c_out, ws + l.wp[1], s)) != SHPL_OK) return rc;
     FwdArgs g = {};
-    g.s[0] = Src{d_a, a_stride, a_off, c_a, ws + l.wp[0], 0};
-    g.s[1] = Src{d_b, b_stride, b_off, c_b, ws + l.wp[1], c_a};
+    g.s[0] = MaskedSrc{{d_a, a_stride, a_off, c_a, ws + l.wp[0]}, 0};
+    g.s[1] = MaskedSrc{{d_b, b_stride, b_off, c_b, ws + l.wp[1]}, c_a};
     g.rows = rows;
     g.bias = d_bias;
     g.c_out = (int)c_out;
-    if (pooled) {
-        PoolRef p;
-        if ((rc = pool_ref(pool, rows, rows_b, reinterpret_cast<int32_t *>(ws + l.kr), s, &p)) != SHPL_OK) return rc;
-        g.key_range = p.key_range;
-        g.ent_src = p.ent_src;
-        g.ent_val = p.ent_val;
-        g.nnz_cap = p.nnz_cap;
-        g.rows_b = rows_b;
-    }
+    if (pooled && (rc = pool_ref(pool, rows, rows_b, reinterpret_cast<int32_t *>(ws + l.kr), s, &g.pool)) != SHPL_OK)
+        return rc;
     g.out = d_out;
     g.out_stride = out_stride;
     g.m = m;
@@ -753,11 +581,9 @@ extern "C" int shpl_head1x1_drop(int dtype, int64_t rows, const void *d_a, int64
     const unsigned grid = blocks_for(rows, (int64_t)TILE_ROWS * GEMM_WAVES);
     by_dtype(dtype, [&](auto tt) {
         typedef typename decltype(tt)::T T;
-        if (al) {
-            hipLaunchKernelGGL((k_head_drop_gemm<T, true>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
-        } else {
-            hipLaunchKernelGGL((k_head_drop_gemm<T, false>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
-        }
+        by_bools([&](auto al_) {
+            hipLaunchKernelGGL((k_head_drop_gemm<T, decltype(al_)::value>), dim3(grid), dim3(GEMM_WAVES * 64), 0, s, g);
+        }, al);
         return SHPL_OK;
     });
     SHPL_LAUNCH_CHECK();
@@ -768,20 +594,13 @@ extern "C" int shpl_head1x1_drop_dgrad(int dtype, int64_t rows, const void *d_gy
                                        const void *d_weights, int64_t c_a, int64_t c_b, void *d_da, int64_t da_stride,
                                        void *d_db, int64_t db_stride, int64_t rows_b, const shpl_csr *pool_grad,
                                        double keep_prob, uint64_t seed, void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
-    if (rc != SHPL_OK) return rc;
     Mask m;
-    if (!make_mask(keep_prob, seed, &m)) return SHPL_ERR_ARG;
-    if (!d_gy || !d_weights || (!d_da && !d_db)) return SHPL_ERR_ARG;
-    if (d_db && c_b < 1) return SHPL_ERR_BAD_SHAPE;
-    if ((rc = check_pool(pool_grad, true, rows, rows_b, c_b)) != SHPL_OK) return rc;
-    if (gy_stride < c_out || (d_da && da_stride < c_a) || (d_db && db_stride < c_b)) return SHPL_ERR_BAD_SHAPE;
-    const bool pooled = pool_grad != nullptr;
+    const bool mask_ok = make_mask(keep_prob, seed, &m), pooled = pool_grad != nullptr;
+    int rc = check_dgrad(dtype, rows, d_gy, gy_stride, c_out, d_weights, c_a, c_b, d_da, da_stride, d_db, db_stride,
+                         rows_b, pool_grad, mask_ok, d_ws, ws_bytes,
+                         [&] { return ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled); });
+    if (rc != SHPL_OK || rows == 0) return rc;
     const DgradLayout l = dgrad_layout(rows, rows_b, c_out, pooled);
-    if (!d_ws) return SHPL_ERR_ARG;
-    if (ws_bytes < ws_need(dtype, rows, c_a, rows_b, c_b, c_out, pooled)) return SHPL_ERR_WORKSPACE;
-    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
-    if (rows == 0) return SHPL_OK;
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(d_ws);
     float *gp = reinterpret_cast<float *>(ws + l.gp);
@@ -843,25 +662,17 @@ extern "C" int shpl_head1x1_drop_wgrad(int dtype, int64_t rows, const void *d_a,
                                        int64_t rows_b, const shpl_csr *pool, const void *d_gy, int64_t gy_stride,
                                        int64_t c_out, float *d_dw, float *d_dbias, double keep_prob, uint64_t seed,
                                        void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_shape(dtype, rows, c_a, rows_b, c_b, c_out);
-    if (rc != SHPL_OK) return rc;
     Mask m;
-    if (!make_mask(keep_prob, seed, &m)) return SHPL_ERR_ARG;
-    if (!d_a || !d_gy || !d_dw || (c_b > 0 && !d_b)) return SHPL_ERR_ARG;
-    if ((rc = check_pool(pool, false, rows, rows_b, c_b)) != SHPL_OK) return rc;
-    if (a_off < 0 || b_off < 0 || a_stride < a_off + c_a || (c_b > 0 && b_stride < b_off + c_b) || gy_stride < c_out)
-        return SHPL_ERR_BAD_SHAPE;
-    const bool pooled = pool != nullptr;
+    const bool mask_ok = make_mask(keep_prob, seed, &m), pooled = pool != nullptr;
+    int rc = check_sources(dtype, rows, d_a, a_stride, a_off, c_a, d_b, b_stride, b_off, c_b, rows_b, pool, false, d_gy,
+                           d_dw, c_out, gy_stride, mask_ok, d_ws, ws_bytes,
+                           [&] { return wgrad_layout(rows, c_a, c_b, c_out, pooled).bytes; });
+    if (rc != SHPL_OK) return rc;
     const WgradLayout l = wgrad_layout(rows, c_a, c_b, c_out, pooled);
-    if (!d_ws) return SHPL_ERR_ARG;
-    if (ws_bytes < l.bytes) return SHPL_ERR_WORKSPACE;
-    if (!aligned16(d_ws)) return SHPL_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(d_ws);
     const int64_t esz = esize(dtype);
-    int64_t per = (rows + WG_MAX_CHUNKS - 1) / WG_MAX_CHUNKS;
-    if (per < WG_MIN_ROWS) per = WG_MIN_ROWS;
-    const int64_t chunks = (rows + per - 1) / per;  // <= l.chunks; 0 rows: no partial, zeros
+    const int64_t per = l.ch.per, chunks = l.ch.chunks;  // 0 rows: no partial, zeros
     PoolRef p = {};
     if (pooled && chunks > 0 &&
         (rc = pool_ref(pool, rows, rows_b, reinterpret_cast<int32_t *>(ws + l.kr), s, &p)) != SHPL_OK)
