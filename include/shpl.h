@@ -746,6 +746,49 @@ int shpl_upconv3x3(int dtype, int n_frames, int64_t h, int64_t w, const void *d_
                    int64_t c_out, const float *d_center, const float *d_scale, const float *d_shift, int act,
                    void *d_out, int64_t out_stride, double *d_stats, void *d_ws, size_t ws_bytes, void *stream);
 
+/* Input gradient of shpl_upconv3x3 (its adjoint in x). h, w are the INPUT map's size; d_gy is the gradient of the
+ * raw (pre-epilogue) output, 2h x 2w rows per frame of c_gy channels, gy_stride elements apart:
+ *   dx[f,i,j,ci] = sum over ky, kx in 0..2 with 2i+ky < 2h, 2j+kx < 2w, and co of
+ *                  gy[f,2i+ky,2j+kx,co] * W[ky,kx,co,ci]
+ * (a tap whose output pixel falls outside the map contributes nothing: ky = 2 at i = h-1, kx = 2 at j = w-1).
+ * d_weights is the forward's variable [3][3][c_gy][c_dx] (HWOI), unpacked and untransposed by the caller.
+ * c_split, d_dx_b, dx_b_stride as in shpl_conv3x3_dgrad: channels [0, c_split) go to d_dx (dx_stride apart),
+ * channels [c_split, c_dx) to d_dx_b, a dense map in the feature dtype whose every row is written -- the pooled
+ * half, which shpl_pull over the side's gradient CSR then carries back to its source; with d_dx_b NULL the
+ * split is ignored and all c_dx channels go to d_dx.
+ * f32: v_mfma_f32_32x32x2_f32 (exact f32 products); SHPL_BF16: v_mfma_f32_32x32x16_bf16; f32 accumulation, one
+ * rounding at the store; no atomics, bitwise repeatable. One staged chunk of gy feeds up to four blocks of 32 dx
+ * channels. shpl_upconv3x3's argument checks, status codes and order, with gy in the place of the output
+ * (gy_stride < c_gy: SHPL_ERR_BAD_SHAPE); n_frames, h or w of 0: SHPL_OK, nothing launched. Stream-ordered, no
+ * allocation, no host synchronisation (capturable). Workspace: shpl_upconv3x3_dgrad_workspace_bytes. */
+int shpl_upconv3x3_dgrad_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_gy,
+                                         int64_t c_dx, size_t *bytes);
+int shpl_upconv3x3_dgrad(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, int64_t gy_stride,
+                         int64_t c_gy, const void *d_weights /* HWOI [3][3][c_gy][c_dx] */, int64_t c_dx,
+                         void *d_dx, int64_t dx_stride, int64_t c_split, void *d_dx_b, int64_t dx_b_stride,
+                         void *d_ws, size_t ws_bytes, void *stream);
+
+/* Weight gradient of shpl_upconv3x3 (its adjoint in W), f32 HWOI:
+ *   dW[ky,kx,co,ci] = sum over f, i, j with 2i+ky < 2h, 2j+kx < 2w of gy[f,2i+ky,2j+kx,co] * x[f,i,j,ci]
+ * x = [a || b] given exactly as shpl_upconv3x3 takes its sources, in every form: dense, c_b = 0, pooled through the
+ * cell-keyed CSR, pooled through the pixel-keyed CSR (ent_col groups or SHPL_CSR_IDENTITY_COLS). The pooled
+ * channels are recomputed in the staging, in the pull's order, rounded once to the storage dtype and never
+ * stored: when c_a is a multiple of the staging chunk (8 f32 / 16 bf16 channels) the pooled call gives bitwise
+ * the dW of the same call with d_b = the dense map shpl_pull writes. d_gy as in shpl_upconv3x3_dgrad, c_out
+ * channels. f32: v_mfma_f32_32x32x2_f32 (exact f32 products); SHPL_BF16: v_mfma_f32_32x32x16_bf16; f32 sums per
+ * workgroup, the workgroups' partials added in a fixed order (f64): no atomics, bitwise repeatable.
+ * shpl_upconv3x3's argument checks, status codes and order, with gy in the place of the output and d_dw in the
+ * place of the weights; n_frames, h or w of 0: SHPL_OK, nothing launched (d_dw is left as it is). Stream-ordered,
+ * no allocation, no host synchronisation (capturable). Workspace: shpl_upconv3x3_wgrad_workspace_bytes,
+ * pool_nnz_cap = pool->nnz_cap for a pooled call, -1 without a pool. */
+int shpl_upconv3x3_wgrad_workspace_bytes(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b,
+                                         int64_t c_out, int64_t pool_nnz_cap, size_t *bytes);
+int shpl_upconv3x3_wgrad(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
+                         int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b,
+                         const shpl_csr *pool, const int64_t *d_frame_off, const void *d_gy, int64_t gy_stride,
+                         int64_t c_out, float *d_dw /* f32 HWOI [3][3][c_out][c_a+c_b] */, void *d_ws,
+                         size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------
  * 1x1 heads over the fused map, the SHPL applied after the projection
  * (MV3D's rpn_cls_score / rpn_bbox_pred)

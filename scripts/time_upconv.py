@@ -1,12 +1,14 @@
 """Times the after-VGG upconv3 (fusion_vgg_pyramid.py:53-60, :198-206) at the reference's shapes: BEV 88x100 and
 image 45x150 (stride 8 of 704x800 and 1200x360), 256 + 256 -> 128 channels, 20 k points per frame, 8 frames, in
-bf16 and in f32, both sides. Three forms, alternated in one process after a warm-up, each call between two HIP
+bf16 and in f32, both sides. The forms, alternated in one process after a warm-up, each call between two HIP
 events on the current stream:
 
-  fused    FusionUpconv.fused / .fused_img: shpl_upconv3x3 with the pooling in its staging (no pooled map, no concat);
-  phases   FusionUpconv.forward_phases: shpl_conv3x3 with phase_weights (4 c_out channels, 27 of 36 taps zero),
-           then depth_to_space; its training step is the fused form's (the backward is the phase route already),
-           so only its forward is timed;
+  fused    FusionUpconv.fused / .fused_img: shpl_upconv3x3 with the pooling in its staging (no pooled map, no
+           concat); its training step runs backward="direct" (shpl_upconv3x3_dgrad / shpl_upconv3x3_wgrad);
+  fused_phases  (training step only) the same module with backward="phases": the gradients through
+           shpl_conv3x3_dgrad / shpl_conv3x3_wgrad with phase_weights -- the comparator of the direct backward;
+  phases   (forward only) FusionUpconv.forward_phases: shpl_conv3x3 with phase_weights (4 c_out channels, 27 of 36
+           taps zero), then depth_to_space;
   unfused  the pull with the concat fused in (shpl_map.pool_*), torch.nn.functional.conv_transpose2d on the
            materialised map, cropped to 2h x 2w, then the same BatchNorm call (shpl_batch_norm; inference: the same
            affine map and ReLU in torch).
@@ -75,14 +77,17 @@ def main():
             b = maps[other].detach().clone().requires_grad_(True)
             ca, cb = int(a.shape[-1]), int(b.shape[-1])
             h, w = hw[side_name]
-            up = fu.FusionUpconv(ca + cb, C_OUT, dtype=dtype, device=dev, seed=0)
+            up = fu.FusionUpconv(ca + cb, C_OUT, dtype=dtype, device=dev, seed=0, backward="direct")
             up.weights.requires_grad_(True)
             up.beta.requires_grad_(True)
+            up_ph = fu.FusionUpconv(ca + cb, C_OUT, dtype=dtype, device=dev, seed=0, backward="phases")
+            up_ph.weights, up_ph.beta = up.weights, up.beta  # one set of variables, two backward routes
             gy = torch.randn((F, 2 * h, 2 * w, C_OUT), device=dev, generator=g).to(dtype)
             pool, fo = smap.csr(*side.fwd), smap.frame_off
 
-            def fused(training):
-                return (up.fused if side_name == "bev" else up.fused_img)(a, b, smap, is_training=training)
+            def fused(training, m=None):
+                m = up if m is None else m
+                return (m.fused if side_name == "bev" else m.fused_img)(a, b, smap, is_training=training)
 
             def phases(training):
                 return up.forward_phases(a, b, pool, fo, is_training=training)
@@ -113,10 +118,13 @@ def main():
                         return r[0] if isinstance(r, tuple) else r
                 return step
 
-            def train_fused():
+            def train_fused(m=None):
                 for t in (a, b, up.weights, up.beta):
                     t.grad = None
-                fused(True).backward(gy)
+                fused(True, m).backward(gy)
+
+            def train_fused_phases():
+                train_fused(up_ph)
 
             def train_unfused():
                 # forward as above; backward: the library's BatchNorm backward, torch's autograd through the
@@ -134,13 +142,14 @@ def main():
 
             with torch.no_grad():
                 ref = fused(False).float()
-                diff = {"fused": 0.0, "phases": float((phases(False).float() - ref).abs().max().item()),
+                diff = {"fused": 0.0, "fused_phases": 0.0,
+                        "phases": float((phases(False).float() - ref).abs().max().item()),
                         "unfused": float((unfused(False)[0].float() - ref).abs().max().item())}
             rows_a, rows_b = F * h * w, b.numel() // cb
             model_bytes = (rows_a * ca + rows_b * cb) * esz + 4 * rows_a * C_OUT * esz
             model_flops = 2 * rows_a * 9 * (ca + cb) * C_OUT
             steps = (("forward", {"fused": fwd(fused), "phases": fwd(phases), "unfused": fwd(unfused)}),
-                     ("train", {"fused": train_fused, "unfused": train_unfused}))
+                     ("train", {"fused": train_fused, "fused_phases": train_fused_phases, "unfused": train_unfused}))
             for step, forms in steps:
                 for _ in range(args.warmup):
                     for fn in forms.values():
@@ -169,7 +178,7 @@ def main():
                         rec["fraction_of_8TBps"] = round((model_bytes + extra) / 8e12 * 1e3 / med, 4)
                         rec["fraction_of_mfma_peak"] = round(model_flops / PEAK_FLOPS[name] * 1e3 / med, 4)
                     print(json.dumps(rec), flush=True)
-            del a, b, up, gy
+            del a, b, up, up_ph, gy
             torch.cuda.empty_cache()
 
 

@@ -189,6 +189,11 @@ def _declare(lib):
         "shpl_upconv3x3_workspace_bytes": (i32, [i32, i32, i64, i64, i64, i64, i64, i64, i32, psz]),
         "shpl_upconv3x3": (i32, [i32, i32, i64, i64, p, i64, i64, i64, p, i64, i64, i64,
                                  ctypes.POINTER(ShplCsr), p, p, i64, p, p, p, i32, p, i64, p, p, sz, p]),
+        "shpl_upconv3x3_dgrad_workspace_bytes": (i32, [i32, i32, i64, i64, i64, i64, psz]),
+        "shpl_upconv3x3_dgrad": (i32, [i32, i32, i64, i64, p, i64, i64, p, i64, p, i64, i64, p, i64, p, sz, p]),
+        "shpl_upconv3x3_wgrad_workspace_bytes": (i32, [i32, i32, i64, i64, i64, i64, i64, i64, psz]),
+        "shpl_upconv3x3_wgrad": (i32, [i32, i32, i64, i64, p, i64, i64, i64, p, i64, i64, i64,
+                                       ctypes.POINTER(ShplCsr), p, p, i64, i64, p, p, sz, p]),
         "shpl_head1x1_workspace_bytes": (i32, [i32, i64, i64, i64, i64, i64, i32, psz]),
         "shpl_head1x1": (i32, [i32, i64, p, i64, i64, i64, p, i64, i64, i64, i64, ctypes.POINTER(ShplCsr), p, i64,
                                p, p, i64, p, sz, p]),

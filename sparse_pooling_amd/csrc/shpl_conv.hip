@@ -1048,13 +1048,7 @@ int wgrad_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64
     const int Q = wp->cp.qa + wp->cp.qb;
     wp->n_cib = (Q * wp->cp.ck + WG_CI - 1) / WG_CI;
     const int64_t blocks_per_group = (int64_t)wp->n_cib * wp->cp.n_cob;
-    int64_t ng = 1024 / blocks_per_group;
-    if (ng < 1) ng = 1;
-    if (ng > wp->cp.n_tiles) ng = wp->cp.n_tiles > 0 ? wp->cp.n_tiles : 1;
-    wp->tiles_per_group = (int)((wp->cp.n_tiles + ng - 1) / ng);
-    if (wp->tiles_per_group < 1) wp->tiles_per_group = 1;
-    wp->n_groups = (int)((wp->cp.n_tiles + wp->tiles_per_group - 1) / wp->tiles_per_group);
-    if (wp->n_groups < 1) wp->n_groups = 1;
+    wgrad_groups(wp->cp.n_tiles, blocks_per_group, &wp->tiles_per_group, &wp->n_groups);
     Layout t;
     wp->row_ptr = t.take(pooled ? (size_t)n_frames * (h + 1) * 4 : 0);
     wp->part = t.take((size_t)wp->n_groups * blocks_per_group * 9 * WG_CI * NCO * sizeof(float));

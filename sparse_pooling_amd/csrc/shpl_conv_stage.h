@@ -171,11 +171,10 @@ struct HaloRuns {
 // Lists the runs of the halo of output tile (f, y0, x0): per halo
 // row the entry range of cells [x0-1, x0-1+HWD_) (row pointers + counting the
 // row's sorted entries below each bound), then one block scan in entry
-// order. Every thread of the 256 calls it.
+// order. Every thread of the 256 calls it (tid: its index; a caller may hand it in opaque, as to conv_stage).
 template <int HH_ = HH, int HWD_ = HWD>
-__device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRuns &r) {
+__device__ int find_runs(const ConvArgs &p, int f, int y0, int x0, const HaloRuns &r, int tid = threadIdx.x) {
     constexpr int NPIX = HH_ * HWD_;
-    const int tid = threadIdx.x;
     const int H = p.h, W = p.w;
     const int64_t frame_row0 = (int64_t)f * H * W;
     for (int j = tid; j < NPIX; j += CONV_BLOCK) r.occ[j] = 0;
@@ -494,6 +493,18 @@ struct Layout {
 template <typename T>
 T *region(const void *ws, size_t at) {
     return ws ? reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(const_cast<void *>(ws)) + at) : nullptr;
+}
+
+// The tiled weight gradients' cut of n_tiles tiles into groups, one partial per (group, channel block pair): about
+// 1024 workgroups in all, which bounds the partials' bytes; a group holds at least one tile.
+void wgrad_groups(int64_t n_tiles, int64_t blocks_per_group, int *tiles_per_group, int *n_groups) {
+    int64_t ng = 1024 / blocks_per_group;
+    if (ng < 1) ng = 1;
+    if (ng > n_tiles) ng = n_tiles > 0 ? n_tiles : 1;
+    *tiles_per_group = (int)((n_tiles + ng - 1) / ng);
+    if (*tiles_per_group < 1) *tiles_per_group = 1;
+    *n_groups = (int)((n_tiles + *tiles_per_group - 1) / *tiles_per_group);
+    if (*n_groups < 1) *n_groups = 1;
 }
 
 // A pool counts as pixel-keyed (shpl_build_csr SHPL_BY_PIXEL, SHPL_ORDER_COL_ROW: the keys are image pixels, the

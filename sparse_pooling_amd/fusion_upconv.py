@@ -20,15 +20,21 @@ pad_total // 2 = 0, pad_after = 1):
 (shpl_upconv3x3): the fused conv4 never reaches HBM, and the result is bitwise that of the materialised map.
 ``fused_img`` is the image side from the BEV->img CSR. ``AfterVggFusion`` holds both upconv3 scopes.
 
-The four output parities (oy & 1, ox & 1) are four stride-1 convs over the 2 x 2 window x[i-1..i, j-1..j]:
-``phase_weights`` writes them as ONE stride-1 3x3 SAME conv to 4 c_out channels whose taps are 9 of 36 nonzero.
-The forward kernel does not take that route (it runs each tap once, into the parity it belongs to). The BACKWARD
-does, on the kernels the library already has: BatchNorm/ReLU backward over the 2h x 2w rows, the gradient through
-``space_to_depth``, then shpl_conv3x3_dgrad and shpl_conv3x3_wgrad with ``phase_weights(W)`` -- the pooled
-channels recomputed from the CSR, their gradient carried back by the side's pull, the weight gradient gathered
-back to HWOI by ``phase_weight_grad``. That is 4x the MFMA work the gradients need (the zero taps are multiplied
-too) and never stores the fused map; dedicated gradient kernels are a follow-up. One stream, plain calls.
-``FusionUpconv.forward_phases`` is the forward by the same route (a cross-check and a timing comparator).
+The backward (``FusionUpconv(backward=...)``), after BatchNorm/ReLU backward over the 2h x 2w rows:
+
+``"direct"`` (the default): the transposed conv's own gradient kernels on the raw output's gradient --
+``upconv3x3_dgrad`` (shpl_upconv3x3_dgrad: the nine taps over the four parity planes of gy, one staged chunk
+feeding up to four blocks of 32 input channels; the pooled half written to a dense map and carried back to the
+pooled source by the side's pull) and ``upconv3x3_wgrad`` (shpl_upconv3x3_wgrad: the pooled channels recomputed
+from the CSR in the staging, never stored). 9 c_in c_out multiply-adds per input pixel each.
+
+``"phases"``: the four output parities (oy & 1, ox & 1) are four stride-1 convs over the 2 x 2 window
+x[i-1..i, j-1..j]; ``phase_weights`` writes them as ONE stride-1 3x3 SAME conv to 4 c_out channels whose taps are
+9 of 36 nonzero, and the gradients go through ``space_to_depth``, shpl_conv3x3_dgrad and shpl_conv3x3_wgrad with
+``phase_weights(W)``, the weight gradient gathered back to HWOI by ``phase_weight_grad``. 4x the MFMA work (the
+zero taps are multiplied too); kept as the comparator of the direct route (scripts/time_upconv.py, DESIGN.md §8
+item 6). ``FusionUpconv.forward_phases`` is the forward by the same route, in the same spirit.
+One stream, plain calls; neither route stores the fused map.
 """
 from __future__ import annotations
 
@@ -138,8 +144,82 @@ def upconv3x3(a, weights, b=None, pool=None, frame_off=None, center=None, scale=
     return out
 
 
+def upconv_grad_ws_bytes(which, dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap=None):
+    """Workspace of shpl_upconv3x3_dgrad (which = "dgrad": c_a = c_gy, c_out = c_dx, c_b and pool_cap unused) or
+    of shpl_upconv3x3_wgrad (which = "wgrad"; pool_cap: the pooling CSR's entry capacity, or None without a pool).
+    h, w: the INPUT map's size."""
+    out = ctypes.c_size_t()
+    if which == "dgrad":
+        L.check(L.lib().shpl_upconv3x3_dgrad_workspace_bytes(dtype, int(n_frames), int(h), int(w), int(c_a),
+                                                             int(c_out), ctypes.byref(out)),
+                "shpl_upconv3x3_dgrad_workspace_bytes")
+    elif which == "wgrad":
+        L.check(L.lib().shpl_upconv3x3_wgrad_workspace_bytes(dtype, int(n_frames), int(h), int(w), int(c_a),
+                                                             int(c_b), int(c_out),
+                                                             -1 if pool_cap is None else int(pool_cap),
+                                                             ctypes.byref(out)),
+                "shpl_upconv3x3_wgrad_workspace_bytes")
+    else:
+        raise ValueError(f"which = {which!r}: 'dgrad' or 'wgrad'")
+    return out.value
+
+
+def upconv3x3_dgrad(gy, weights, c_dx, split=None, ws=None):
+    """Input gradient [B,H,W,c_dx] of ``upconv3x3`` with its HWOI ``weights`` [3,3,Cout,c_dx]: gy is the gradient
+    of the raw output, [B,2H,2W,Cout] (its last dimension dense; rows may be a view into a wider buffer). With
+    ``split`` = c, the pair (channels [0, c), channels [c, c_dx)) as two dense maps written by the kernel's
+    epilogue (shpl_upconv3x3_dgrad)."""
+    if gy.stride(-1) != 1 or gy.stride(2) < gy.shape[3] or gy.stride(1) != gy.stride(2) * gy.shape[2] \
+            or gy.stride(0) != gy.stride(1) * gy.shape[1]:
+        gy = gy.contiguous()
+    B, H2, W2, Cg = (int(s) for s in gy.shape)
+    if H2 % 2 or W2 % 2:
+        raise ValueError(f"the output gradient {tuple(gy.shape)} is not 2H x 2W")
+    H, W = H2 // 2, W2 // 2
+    weights = weights.to(gy.dtype).contiguous()
+    c_dx = int(c_dx)
+    if tuple(weights.shape) != (3, 3, Cg, c_dx):
+        raise ValueError(f"weights {tuple(weights.shape)} (HWOI) do not match {Cg} -> {c_dx} channels")
+    dt = L.dtype_code(gy)
+    c0 = c_dx if split is None else int(split)
+    dx = torch.empty((B, H, W, c0), dtype=gy.dtype, device=gy.device)
+    dx_b = None if split is None else torch.empty((B, H, W, c_dx - c0), dtype=gy.dtype, device=gy.device)
+    if ws is None:
+        ws = L.workspace(upconv_grad_ws_bytes("dgrad", dt, B, H, W, Cg, 0, c_dx), gy.device)
+    L.check(L.lib().shpl_upconv3x3_dgrad(dt, B, H, W, L.ptr(gy), int(gy.stride(2)), Cg, L.ptr(weights), c_dx,
+                                         L.ptr(dx), max(c0, 1), c0, L.ptr(dx_b), max(c_dx - c0, 1), L.ptr(ws),
+                                         ws.numel(), L.stream_of(gy.device)), "shpl_upconv3x3_dgrad")
+    return dx if split is None else (dx, dx_b)
+
+
+def upconv3x3_wgrad(a, gy, b=None, pool=None, frame_off=None, ws=None):
+    """Weight gradient (f32 HWOI [3,3,Cout,Ca+Cb]) of ``upconv3x3`` of [a || b]: b dense, pooled through ``pool``
+    (recomputed in the staging, never stored) or absent, as ``upconv3x3`` takes it; gy the gradient of the raw
+    output, [B,2H,2W,Cout] (shpl_upconv3x3_wgrad)."""
+    a = a.contiguous()
+    gy = gy.contiguous()
+    dt = L.dtype_code(a)
+    B, H, W, Ca = (int(s) for s in a.shape)
+    Cb = 0 if b is None else int(b.shape[-1])
+    if b is not None:
+        b = b.contiguous()
+    Cout = int(gy.shape[-1])
+    if tuple(gy.shape[:3]) != (B, 2 * H, 2 * W) or gy.dtype != a.dtype:
+        raise ValueError(f"the output gradient {tuple(gy.shape)} {gy.dtype} does not match the input {tuple(a.shape)}")
+    dw = torch.empty((3, 3, Cout, Ca + Cb), dtype=torch.float32, device=a.device)
+    if ws is None:
+        ws = L.workspace(upconv_grad_ws_bytes("wgrad", dt, B, H, W, Ca, Cb, Cout,
+                                              None if pool is None else pool.nnz_cap), a.device)
+    L.check(L.lib().shpl_upconv3x3_wgrad(dt, B, H, W, L.ptr(a), Ca, 0, Ca, L.ptr(b), Cb, 0, Cb,
+                                         None if pool is None else pool.ref(), L.ptr(frame_off), L.ptr(gy), Cout,
+                                         Cout, L.ptr(dw), L.ptr(ws), ws.numel(), L.stream_of(a.device)),
+            "shpl_upconv3x3_wgrad")
+    return dw
+
+
 class _FusionUpconvFn(torch.autograd.Function):
-    """FusionUpconv forward + the TF-autodiff backward of the same graph, by the phase route (module docstring).
+    """FusionUpconv forward + the TF-autodiff backward of the same graph, by the module's route (``up.backward``,
+    module docstring).
     Inputs: a [B,H,W,Ca]; b: None, or -- with side -- the other map, pooled through smap; the HWOI weights; beta."""
 
     @staticmethod
@@ -169,14 +249,25 @@ class _FusionUpconvFn(torch.autograd.Function):
                                                   training=ctx.train_bn, beta=beta)
         else:
             g_raw, dbeta = gy, None
-        g_ph = space_to_depth(g_raw).contiguous()
+        pool = smap.csr(*side.fwd) if pooled else None
+        frame_off = smap.frame_off if pooled else None
+        direct = up.backward == "direct"
+        g_ph = None if direct else space_to_depth(g_raw).contiguous()
+        B, H, W = (int(s) for s in a.shape[:3])
+        dt = L.dtype_code(a)
         d_a = d_b = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            w_ph = phase_weights(weights.to(a.dtype))
-            if b is None:
-                d_a = conv3x3_dgrad(g_ph, w_ph, Ca)
+            split = None if b is None else Ca
+            if direct:
+                ws = up._ws_for(("up_dgrad", dt, B, H, W, Cb),
+                                upconv_grad_ws_bytes("dgrad", dt, B, H, W, up.c_out, 0, Ca + Cb))
+                dx = upconv3x3_dgrad(g_raw, weights, Ca + Cb, split=split, ws=ws)
             else:
-                d_a, dx_b = conv3x3_dgrad(g_ph, w_ph, Ca + Cb, split=Ca)
+                dx = conv3x3_dgrad(g_ph, phase_weights(weights.to(a.dtype)), Ca + Cb, split=split)
+            if b is None:
+                d_a = dx
+            else:
+                d_a, dx_b = dx
                 if ctx.needs_input_grad[1]:
                     # the pooled channels' gradient back to the pooled source (_Side.grad), as FusionConv's
                     d_b = torch.empty(b.shape, dtype=dx_b.dtype, device=dx_b.device)
@@ -184,9 +275,13 @@ class _FusionUpconvFn(torch.autograd.Function):
             if not ctx.needs_input_grad[0]:
                 d_a = None
         if ctx.needs_input_grad[2]:
-            dw_ph = conv3x3_wgrad(a, g_ph, b=b, pool=smap.csr(*side.fwd) if pooled else None,
-                                  frame_off=smap.frame_off if pooled else None)
-            dw = phase_weight_grad(dw_ph).to(weights.dtype)
+            if direct:
+                cap = None if pool is None else pool.nnz_cap
+                ws = up._ws_for(("up_wgrad", dt, B, H, W, Cb, cap),
+                                upconv_grad_ws_bytes("wgrad", dt, B, H, W, Ca, Cb, up.c_out, cap))
+                dw = upconv3x3_wgrad(a, g_raw, b=b, pool=pool, frame_off=frame_off, ws=ws).to(weights.dtype)
+            else:
+                dw = phase_weight_grad(conv3x3_wgrad(a, g_ph, b=b, pool=pool, frame_off=frame_off)).to(weights.dtype)
         d_beta = dbeta if (up.batch_norm and ctx.needs_input_grad[3]) else None
         return d_a, d_b, dw, d_beta, None, None, None, None, None
 
@@ -196,8 +291,17 @@ class FusionUpconv(FusionConv):
     ``upconv3`` scope and its forward. ``weights`` is slim's HWOI variable [3,3,c_out,c_in] (xavier-uniform);
     beta, the moving statistics and the device-resident inference scale are kept as ``FusionConv`` keeps them."""
 
+    DEFAULT_BACKWARD = "direct"
+    BACKWARDS = ("direct", "phases")
+
     def __init__(self, c_in, c_out, batch_norm=True, relu=True, eps=1e-3, decay=0.999, dtype=torch.float32,
-                 device="cuda", seed=0):
+                 device="cuda", seed=0, backward=None):
+        """backward: "direct" -- shpl_upconv3x3_dgrad / shpl_upconv3x3_wgrad on the raw output's gradient -- or
+        "phases", the stride-1 phase conv's gradients (module docstring); None: DEFAULT_BACKWARD."""
+        backward = self.DEFAULT_BACKWARD if backward is None else backward
+        if backward not in self.BACKWARDS:
+            raise ValueError(f"backward = {backward!r}: one of {self.BACKWARDS}")
+        self.backward = backward
         super().__init__(c_in, c_out, batch_norm=batch_norm, bias=False, relu=relu, eps=eps, decay=decay,
                          dtype=dtype, device=device, seed=seed)
         g = np.random.default_rng(seed)
