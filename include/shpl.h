@@ -49,6 +49,9 @@ typedef enum {
 #define SHPL_EBIT_CAPACITY 16u /* a frame holds more points than max_points_per_frame */
 #define SHPL_EBIT_BARRIER 32u  /* shpl_build_index_buckets' one-launch form gave up waiting at a frame barrier
                                   (its chunks were not all resident: results of that call are invalid) */
+#define SHPL_EBIT_GATHER 64u   /* shpl_mv3d_augment_points / shpl_mv3d_voxels_aug: a remain_index entry outside its
+                                  frame (the point is skipped), or frame offsets outside the arrays (the frame is
+                                  treated as empty); nothing is read through either */
 
 typedef enum { SHPL_F32 = 0, SHPL_BF16 = 1, SHPL_F64 = 2 } shpl_dtype;
 typedef enum { SHPL_I32 = 0, SHPL_I64 = 1 } shpl_itype;
@@ -231,6 +234,45 @@ int shpl_mv3d_voxels(int n_frames, const int64_t *d_point_offsets, int64_t total
                      double zres, int voxel_point_count, double *d_img_index, int64_t ld, int64_t *d_bv_index,
                      double *d_mval, int64_t *d_frame_n, int32_t *d_number_buffer,
                      int64_t *d_frame_nvox, void *d_ws, size_t ws_bytes, void *stream);
+
+/* MV3D_TF's training augmentation augment_voxel (MV3D_TF_release/lib/roi_data_layer/
+ * minibatch_mv3d_img.py:132-189; cfg.TRAIN.AUGMENT_BV, on by default), the cloud half, n_frames at once.
+ *   d_points     [N, point_stride] camera-frame points (x, y, z, r), point_dtype SHPL_F32 or SHPL_F64: the
+ *                type T the reference's cloud is stored in -- it rounds to T after every step
+ *   d_vox_aug    [n_frames, 8] f64: sx, sz, ratio, r00, r01, r10, r11, 0 -- the drawn shift and expansion
+ *                ratio and rot = [[cos, sin], [-sin, cos]] of the drawn angle, formed on the host
+ *   d_remain_index, d_remain_offsets  optional (both or neither), cfg.TRAIN.AUGMENT_PC: frame f's cloud becomes
+ *                points[remain_index[roff[f] .. roff[f+1])] in that order, indices local to the frame, repeats
+ *                allowed; total_out = roff[n_frames]. Without them total_out = total_points.
+ * Per out point: (u, v) = round(project(P_f, ORIGINAL x, y, z)); x1 = T(x + sx), z1 = T(z + sz);
+ * (x2, y2, z2) = T((x1, y, z1) * ratio); (x3, z3) = T(rot . (x2, z2)) in np.dot's order -- every step in f64,
+ * unfused except np.dot's own chain, rounded once to T. A frame of one out point takes np.dot's one-column
+ * orders, for the projection and the rotation.
+ * shpl_mv3d_augment_points writes d_cloud [total_out, 4] f64 = (x3, y2, z3, r) (T's values widened; 16-byte
+ * aligned; point_stride >= 4) and d_img_index2 [2, ld] i64 (ld >= total_out): shpl_mv3d_voxels' inputs.
+ * shpl_mv3d_voxels_aug is shpl_mv3d_voxels over that cloud without writing it: both passes of the frame kernel
+ * read the original point through the gather, augment it in registers and key the voxel on the result; the
+ * image index is the ORIGINAL's (d_P, or d_img_index2 [2, total_points] indexed by the source point), and
+ * d_fv_aug applies on top. Outputs and workspace are laid out by OUT point: ld >= total_out,
+ * shpl_mv3d_workspace_bytes(total_out). On an f32 cloud the range tests and voxel indices run in f32 with the
+ * bounds rounded to f32, as numpy runs point_cloud_2_top_sparse on an f32 array; shpl_mv3d_voxels over the widened
+ * d_cloud runs them in f64, which can place a point at a voxel boundary differently.
+ * Status: null or inconsistent pointers SHPL_ERR_ARG; point_dtype not SHPL_F32 / SHPL_F64, negative totals or
+ * total_out != total_points without a gather SHPL_ERR_BAD_SHAPE. The offsets and remain_index live on the device
+ * and are bounded there: *d_err (nullable) gets SHPL_EBIT_GATHER, see above. */
+int shpl_mv3d_augment_points(int n_frames, const int64_t *d_point_offsets, int64_t total_points,
+                             const void *d_points, int point_dtype, int64_t point_stride, const double *d_P,
+                             const double *d_vox_aug, const int64_t *d_remain_index,
+                             const int64_t *d_remain_offsets, int64_t total_out, double *d_cloud,
+                             int64_t *d_img_index2, int64_t ld, uint32_t *d_err, void *stream);
+int shpl_mv3d_voxels_aug(int n_frames, const int64_t *d_point_offsets, int64_t total_points,
+                         const void *d_points, int point_dtype, int64_t point_stride,
+                         const int64_t *d_img_index2, const double *d_P, const double *d_fv_aug,
+                         const double *d_vox_aug, const int64_t *d_remain_index,
+                         const int64_t *d_remain_offsets, int64_t total_out, const double *ranges, double res,
+                         double zres, int voxel_point_count, double *d_img_index, int64_t ld,
+                         int64_t *d_bv_index, double *d_mval, int64_t *d_frame_n, int32_t *d_number_buffer,
+                         int64_t *d_frame_nvox, uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * KITTI velodyne loader: the BEV voxelizer's input

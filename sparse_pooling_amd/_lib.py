@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("SHPL_LIB") or os.path.join(_HERE, "libshpl.so")
 
 # enums of include/shpl.h
 OK, ERR_BAD_SHAPE, ERR_INDEX_OOB, ERR_HIP, ERR_WORKSPACE, ERR_ARG = range(6)
-EBIT_ROW, EBIT_COL, EBIT_PIXEL, EBIT_VALUES, EBIT_CAPACITY, EBIT_BARRIER = 1, 2, 4, 8, 16, 32
+EBIT_ROW, EBIT_COL, EBIT_PIXEL, EBIT_VALUES, EBIT_CAPACITY, EBIT_BARRIER, EBIT_GATHER = 1, 2, 4, 8, 16, 32, 64
 F32, BF16, F64 = 0, 1, 2
 I32, I64 = 0, 1
 BY_CELL, BY_PIXEL = 0, 1
@@ -138,6 +138,9 @@ def _declare(lib):
         "shpl_mv3d_workspace_bytes": (i32, [i64, psz]),
         "shpl_mv3d_voxels": (i32, [i32, p, i64, p, i64, p, p, p, p, d, d, i32, p, i64, p, p, p, p, p, p,
                                    sz, p]),
+        "shpl_mv3d_augment_points": (i32, [i32, p, i64, p, i32, i64, p, p, p, p, i64, p, p, i64, p, p]),
+        "shpl_mv3d_voxels_aug": (i32, [i32, p, i64, p, i32, i64, p, p, p, p, p, p, i64, p, d, d, i32, p, i64, p, p, p,
+                                       p, p, p, p, sz, p]),
         "shpl_bev_slices": (i32, [i32, p, p, i64, p, i32, p, p, d, i32, p, p, d, d, d, p, p, p, p, p, p,
                                   p, p, sz, p]),
         "shpl_bev_maps": (i32, [i32, p, i64, p, i32, p, p, d, i32, p, p, d, d, d, p, p, p, i32, p, sz, p]),

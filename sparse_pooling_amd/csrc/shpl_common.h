@@ -182,6 +182,15 @@ __device__ __forceinline__ double dot4(const double *row, double a0, double a1, 
     return gemv ? dot4_gemv(row, a0, a1, a2) : dot4_chain(row, a0, a1, a2);
 }
 
+// One row of a 2x2 matrix times [a0; a1] as np.dot evaluates it (MV3D's rotation about the camera's y axis,
+// minibatch_mv3d_img.py:185). N >= 2 columns (dgemm): dot4_chain's order at K = 2, the first product rounded
+// and the second fused onto it. One column (dgemv): the SECOND product rounded and the first fused onto it
+// (probed against np.dot; "two products, one add" differs from both). Pinned by tests/golden/mv3d_augment_f64*
+// and mv3d_augment_one_f64.
+__device__ __forceinline__ double dot2(const double *row, double a0, double a1, bool gemv) {
+    return gemv ? __fma_rn(row[0], a0, __dmul_rn(row[1], a1)) : __fma_rn(row[1], a1, __dmul_rn(row[0], a0));
+}
+
 // projectToImage (avod/avod/utils/transform.py:3-26; calib_utils.project_to_image
 // :281-298): [u;v;w] = P [x;y;z;1]; u/=w; v/=w (IEEE division). gemv: the
 // product had one column (see dot4_gemv).

@@ -17,6 +17,15 @@
 // (shpl_tilesort.h); the thread at the start of each voxel run marks the run's
 // first VOXEL_POINT_COUNT points accepted with weight 1/min(run, cap); a
 // ballot compaction then emits the accepted points in point order.
+//
+// augment_voxel (minibatch_mv3d_img.py:132-189; cfg.TRAIN.AUGMENT_BV, the training default) sits in front of
+// the producer: an optional redraw of the cloud (points[remain_index]), the projection of the ORIGINAL points
+// (img_index2), then shift, scale and a rotation about the camera's y axis of the coordinates the voxels are
+// keyed on. k_mv3d_augment writes that cloud and img_index2; k_mv3d_frame<T, true> does the same per point in
+// registers, where it forms the voxel words and again where it emits the accepted points, and writes neither.
+// T is the cloud's storage type: the reference rounds to it after every step, and on an f32 cloud numpy also
+// runs the producer's range tests and voxel indices in f32 (python-float bounds do not promote an f32 array),
+// so voxel_key<float> does.
 #include "shpl_tilesort.h"
 
 namespace shpl {
@@ -41,39 +50,167 @@ __device__ __forceinline__ void project_round(const double *P, double x, double 
     v = (int64_t)rint(vf);
 }
 
-// voxel key of camera-frame point (x, y, z) or -1 when outside the ranges
-__device__ __forceinline__ int64_t voxel_key(const Mv3dGeom &g, double x, double y, double z, int &si, int &fi) {
-    const double fwd = z, side = x, h = y;  // points[:, [2, 0, 1, 3]]
-    if (!(fwd > g.fwd_lo && fwd < g.fwd_hi && side > g.side_lo && side < g.side_hi && h > g.h_lo && h < g.h_hi))
+__device__ __forceinline__ double sub_rn(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ double div_rn(double a, double b) { return __ddiv_rn(a, b); }
+__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
+
+// voxel key of camera-frame point (x, y, z) or -1 when outside the ranges, in the cloud's type T (the bounds
+// and sizes rounded to it, as numpy rounds python floats beside an f32 array)
+template <typename T>
+__device__ __forceinline__ int64_t voxel_key(const Mv3dGeom &g, T x, T y, T z, int &si, int &fi) {
+    const T fwd = z, side = x, h = y;  // points[:, [2, 0, 1, 3]]
+    if (!(fwd > (T)g.fwd_lo && fwd < (T)g.fwd_hi && side > (T)g.side_lo && side < (T)g.side_hi && h > (T)g.h_lo &&
+          h < (T)g.h_hi))
         return -1;
-    si = (int)__ddiv_rn(__dsub_rn(side, g.side_lo), g.res);
-    fi = (int)__ddiv_rn(__dsub_rn(fwd, g.fwd_lo), g.res);
-    const int hi = (int)__ddiv_rn(__dsub_rn(h, g.h_lo), g.zres);
+    si = (int)div_rn(sub_rn(side, (T)g.side_lo), (T)g.res);
+    fi = (int)div_rn(sub_rn(fwd, (T)g.fwd_lo), (T)g.res);
+    const int hi = (int)div_rn(sub_rn(h, (T)g.h_lo), (T)g.zres);
+    if constexpr (!std::is_same<T, double>::value) {
+        // f64 quotients are monotone below the host's f64 sizes; f32 roundings of caller-chosen ranges need
+        // not be: a cell outside the grid is no voxel (the sort's tiles are sized for the grid)
+        if (si >= g.n_side || fi >= g.n_fwd || hi >= g.n_h) return -1;
+    }
     return ((int64_t)si * g.n_fwd + fi) * g.n_h + hi;
 }
 
-__global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64_t *pt_off, const double *pts,
+// augment_voxel's device arguments (the augmented instantiations only)
+template <bool AUG>
+struct Mv3dAug {};
+template <>
+struct Mv3dAug<true> {
+    const double *vox_aug;   // [F, 8]: sx, sz, ratio, r00, r01, r10, r11, 0
+    const int64_t *remain;   // optional [n_out]: frame-local source point of each out point (AUGMENT_PC)
+    const int64_t *out_off;  // [F + 1] out points of each frame (the point offsets without remain)
+    int64_t n_in, n_out;     // points, out points over all frames: every offset is held inside them
+    uint32_t *err;           // nullable: SHPL_EBIT_GATHER
+};
+
+// Frame f's out points [p0, p1) and source points [q0, q0 + nq): offsets outside the arrays, decreasing, or
+// (no remain) unequal counts make the frame empty and set SHPL_EBIT_GATHER -- nothing is read through them.
+__device__ __forceinline__ void aug_frame(const Mv3dAug<true> &ag, const int64_t *pt_off, int f, int64_t &p0,
+                                          int64_t &p1, int64_t &q0, int64_t &nq) {
+    p0 = ag.out_off[f];
+    p1 = ag.out_off[f + 1];
+    q0 = pt_off[f];
+    nq = pt_off[f + 1] - q0;
+    if (p0 < 0 || p1 < p0 || p1 > ag.n_out || q0 < 0 || nq < 0 || nq > ag.n_in - q0 || (!ag.remain && nq != p1 - p0)) {
+        if (threadIdx.x == 0 && ag.err) atomicOr(ag.err, SHPL_EBIT_GATHER);
+        p0 = p1 = q0 = nq = 0;
+    }
+}
+
+// Source row of out point i of a frame (aug_frame's ranges), or -1 for a remain_index entry outside the frame
+// (SHPL_EBIT_GATHER; the point is skipped, never read).
+__device__ __forceinline__ int64_t aug_source(const Mv3dAug<true> &ag, int64_t i, int64_t p0, int64_t q0, int64_t nq) {
+    if (!ag.remain) return q0 + (i - p0);
+    const int64_t r = ag.remain[i];
+    if (r < 0 || r >= nq) {
+        if (ag.err) atomicOr(ag.err, SHPL_EBIT_GATHER);
+        return -1;
+    }
+    return q0 + r;
+}
+
+// augment_voxel's cloud half for one point (minibatch_mv3d_img.py:180-185), every step in f64 and rounded to
+// the cloud's type T, as numpy's in-place operators do with f64 operands: += sx / sz, *= ratio, then the
+// rotation np.dot(rot, [x; z]) (dot2) rounded once. gemv: the frame has one out point.
+template <typename T>
+__device__ __forceinline__ void augment_point(const double *a, bool gemv, T &x, T &y, T &z) {
+    const T x1 = (T)__dadd_rn((double)x, a[0]), z1 = (T)__dadd_rn((double)z, a[1]);
+    const T x2 = (T)__dmul_rn((double)x1, a[2]), z2 = (T)__dmul_rn((double)z1, a[2]);
+    y = (T)__dmul_rn((double)y, a[2]);
+    x = (T)dot2(a + 3, (double)x2, (double)z2, gemv);
+    z = (T)dot2(a + 5, (double)x2, (double)z2, gemv);
+}
+
+// A frame's out point i: the coordinates the voxel is keyed on in (x, y, z), the ORIGINAL point's in (ox, oy,
+// oz) -- what the image sees -- and its row in the cloud (src). false: no such point (a bad remain entry).
+template <typename T, bool AUG>
+__device__ __forceinline__ bool frame_point(const Mv3dAug<AUG> &ag, const T *pts, int64_t pt_stride, int f, int64_t i,
+                                            int64_t p0, int64_t p1, int64_t q0, int64_t nq, T &x, T &y, T &z, T &ox,
+                                            T &oy, T &oz, int64_t &src) {
+    if constexpr (AUG) {
+        src = aug_source(ag, i, p0, q0, nq);
+        if (src < 0) return false;
+    } else {
+        src = i;
+    }
+    const T *q = pts + src * pt_stride;
+    x = ox = q[0];
+    y = oy = q[1];
+    z = oz = q[2];
+    if constexpr (AUG) augment_point(ag.vox_aug + 8 * f, p1 - p0 == 1, x, y, z);
+    return true;
+}
+
+constexpr int AUG_UNROLL = 4;            // points per thread in flight while the augmented words are formed
+constexpr uint64_t NO_WORD = ~0ull;      // a rejected point's parked word (keys are below 2^31)
+
+template <typename T, bool AUG>
+__global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64_t *pt_off, const T *pts,
                                                          int64_t pt_stride, const int64_t *img2, int64_t img2_ld,
                                                          const double *P, const double *fv_aug, uint64_t *tmp,
                                                          uint64_t *srt, int32_t *acc,
                                                          double *img_index, int64_t ld, int64_t *bv_index,
                                                          double *mval, int64_t *frame_n, int32_t *vox_count,
-                                                         int64_t *frame_nvox) {
+                                                         int64_t *frame_nvox, Mv3dAug<AUG> ag) {
     __shared__ TileSortLds lds;
     const int f = blockIdx.x;
-    const int64_t p0 = pt_off[f], p1 = pt_off[f + 1];
+    // [p0, p1): the frame's slots in the outputs and the workspace -- its points, or (AUG) its out points,
+    // read from the cloud's rows q0 + [0, nq) through the optional gather
+    int64_t p0, p1, q0 = 0, nq = 0;
+    if constexpr (AUG) {
+        aug_frame(ag, pt_off, f, p0, p1, q0, nq);
+    } else {
+        p0 = pt_off[f];
+        p1 = pt_off[f + 1];
+    }
     const int64_t n_keys = (int64_t)g.n_side * g.n_fwd * g.n_h;
     const int n_tiles = (int)(((n_keys - 1) >> g.log_tile) + 1);
     // per point: points accepted by its voxel, 0 = rejected (outside the ranges or over the cap)
     for (int64_t i = p0 + threadIdx.x; i < p1; i += TS_BLOCK) acc[i] = 0;
+    if constexpr (AUG) {
+        // The sort walks the frame's words twice (count, placement). Augmenting a point costs a dependent
+        // gather and a dozen f64 operations, so the words are formed ONCE, AUG_UNROLL points per thread in
+        // flight, and parked in srt -- which the sort writes only after both walks -- with NO_WORD for a
+        // rejected point. (tile_sort's first block_publish orders these stores before the walks' loads.)
+        for (int64_t b = p0 + threadIdx.x; b < p1; b += (int64_t)AUG_UNROLL * TS_BLOCK) {
+            uint64_t w[AUG_UNROLL];
+#pragma unroll
+            for (int u = 0; u < AUG_UNROLL; ++u) {
+                const int64_t i = b + (int64_t)u * TS_BLOCK;
+                w[u] = NO_WORD;
+                T x, y, z, ox, oy, oz;
+                int64_t src;
+                if (i < p1 && frame_point<T, AUG>(ag, pts, pt_stride, f, i, p0, p1, q0, nq, x, y, z, ox, oy, oz, src)) {
+                    int si, fi;
+                    const int64_t key = voxel_key<T>(g, x, y, z, si, fi);
+                    if (key >= 0) w[u] = ((uint64_t)key << 32) | (uint32_t)(i - p0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < AUG_UNROLL; ++u) {
+                const int64_t i = b + (int64_t)u * TS_BLOCK;
+                if (i < p1) srt[i] = w[u];
+            }
+        }
+    }
     const int32_t n = tile_sort(
         lds, n_tiles, tmp + p0, srt + p0,
         [&](auto &&emit) {
             for (int64_t i = p0 + threadIdx.x; i < p1; i += TS_BLOCK) {
-                const double *q = pts + i * pt_stride;
-                int si, fi;
-                const int64_t key = voxel_key(g, q[0], q[1], q[2], si, fi);
-                if (key >= 0) emit(((uint64_t)key << 32) | (uint32_t)(i - p0));
+                if constexpr (AUG) {
+                    const uint64_t w = srt[i];
+                    if (w != NO_WORD) emit(w);
+                } else {
+                    T x, y, z, ox, oy, oz;
+                    int64_t src;
+                    frame_point<T, AUG>(ag, pts, pt_stride, f, i, p0, p1, q0, nq, x, y, z, ox, oy, oz, src);
+                    int si, fi;
+                    const int64_t key = voxel_key<T>(g, x, y, z, si, fi);
+                    if (key >= 0) emit(((uint64_t)key << 32) | (uint32_t)(i - p0));
+                }
             }
         },
         [&](uint64_t w) { return (int)((w >> 32) >> g.log_tile); });
@@ -130,17 +267,19 @@ __global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64
             before += w < (int)(threadIdx.x >> 6) ? lds.wsum[w] : 0;
             tot += lds.wsum[w];
         }
-        if (keep) {
+        T x, y, z, ox, oy, oz;
+        int64_t src;
+        // (an accepted point was read in the key pass; AUG bounds its remain entry again before this read)
+        if (keep && frame_point<T, AUG>(ag, pts, pt_stride, f, i, p0, p1, q0, nq, x, y, z, ox, oy, oz, src)) {
             const int64_t pos = p0 + kept + before + lane_rank(m);
-            const double *q = pts + i * pt_stride;
             int si = 0, fi = 0;
-            voxel_key(g, q[0], q[1], q[2], si, fi);
+            voxel_key<T>(g, x, y, z, si, fi);
             int64_t u, v;
             if (g.has_proj) {
-                project_round(P + 12 * f, q[0], q[1], q[2], u, v, p1 - p0 == 1);
+                project_round(P + 12 * f, (double)ox, (double)oy, (double)oz, u, v, p1 - p0 == 1);
             } else {
-                u = img2[i];
-                v = img2[img2_ld + i];
+                u = img2[src];
+                v = img2[img2_ld + src];
             }
             if (fv_aug) {
                 // augment_fv (minibatch_mv3d_img.py:205-206): (img_index * ratio + shift).astype(int)
@@ -159,6 +298,99 @@ __global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64
         __syncthreads();
     }
     if (threadIdx.x == 0) frame_n[f] = kept;
+}
+
+// augment_voxel materialised (minibatch_mv3d_img.py:170-187): out point i of frame blockIdx.y gets the
+// augmented row [x, y, z, r] (T's values widened to f64, exact) and the rounded projection of the ORIGINAL
+// point. A bad remain entry leaves a NaN row (the producer's range tests reject it) and pixel (0, 0).
+constexpr int AUG_BLOCK = 256;
+
+template <typename T>
+__global__ __launch_bounds__(AUG_BLOCK) void k_mv3d_augment(const int64_t *pt_off, const T *pts, int64_t pt_stride,
+                                                            const double *P, Mv3dAug<true> ag, double *cloud,
+                                                            int64_t *img2, int64_t ld) {
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    const int f = blockIdx.y;
+    int64_t p0, p1, q0, nq;
+    aug_frame(ag, pt_off, f, p0, p1, q0, nq);
+    for (int64_t i = p0 + (int64_t)blockIdx.x * AUG_BLOCK + threadIdx.x; i < p1; i += (int64_t)gridDim.x * AUG_BLOCK) {
+        const int64_t src = aug_source(ag, i, p0, q0, nq);
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        f64x2 xy = {nan, nan}, zr = {nan, nan};
+        int64_t u = 0, v = 0;
+        if (src >= 0) {
+            const T *q = pts + src * pt_stride;
+            T x = q[0], y = q[1], z = q[2];
+            const T r = q[3];
+            project_round(P + 12 * f, (double)x, (double)y, (double)z, u, v, p1 - p0 == 1);
+            augment_point(ag.vox_aug + 8 * f, p1 - p0 == 1, x, y, z);
+            xy = f64x2{(double)x, (double)y};
+            zr = f64x2{(double)z, (double)r};
+        }
+        f64x2 *row = reinterpret_cast<f64x2 *>(cloud + 4 * i);
+        row[0] = xy;
+        row[1] = zr;
+        img2[i] = u;
+        img2[ld + i] = v;
+    }
+}
+
+// Host checks shared by the two augmented entry points: SHPL_OK and *ag filled, or the status the arguments get.
+int make_aug(const int64_t *d_point_offsets, int64_t total_points, const void *d_points, int point_dtype,
+             const double *d_vox_aug, const int64_t *d_remain_index, const int64_t *d_remain_offsets, int64_t total_out,
+             uint32_t *d_err, Mv3dAug<true> *ag) {
+    if (!d_point_offsets || !d_vox_aug || (total_points > 0 && !d_points)) return SHPL_ERR_ARG;
+    if (!d_remain_index != !d_remain_offsets) return SHPL_ERR_ARG;
+    if (point_dtype != SHPL_F32 && point_dtype != SHPL_F64) return SHPL_ERR_BAD_SHAPE;
+    if (total_points < 0 || total_out < 0 || total_points >= ((int64_t)1 << 31) || total_out >= ((int64_t)1 << 31) ||
+        (!d_remain_index && total_out != total_points))
+        return SHPL_ERR_BAD_SHAPE;
+    *ag = Mv3dAug<true>{d_vox_aug, d_remain_index, d_remain_index ? d_remain_offsets : d_point_offsets, total_points,
+                        total_out, d_err};
+    return SHPL_OK;
+}
+
+// voxel_full_size and the sort's tiling from the ranges (construct_voxel.py:77-80)
+int make_geom(const double *ranges, double res, double zres, int voxel_point_count, bool has_proj, Mv3dGeom *out) {
+    Mv3dGeom g{};
+    g.fwd_lo = ranges[0];
+    g.fwd_hi = ranges[1];
+    g.side_lo = ranges[2];
+    g.side_hi = ranges[3];
+    g.h_lo = ranges[4];
+    g.h_hi = ranges[5];
+    g.res = res;
+    g.zres = zres;
+    // construct_voxel.py:77-80: x_max = int((side_hi - side_lo) / res) etc.; sizes are max + 1
+    g.n_side = (int)((g.side_hi - g.side_lo) / res) + 1;
+    g.n_fwd = (int)((g.fwd_hi - g.fwd_lo) / res) + 1;
+    g.n_h = (int)((g.h_hi - g.h_lo) / zres) + 1;
+    g.cap = voxel_point_count;
+    g.has_proj = has_proj ? 1 : 0;
+    const int64_t n_keys = (int64_t)g.n_side * g.n_fwd * g.n_h;
+    if (n_keys >= ((int64_t)1 << 31)) return SHPL_ERR_BAD_SHAPE;
+    g.log_tile = 0;
+    while (((n_keys - 1) >> g.log_tile) + 1 > TS_TILES) ++g.log_tile;
+    *out = g;
+    return SHPL_OK;
+}
+
+// One workgroup per frame; the workspace holds tmp / srt / acc for n_slots point slots (shpl_mv3d_workspace_bytes).
+template <typename T, bool AUG>
+int launch_frames(const Mv3dGeom &g, int n_frames, const int64_t *d_point_offsets, const void *d_points,
+                  int64_t point_stride, const int64_t *d_img_index2, int64_t img2_ld, const double *d_P,
+                  const double *d_fv_aug, int64_t n_slots, double *d_img_index, int64_t ld, int64_t *d_bv_index,
+                  double *d_mval, int64_t *d_frame_n, int32_t *d_number_buffer, int64_t *d_frame_nvox, void *d_ws,
+                  const Mv3dAug<AUG> &ag, hipStream_t stream) {
+    const size_t n = (size_t)(n_slots > 0 ? n_slots : 1);
+    uint64_t *tmp = (uint64_t *)d_ws;
+    uint64_t *srt = (uint64_t *)((char *)d_ws + align_up(n * sizeof(uint64_t), 256));
+    int32_t *acc = (int32_t *)((char *)d_ws + 2 * align_up(n * sizeof(uint64_t), 256));
+    hipLaunchKernelGGL((k_mv3d_frame<T, AUG>), dim3(n_frames), dim3(TS_BLOCK), 0, stream, g, d_point_offsets,
+                       (const T *)d_points, point_stride, d_img_index2, img2_ld, d_P, d_fv_aug, tmp, srt, acc,
+                       d_img_index, ld, d_bv_index, d_mval, d_frame_n, d_number_buffer, d_frame_nvox, ag);
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
 }
 
 }  // namespace
@@ -189,33 +421,70 @@ extern "C" int shpl_mv3d_voxels(int n_frames, const int64_t *d_point_offsets, in
     size_t need;
     shpl_mv3d_workspace_bytes(total_points, &need);
     if (need > ws_bytes) return SHPL_ERR_WORKSPACE;
-    Mv3dGeom g{};
-    g.fwd_lo = ranges[0];
-    g.fwd_hi = ranges[1];
-    g.side_lo = ranges[2];
-    g.side_hi = ranges[3];
-    g.h_lo = ranges[4];
-    g.h_hi = ranges[5];
-    g.res = res;
-    g.zres = zres;
-    // construct_voxel.py:77-80: x_max = int((side_hi - side_lo) / res) etc.; sizes are max + 1
-    g.n_side = (int)((g.side_hi - g.side_lo) / res) + 1;
-    g.n_fwd = (int)((g.fwd_hi - g.fwd_lo) / res) + 1;
-    g.n_h = (int)((g.h_hi - g.h_lo) / zres) + 1;
-    g.cap = voxel_point_count;
-    g.has_proj = d_img_index2 ? 0 : 1;
-    const int64_t n_keys = (int64_t)g.n_side * g.n_fwd * g.n_h;
-    if (n_keys >= ((int64_t)1 << 31)) return SHPL_ERR_BAD_SHAPE;
-    g.log_tile = 0;
-    while (((n_keys - 1) >> g.log_tile) + 1 > TS_TILES) ++g.log_tile;
-    const size_t n = (size_t)(total_points > 0 ? total_points : 1);
-    uint64_t *tmp = (uint64_t *)d_ws;
-    uint64_t *srt = (uint64_t *)((char *)d_ws + align_up(n * sizeof(uint64_t), 256));
-    int32_t *acc = (int32_t *)((char *)d_ws + 2 * align_up(n * sizeof(uint64_t), 256));
-    hipLaunchKernelGGL(k_mv3d_frame, dim3(n_frames), dim3(TS_BLOCK), 0, (hipStream_t)stream, g, d_point_offsets,
-                       d_points, point_stride, d_img_index2, total_points, d_P, d_fv_aug, tmp, srt, acc, d_img_index, ld,
-                       d_bv_index, d_mval,
-                       d_frame_n, d_number_buffer, d_frame_nvox);
+    Mv3dGeom g;
+    const int st = make_geom(ranges, res, zres, voxel_point_count, !d_img_index2, &g);
+    if (st != SHPL_OK) return st;
+    return launch_frames<double, false>(g, n_frames, d_point_offsets, d_points, point_stride, d_img_index2, total_points,
+                                        d_P, d_fv_aug, total_points, d_img_index, ld, d_bv_index, d_mval, d_frame_n,
+                                        d_number_buffer, d_frame_nvox, d_ws, Mv3dAug<false>{}, (hipStream_t)stream);
+}
+
+extern "C" int shpl_mv3d_augment_points(int n_frames, const int64_t *d_point_offsets, int64_t total_points,
+                                        const void *d_points, int point_dtype, int64_t point_stride, const double *d_P,
+                                        const double *d_vox_aug, const int64_t *d_remain_index,
+                                        const int64_t *d_remain_offsets, int64_t total_out, double *d_cloud,
+                                        int64_t *d_img_index2, int64_t ld, uint32_t *d_err, void *stream) {
+    if (n_frames < 1 || !d_P) return SHPL_ERR_ARG;
+    Mv3dAug<true> ag;
+    const int st = make_aug(d_point_offsets, total_points, d_points, point_dtype, d_vox_aug, d_remain_index,
+                            d_remain_offsets, total_out, d_err, &ag);
+    if (st != SHPL_OK) return st;
+    if (total_out > 0 && (!d_cloud || !d_img_index2)) return SHPL_ERR_ARG;
+    if (point_stride < 4 || ld < total_out || !aligned16(d_cloud)) return SHPL_ERR_BAD_SHAPE;
+    if (total_out == 0) return SHPL_OK;
+    // ~16 points per thread at most 64 workgroups a frame: a streaming pass, small beside the producer
+    int64_t per = (total_out / n_frames + 16 * AUG_BLOCK - 1) / (16 * AUG_BLOCK);
+    per = per < 1 ? 1 : (per > 64 ? 64 : per);
+    const dim3 grid((unsigned)per, (unsigned)n_frames);
+    if (point_dtype == SHPL_F32)
+        hipLaunchKernelGGL((k_mv3d_augment<float>), grid, dim3(AUG_BLOCK), 0, (hipStream_t)stream, d_point_offsets,
+                           (const float *)d_points, point_stride, d_P, ag, d_cloud, d_img_index2, ld);
+    else
+        hipLaunchKernelGGL((k_mv3d_augment<double>), grid, dim3(AUG_BLOCK), 0, (hipStream_t)stream, d_point_offsets,
+                           (const double *)d_points, point_stride, d_P, ag, d_cloud, d_img_index2, ld);
     SHPL_LAUNCH_CHECK();
     return SHPL_OK;
+}
+
+extern "C" int shpl_mv3d_voxels_aug(int n_frames, const int64_t *d_point_offsets, int64_t total_points,
+                                    const void *d_points, int point_dtype, int64_t point_stride,
+                                    const int64_t *d_img_index2, const double *d_P, const double *d_fv_aug,
+                                    const double *d_vox_aug, const int64_t *d_remain_index,
+                                    const int64_t *d_remain_offsets, int64_t total_out, const double *ranges, double res,
+                                    double zres, int voxel_point_count, double *d_img_index, int64_t ld,
+                                    int64_t *d_bv_index, double *d_mval, int64_t *d_frame_n, int32_t *d_number_buffer,
+                                    int64_t *d_frame_nvox, uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream) {
+    if (n_frames < 1 || !ranges || !d_frame_n || !d_ws) return SHPL_ERR_ARG;
+    Mv3dAug<true> ag;
+    int st = make_aug(d_point_offsets, total_points, d_points, point_dtype, d_vox_aug, d_remain_index, d_remain_offsets,
+                      total_out, d_err, &ag);
+    if (st != SHPL_OK) return st;
+    if (total_out > 0 && (!d_img_index || !d_bv_index || !d_mval)) return SHPL_ERR_ARG;
+    if (!d_img_index2 && !d_P) return SHPL_ERR_ARG;
+    if (d_number_buffer && !d_frame_nvox) return SHPL_ERR_ARG;
+    if (point_stride < 3 || ld < total_out || !(res > 0) || !(zres > 0) || voxel_point_count < 1)
+        return SHPL_ERR_BAD_SHAPE;
+    size_t need;
+    shpl_mv3d_workspace_bytes(total_out, &need);
+    if (need > ws_bytes) return SHPL_ERR_WORKSPACE;
+    Mv3dGeom g;
+    st = make_geom(ranges, res, zres, voxel_point_count, !d_img_index2, &g);
+    if (st != SHPL_OK) return st;
+    if (point_dtype == SHPL_F32)
+        return launch_frames<float, true>(g, n_frames, d_point_offsets, d_points, point_stride, d_img_index2, total_points,
+                                          d_P, d_fv_aug, total_out, d_img_index, ld, d_bv_index, d_mval, d_frame_n,
+                                          d_number_buffer, d_frame_nvox, d_ws, ag, (hipStream_t)stream);
+    return launch_frames<double, true>(g, n_frames, d_point_offsets, d_points, point_stride, d_img_index2, total_points,
+                                       d_P, d_fv_aug, total_out, d_img_index, ld, d_bv_index, d_mval, d_frame_n,
+                                       d_number_buffer, d_frame_nvox, d_ws, ag, (hipStream_t)stream);
 }
