@@ -440,7 +440,9 @@ ROWS_SHAPES = [  # bf16, <= 64 input channels, whole 32-channel output blocks: t
     (3, 17, 70, 24, 64),   # a partial strip, two output blocks, a channel tail inside chunk 2
     (1, 1, 5, 8, 32),      # one row, one partial strip
     (2, 130, 40, 48, 32),  # three bands (band edges inside the map)
-    (1, 61, 33, 16, 32),   # one band of 61 rows (every ring slot phase at the band end)
+    (1, 61, 33, 16, 32),   # two bands of 31 and 30 rows (bands are cut at ceil(h / 60)): 33 and 32 staged rows
+    (1, 60, 33, 16, 32),   # the longest single band: 62 staged rows, 62 % RING = 2 (every band length mod RING at a
+                           # full band: tests/test_gpu_conv_rows.py, geom-58x.. to geom-60x..)
 ]
 
 
