@@ -40,18 +40,10 @@
 #include "shpl_conv_bn.h"
 #include "shpl_conv_rows.h"
 #include "shpl_conv_wide.h"
-#include "shpl_conv_stage.h"
+#include "shpl_conv_tile.h"
 
 namespace shpl {
 namespace {
-
-// Where channel c of output pixel `row` is stored: in out, or -- the input gradient's second map -- in out2 as
-// channel c - c_split.
-template <typename T>
-__device__ __forceinline__ T *out_ptr(const ConvArgs &p, int64_t row, int c) {
-    return p.out2 && c >= p.c_split ? reinterpret_cast<T *>(p.out2) + row * p.out2_stride + (c - p.c_split)
-                                    : reinterpret_cast<T *>(p.out) + row * p.out_stride + c;
-}
 
 // NCB: output-channel blocks per workgroup (blockIdx.y covers NCB of them):
 // 2 for the input gradient's 64 output channels, so each staged input chunk
@@ -65,8 +57,7 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
     static_assert(NP == 2, "two 16-byte pieces per LDS row (the swizzle)");
     constexpr int IN_BYTES = HH * HWD * NP * 16, W_BYTES = W_ROWS * NP * 16 * NCB;
     // the output rows' transpose (epilogue) reuses the chunk buffers: 4 waves x 32 pixels x OPITCH
-    constexpr int OPITCH = NCO * (int)sizeof(T) + 16;
-    static_assert(4 * 32 * OPITCH <= IN_BYTES + W_BYTES, "epilogue rows fit the chunk buffers");
+    static_assert(4 * 32 * OPITCH<T> <= IN_BYTES + W_BYTES, "epilogue rows fit the chunk buffers");
     __shared__ __attribute__((aligned(16))) uint8_t s_buf[IN_BYTES + W_BYTES];
     uint8_t *const s_in = s_buf, *const s_w = s_buf + IN_BYTES;
     __shared__ float s_red[4][2][NCO];
@@ -78,25 +69,13 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
     // each XCD gets one contiguous run of tiles: neighbouring tiles share halo rows through that XCD's L2
     const int tile = (int)xcd_block((int)blockIdx.x, p.n_tiles);
     const int cob0 = blockIdx.y * NCB;
-    const int f = tile / p.tiles_per_frame;
-    const int t_in = tile - f * p.tiles_per_frame;
-    const int ty = t_in / p.tiles_x, tx = t_in - ty * p.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
+    int f, y0, x0;
+    tile_origin<TH>(p, tile, f, y0, x0);
     const int H = p.h, W = p.w;
     const int64_t frame_row0 = (int64_t)f * H * W;
     const int Q = p.qa + p.qb;
 
-    // epilogue coefficients, as k_conv_rows: scale (1 when absent) and shift - center * scale, applied
-    // as one fma -- the two kernels give the same bits for the same call
-    if (tid < NCO * NCB) {
-        const int cb = tid / NCO, c = (cob0 + cb) * NCO + (tid & 31);
-        const bool in = c < p.c_out;
-        const float sc = p.scale && in ? p.scale[c] : 1.0f;
-        const float ce = p.center && in ? p.center[c] : 0.0f;
-        const float sh = p.shift && in ? p.shift[c] : 0.0f;
-        s_par[cb][0][tid & 31] = sc;
-        s_par[cb][1][tid & 31] = __fsub_rn(sh, __fmul_rn(ce, sc));
-    }
+    epilogue_coeffs<NCB>(p, cob0, s_par, tid);
     const int n_run = POOLED ? find_runs(p, f, y0, x0, runs) : 0;  // (s_par: published by the next barrier)
 
     f32x16 acc[NCB][RPW];
@@ -174,101 +153,24 @@ __global__ __launch_bounds__(CONV_BLOCK, NCB == 2 ? 3 : 4) void k_conv3x3(const 
         __syncthreads();  // the chunk's buffers are restaged next
     }
 
-    // ---- epilogue. The MFMAs take the weights as A and the pixels as B (D =
-    // W^T X^T), so acc element i of subtile m is channel cob*32 + 8(i>>2) +
-    // 4h + (i&3) of pixel (y0 + RPW w + m, x0 + pl): four runs of 4 channels
-    // per lane. A row of 32 pixels goes through LDS (wave-private, rows of
-    // OPITCH bytes) and out as 16-byte pieces, consecutive lanes on
-    // consecutive pieces: 2 (bf16) / 4 (f32) store instructions per row, each
-    // one contiguous 1 KB, instead of 16 two- or four-byte stores (the texture
-    // addresser was the bf16 conv's busiest unit). Blocks whose channels are not
-    // whole or whose rows are not 16-byte aligned store channel by channel.
-    constexpr int HE = E::HE, PPP = NCO / HE;  // channels per piece, pieces per pixel
-    const int x = x0 + pl;
-    uint8_t *const s_o = s_buf + wave * 32 * OPITCH;
-    float s1[16], s2[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s1[i] = s2[i] = 0.0f;
+    // ---- epilogue (epilogue_row): acc element i of subtile m is channel cob*32 + 8(i>>2) + 4h + (i&3) of pixel
+    // (y0 + RPW w + m, x0 + pl). The rows' transpose reuses the chunk buffers; the order of the two loops is the
+    // statistics' summation order.
+    uint8_t *const s_o = s_buf + wave * 32 * OPITCH<T>;
+    ChanSums sums;
+    sums.zero();
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-        const int cob = cob0 + cb;
-        const bool fast = p.vec_out && cob * NCO + NCO <= p.c_out;
 #pragma unroll
         for (int m = 0; m < RPW; ++m) {
             const int y = y0 + RPW * wave + m;
-            const bool ok = y < H && x < W;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int cl = 8 * g + 4 * hf, c = cob * NCO + cl;  // first channel of the run
-                const f32x4 scl = *reinterpret_cast<const f32x4 *>(&s_par[cb][0][cl]);
-                const f32x4 sft = *reinterpret_cast<const f32x4 *>(&s_par[cb][1][cl]);
-                T o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = acc[cb][m][4 * g + j];
-                    if (STATS && ok) {
-                        s1[4 * g + j] = __fadd_rn(s1[4 * g + j], v);
-                        s2[4 * g + j] = __fadd_rn(s2[4 * g + j], __fmul_rn(v, v));
-                    }
-                    o[j] = relu_bits(E::back(__builtin_fmaf(v, scl[j], sft[j])), p.act == 1);
-                }
-                if (fast) {
-                    __builtin_memcpy(s_o + pl * OPITCH + cl * sizeof(T), o, sizeof(o));
-                } else if (ok) {
-                    const int64_t row = frame_row0 + (int64_t)y * W + x;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (c + j >= p.c_out) break;
-                        *out_ptr<T>(p, row, c + j) = o[j];
-                    }
-                }
-            }
-            if (fast) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's row is in LDS (one wave: in order)
-#pragma unroll
-                for (int k = 0; k < 32 * PPP / 64; ++k) {
-                    const int pc = lane + 64 * k, px = pc / PPP, pi = pc % PPP;
-                    const u32x4 v = *reinterpret_cast<const u32x4 *>(s_o + px * OPITCH + pi * 16);
-                    if (y < H && x0 + px < W) {
-                        const int64_t row = frame_row0 + (int64_t)y * W + x0 + px;
-                        *reinterpret_cast<u32x4 *>(out_ptr<T>(p, row, cob * NCO + pi * HE)) = v;
-                    }
-                }
-            }
+            const int64_t row = frame_row0 + (int64_t)y * W + x0;  // + column of the tile
+            epilogue_row<T, true, STATS>(
+                p, acc[cb][m], s_par[cb], s_o, (cob0 + cb) * NCO, y < H, x0, W, &sums,
+                [row](const ConvArgs &a, int col, int c) { return out_ptr<T>(a, row + col, c); });
         }
     }
-    if (STATS) {
-        // per channel: sum over the 32 pixels of the lane half by a halving
-        // butterfly (each exchange hands the partner the half of the values it
-        // keeps: 8 + 4 + 2 + 1 + 1 shuffles per statistic instead of 16 x 5),
-        // after which lanes 2j and 2j+1 both hold value j; then over the 4
-        // waves in double
-#pragma unroll
-        for (int n = 8, off = 16; n >= 1; n >>= 1, off >>= 1) {
-            const bool up = (pl & off) != 0;
-#pragma unroll
-            for (int i = 0; i < n; ++i) {
-                const float g1 = up ? s1[i] : s1[i + n], k1 = up ? s1[i + n] : s1[i];
-                const float g2 = up ? s2[i] : s2[i + n], k2 = up ? s2[i + n] : s2[i];
-                s1[i] = __fadd_rn(k1, __shfl_xor(g1, off, 64));
-                s2[i] = __fadd_rn(k2, __shfl_xor(g2, off, 64));
-            }
-        }
-        s1[0] = __fadd_rn(s1[0], __shfl_xor(s1[0], 1, 64));
-        s2[0] = __fadd_rn(s2[0], __shfl_xor(s2[0], 1, 64));
-        if ((pl & 1) == 0) {
-            const int i = pl >> 1, cl = 8 * (i >> 2) + 4 * hf + (i & 3);
-            s_red[wave][0][cl] = s1[0];
-            s_red[wave][1][cl] = s2[0];
-        }
-        __syncthreads();
-        if (tid < 2 * NCO) {
-            const int st = tid >> 5, c = tid & 31;
-            double sum = 0.0;
-            for (int w = 0; w < 4; ++w) sum += (double)s_red[w][st][c];
-            p.part[((int64_t)(cob0 * NCO + c) * 2 + st) * p.n_tiles + tile] = sum;
-        }
-    }
+    if (STATS) stats_reduce_tile(p, sums, s_red, tid, cob0 * NCO, tile);
 }
 
 // Weight gradient: dW[tap][ci][co] = sum over pixels p of x[p + tap offset][ci] * g[p][co].
@@ -398,10 +300,8 @@ __global__ __launch_bounds__(CONV_BLOCK, POOLED ? 1 : 2) void k_conv3x3_wgrad(co
 #pragma unroll
     for (int h = 0; h < 2; ++h) a_off[h] = ((h * 16 + l16) / CK) * NPIX * CB + ((h * 16 + l16) % CK) * (int)sizeof(T);
     for (int tile = t0; tile < t1; ++tile) {
-        const int f = tile / p.tiles_per_frame;
-        const int t_in = tile - f * p.tiles_per_frame;
-        const int ty = t_in / p.tiles_x, tx = t_in - ty * p.tiles_x;
-        const int y0 = ty * TH, x0 = tx * TW;
+        int f, y0, x0;
+        tile_origin<TH>(p, tile, f, y0, x0);
         if constexpr (POOLED) {
             const int n_run = find_runs(p, f, y0, x0, runs);
 #pragma unroll
@@ -521,10 +421,8 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_wgrad_bf16(const ConvArgs p, 
     u32x4 xv[IN_IT], gv[G_IT];
     // the tile's pieces into registers, issued together
     auto load = [&](int tile) {
-        const int f = tile / p.tiles_per_frame;
-        const int t_in = tile - f * p.tiles_per_frame;
-        const int ty = t_in / p.tiles_x, tx = t_in - ty * p.tiles_x;
-        const int y0 = ty * TH, x0 = tx * TW;
+        int f, y0, x0;
+        tile_origin<TH>(p, tile, f, y0, x0);
         const int64_t frame_row0 = (int64_t)f * H * W;
 #pragma unroll
         for (int u = 0; u < IN_IT; ++u) {
@@ -692,9 +590,7 @@ RowGeom row_geom(int64_t h, int64_t w) {
     return g;
 }
 
-struct ConvPlan {
-    int ck, qa, qb, n_cob, tiles_x, tiles_y, tiles_per_frame;
-    int64_t n_tiles;
+struct ConvPlan : TilePlan {
     // the workspace, as byte offsets in this order: packed weights; k_row_ptr's row pointers (pooled); statistics
     // partials; the pooled operand (pooled, rows or wide_cmp); k_conv_rows' junk rows; the pooled map
     // materialised by shpl_pull (pooled, wide and not wide_cmp); its size
@@ -752,36 +648,6 @@ int conv_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_
     pl->map = l.take(pl->wide && pooled && !pl->wide_cmp ? (size_t)n_frames * h * w * c_b * 2 : 0);
     pl->total = l.end;
     return SHPL_OK;
-}
-
-// The fields of ConvArgs every form fills: frame and tile geometry, the sources, the pool's arrays; the rest 0.
-ConvArgs conv_args(int dtype, int n_frames, int64_t h, int64_t w, const ConvPlan &pl, const Src &A, const Src &B,
-                   const shpl_csr *pool) {
-    const int he = piece_elems(dtype);
-    ConvArgs a = {};
-    a.n_frames = n_frames;
-    a.h = (int)h;
-    a.w = (int)w;
-    a.tiles_x = pl.tiles_x;
-    a.tiles_per_frame = pl.tiles_per_frame;
-    a.n_tiles = (int)pl.n_tiles;
-    a.a = A.p;
-    a.a_stride = A.stride;
-    a.a_off = A.off;
-    a.c_a = (int)A.c;
-    a.qa = pl.qa;
-    a.b = B.p;
-    a.b_stride = B.stride;
-    a.b_off = B.off;
-    a.c_b = (int)B.c;
-    a.qb = pl.qb;
-    a.vec_a = vec16(A, he);
-    a.vec_b = vec16(B, he);
-    a.ent_dst = pool ? pool->ent_dst : nullptr;
-    a.ent_src = pool ? pool->ent_src : nullptr;
-    a.ent_val = pool ? pool->ent_val : nullptr;
-    a.ent_col = pool ? pool->ent_col : nullptr;
-    return a;
 }
 
 // ---------------------------------------------------------------- host: forward and input gradient
@@ -901,11 +767,7 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, void *ws, bool pooled, bool sta
             a.n_frames > 0 && (!pooled || pool))
             return conv_wide_launch(pl, a, ws, pooled ? pool : nullptr, frame_off, w, s);
     }
-    T *wp = reinterpret_cast<T *>(const_cast<void *>(a.wp));
-    const int64_t wtot = (int64_t)pl.n_cob * (pl.qa + pl.qb) * W_ROWS * Elem<T>::CK;
-    hipLaunchKernelGGL(k_pack_w<T>, dim3(grid_for(wtot, SHPL_BLOCK, 4096)), dim3(SHPL_BLOCK), 0, s,
-                       reinterpret_cast<const T *>(w), a.c_a, pl.qa, a.c_b, pl.qb, a.c_out, pl.n_cob, transpose, wp);
-    SHPL_LAUNCH_CHECK();
+    if (const int rc = pack_weights<T>(a, w, pl.n_cob, transpose, s)) return rc;
     if constexpr (sizeof(T) == 2) {
         // bf16 with at most 64 input channels: the row-streaming kernel (k_conv_rows), also for the input
         // gradient's two maps (split at a whole output block) and the training forward's statistics
@@ -913,9 +775,7 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, void *ws, bool pooled, bool sta
             return conv_rows_launch(pl, a, ws, pooled, stats, frame_off, d_stats, s);
     }
     if (pooled) {
-        hipLaunchKernelGGL(k_row_ptr, dim3(16, a.n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, frame_off, a.h, a.w,
-                           const_cast<int32_t *>(a.row_ptr));
-        SHPL_LAUNCH_CHECK();
+        if (const int rc = row_pointers(a, frame_off, s)) return rc;
     }
     const dim3 grid((unsigned)pl.n_tiles, (unsigned)pl.n_cob);
     // f32, an even number of dense output blocks (the input gradient's 64
@@ -923,16 +783,12 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, void *ws, bool pooled, bool sta
     // nothing (2.73 / 2.77 ms: 3 waves per SIMD instead of 6 for a
     // memory-pipeline-bound kernel) and keeps one.
     const bool pair = sizeof(T) == 4 && !pooled && !stats && pl.n_cob % 2 == 0;
-    const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
     using Kernel = void (*)(const ConvArgs);
-    const Kernel kernel = by_bools(
-        [](auto po, auto st, auto gr, auto pr) -> Kernel {
-            if constexpr ((gr() && !po()) || (pr() && (po() || st() || sizeof(T) != 4)))
-                return nullptr;  // no such form: the switches above never say so
-            else
-                return k_conv3x3<T, po(), st(), pr() ? 2 : 1, gr()>;
-        },
-        pooled, stats, group, pair);
+    const Kernel kernel = pooled_form<Kernel>(pooled, a.ent_col, [&](auto po, auto gr) -> Kernel {
+        if constexpr (sizeof(T) == 4 && !po())  // the only pair form: `pair` says so for no other
+            if (pair) return k_conv3x3<T, false, false, 2>;
+        return stats ? k_conv3x3<T, po(), true, 1, gr()> : k_conv3x3<T, po(), false, 1, gr()>;
+    });
     hipLaunchKernelGGL(kernel, pair ? dim3(grid.x, grid.y / 2) : grid, dim3(CONV_BLOCK), 0, s, a);
     SHPL_LAUNCH_CHECK();
     if (stats) {
@@ -1008,7 +864,6 @@ int dgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, 
         return SHPL_ERR_BAD_SHAPE;
     if (pl.n_tiles == 0) return SHPL_OK;
     if (!d_gy || (c_split > 0 && !d_dx)) return SHPL_ERR_ARG;
-    const int he = piece_elems(dtype);
     ConvArgs a = conv_args(dtype, n_frames, h, w, pl, {d_gy, gy_stride, 0, c_gy}, {}, nullptr);
     a.wp = region<void>(d_ws, pl.wp);
     a.out = d_dx;
@@ -1017,8 +872,7 @@ int dgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const void *d_gy, 
     a.out2 = d_dx_b;
     a.out2_stride = dx_b_stride;
     a.c_split = (int)c_split;
-    a.vec_out = (!d_dx || (aligned16(d_dx) && dx_stride % he == 0)) &&
-                (!d_dx_b || (aligned16(d_dx_b) && dx_b_stride % he == 0 && c_split % he == 0));
+    a.vec_out = vec_out_split(d_dx, dx_stride, d_dx_b, dx_b_stride, c_split, piece_elems(dtype));
     a.occ2 = d_dx_b ? occ2 : nullptr;
     hipStream_t s = (hipStream_t)stream;
     return by_dtype(dtype, [&](auto t) {
@@ -1157,25 +1011,19 @@ int wgrad_impl(int dtype, int n_frames, int64_t h, int64_t w, const Src &A, cons
               g.vec_g && c_out % NCO == 0;
     g.part = region<float>(d_ws, wp.part);
     if (pooled) {
-        hipLaunchKernelGGL(k_row_ptr, dim3(16, n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, d_frame_off, a.h, a.w,
-                           const_cast<int32_t *>(a.row_ptr));
-        SHPL_LAUNCH_CHECK();
+        rc = row_pointers(a, d_frame_off, s);
+        if (rc) return rc;
     }
     const dim3 grid((unsigned)wp.n_groups, (unsigned)wp.n_cib, (unsigned)pl.n_cob);
-    const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
     using Kernel = void (*)(const ConvArgs, const WgArgs);
     const Kernel kernel = by_dtype(dtype, [&](auto t) {
         typedef typename decltype(t)::T T;
-        return by_bools(
-            [](auto po, auto gr) -> Kernel {
-                if constexpr (gr() && !po())
-                    return nullptr;  // no such form
-                else if constexpr (sizeof(T) == 2 && !po())
-                    return k_wgrad_bf16;  // dense bf16 sources: the bf16 MFMA kernel
-                else
-                    return k_conv3x3_wgrad<T, po(), gr()>;
-            },
-            pooled, group);
+        return pooled_form<Kernel>(pooled, a.ent_col, [](auto po, auto gr) -> Kernel {
+            if constexpr (sizeof(T) == 2 && !po())
+                return k_wgrad_bf16;  // dense bf16 sources: the bf16 MFMA kernel
+            else
+                return k_conv3x3_wgrad<T, po(), gr()>;
+        });
     });
     hipLaunchKernelGGL(kernel, grid, dim3(CONV_BLOCK), 0, s, a, g);
     SHPL_LAUNCH_CHECK();

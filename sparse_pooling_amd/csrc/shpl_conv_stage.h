@@ -1,9 +1,11 @@
-// shpl_conv_stage.h -- what the tiled kernels over [a || pooled b] share (shpl_conv.hip: the 3x3 conv, its
-// gradients; shpl_upconv.hip: the stride-2 transposed conv): the kernel arguments, the staging of one input chunk
-// of a tile's halo into LDS -- dense chunks by LDS-DMA, pooled chunks summed from the CSR's runs in the pull's
-// order -- the weight packing, the row pointers over a destination-sorted CSR, the statistics reduction, and the
-// host's small helpers. The halo tile starts one row above and one column left of the output tile; its size
-// (HH_ x HWD_) is a template parameter that defaults to the 3x3 conv's (TH + 2) x (TW + 2).
+// shpl_conv_stage.h -- what the tiled kernels over [a || pooled b] READ, and the host's helpers (shpl_conv.hip: the
+// 3x3 conv, its gradients; shpl_upconv.hip, shpl_upconv_grad.hip: the stride-2 transposed conv and its): the kernel
+// arguments, the staging of one chunk's weight rows and of one input chunk of a tile's halo into LDS -- dense chunks
+// by LDS-DMA, pooled chunks summed from the CSR's runs in the pull's order -- the weight packing, the row pointers
+// over a destination-sorted CSR, the statistics reduction, and on the host the kernel arguments every form fills,
+// the small launches and the form selection. What a tile computes and writes is in shpl_conv_tile.h. The halo tile
+// starts one row above and one column left of the output tile; its size (HH_ x HWD_) is a template parameter that
+// defaults to the 3x3 conv's (TH + 2) x (TW + 2).
 #pragma once
 
 #include "shpl_conv_bn.h"
@@ -345,31 +347,41 @@ __device__ __forceinline__ HaloRuns halo_runs_lds() {
     return {s_lo, s_pre, s_run_pix, s_run_e, s_run_end, s_run_src, s_run_val, s_occ, s_scan};
 }
 
-// Stages input chunk q of output tile (f, y0, x0) -- its 9x32 weight rows
-// and its HH_ x HWD_ halo -- into one LDS buffer pair (swizzled 32-byte rows).
-// Weights and dense halo chunks are LDS-DMAs (lane k of the wave fills slot
-// k: it loads the piece the swizzle puts there); pooled chunks are computed
-// (stage_halo). The caller waits and synchronises. tid: the thread's index (a caller may hand it in opaque, so
-// that the conditions on it are evaluated per chunk instead of kept as lane masks across its chunk loop).
-template <typename T, bool POOLED, int NCB = 1, bool GROUP = false, int HH_ = HH, int HWD_ = HWD>
-__device__ __forceinline__ void conv_stage(const ConvArgs &p, int q, int f, int y0, int x0, const T *wq,
-                                           int64_t wq_cb, uint8_t *s_in, uint8_t *s_w, const HaloRuns &runs,
-                                           int n_run, int tid = threadIdx.x) {
-    typedef Elem<T> E;
-    constexpr int CK = E::CK, HE = E::HE, NP = E::NP;
-    constexpr int IN_PIECES = HH_ * HWD_ * NP, W_PIECES = W_ROWS * NP;
+// Chunk q's 9x32 weight rows of NCB output blocks (wq: the first block's packed weights, wq_cb elements to the next
+// block's) into s_w, the blocks W_ROWS rows apart: LDS-DMAs into swizzled 32-byte rows (lane k of the wave fills
+// slot k: it loads the piece the swizzle puts there). The caller waits and synchronises.
+template <typename T, int NCB>
+__device__ __forceinline__ void stage_weights(const T *wq, int64_t wq_cb, int q, uint8_t *s_w, int tid) {
+    constexpr int CK = Elem<T>::CK, HE = Elem<T>::HE, W_PIECES = W_ROWS * Elem<T>::NP;
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {  // the weight rows of each output block, W_PIECES slots apart
+    for (int cb = 0; cb < NCB; ++cb) {
 #pragma unroll
         for (int u = 0; u < (W_PIECES + CONV_BLOCK - 1) / CONV_BLOCK; ++u) {
             const int base = u * CONV_BLOCK + wave * 64;  // the wave's first slot
             if (base >= W_PIECES) break;
             const int k = base + lane, row = k >> 1, g = (k & 1) ^ ((row >> 3) & 1);
             if (k < W_PIECES)
-                dma16(wq + cb * wq_cb + ((int64_t)q * W_ROWS + row) * CK + g * HE, s_w + (cb * W_PIECES + base) * 16);
+                dma16(wq + cb * wq_cb + ((int64_t)q * W_ROWS + row) * CK + g * HE,
+                      s_w + (cb * W_PIECES + base) * 16);
         }
     }
+}
+
+// Stages input chunk q of output tile (f, y0, x0) -- its 9x32 weight rows
+// (stage_weights) and its HH_ x HWD_ halo -- into one LDS buffer pair (swizzled
+// 32-byte rows). Dense halo chunks are LDS-DMAs as the weights are; pooled
+// chunks are computed (stage_halo). The caller waits and synchronises. tid: the thread's index (a caller may hand it in opaque, so
+// that the conditions on it are evaluated per chunk instead of kept as lane masks across its chunk loop).
+template <typename T, bool POOLED, int NCB = 1, bool GROUP = false, int HH_ = HH, int HWD_ = HWD>
+__device__ __forceinline__ void conv_stage(const ConvArgs &p, int q, int f, int y0, int x0, const T *wq,
+                                           int64_t wq_cb, uint8_t *s_in, uint8_t *s_w, const HaloRuns &runs,
+                                           int n_run, int tid = threadIdx.x) {
+    typedef Elem<T> E;
+    constexpr int HE = E::HE, NP = E::NP;
+    constexpr int IN_PIECES = HH_ * HWD_ * NP;
+    const int lane = tid & 63, wave = tid >> 6;
+    stage_weights<T, NCB>(wq, wq_cb, q, s_w, tid);
     if (!POOLED || q < p.qa) {
         const int H = p.h, W = p.w;
         const int64_t frame_row0 = (int64_t)f * H * W;
@@ -528,6 +540,84 @@ int check_sources(int n_frames, int64_t h, int64_t w, const Src &A, const Src &B
         return SHPL_ERR_ARG;
     }
     return SHPL_OK;
+}
+
+// What the plans of the tiled kernels share: elements per chunk, chunks of A and of B, output blocks, the tiling.
+struct TilePlan {
+    int ck, qa, qb, n_cob, tiles_x, tiles_y, tiles_per_frame;
+    int64_t n_tiles;
+};
+
+// The fields of ConvArgs every form fills: frame and tile geometry, the sources, the pool's arrays; the rest 0.
+ConvArgs conv_args(int dtype, int n_frames, int64_t h, int64_t w, const TilePlan &pl, const Src &A, const Src &B,
+                   const shpl_csr *pool) {
+    const int he = piece_elems(dtype);
+    ConvArgs a = {};
+    a.n_frames = n_frames;
+    a.h = (int)h;
+    a.w = (int)w;
+    a.tiles_x = pl.tiles_x;
+    a.tiles_per_frame = pl.tiles_per_frame;
+    a.n_tiles = (int)pl.n_tiles;
+    a.a = A.p;
+    a.a_stride = A.stride;
+    a.a_off = A.off;
+    a.c_a = (int)A.c;
+    a.qa = pl.qa;
+    a.b = B.p;
+    a.b_stride = B.stride;
+    a.b_off = B.off;
+    a.c_b = (int)B.c;
+    a.qb = pl.qb;
+    a.vec_a = vec16(A, he);
+    a.vec_b = vec16(B, he);
+    a.ent_dst = pool ? pool->ent_dst : nullptr;
+    a.ent_src = pool ? pool->ent_src : nullptr;
+    a.ent_val = pool ? pool->ent_val : nullptr;
+    a.ent_col = pool ? pool->ent_col : nullptr;
+    return a;
+}
+
+// ConvArgs::vec_out of an input gradient's one or two maps (d_dx_b: channels >= c_split, or NULL): the rows of
+// each map that is there are 16-byte aligned, and with two the split falls on a whole piece.
+bool vec_out_split(const void *d_dx, int64_t dx_stride, const void *d_dx_b, int64_t dx_b_stride, int64_t c_split,
+                   int he) {
+    return (!d_dx || (aligned16(d_dx) && dx_stride % he == 0)) &&
+           (!d_dx_b || (aligned16(d_dx_b) && dx_b_stride % he == 0 && c_split % he == 0));
+}
+
+// k_pack_w of the weights w over a's chunks and n_cob output blocks, into a.wp.
+template <typename T>
+int pack_weights(const ConvArgs &a, const void *w, int n_cob, int transpose, hipStream_t s) {
+    const int64_t wtot = (int64_t)n_cob * (a.qa + a.qb) * W_ROWS * Elem<T>::CK;
+    hipLaunchKernelGGL(k_pack_w<T>, dim3(grid_for(wtot, SHPL_BLOCK, 4096)), dim3(SHPL_BLOCK), 0, s,
+                       reinterpret_cast<const T *>(w), a.c_a, a.qa, a.c_b, a.qb, a.c_out, n_cob, transpose,
+                       reinterpret_cast<T *>(const_cast<void *>(a.wp)));
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
+
+// k_row_ptr over the pool's destinations (pooled forms), into a.row_ptr.
+int row_pointers(const ConvArgs &a, const int64_t *frame_off, hipStream_t s) {
+    hipLaunchKernelGGL(k_row_ptr, dim3(16, a.n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, frame_off, a.h, a.w,
+                       const_cast<int32_t *>(a.row_ptr));
+    SHPL_LAUNCH_CHECK();
+    return SHPL_OK;
+}
+
+// The (POOLED, GROUP) form of a kernel family: fn(po, gr) returns the instantiation's address. GROUP -- the
+// pixel-keyed CSR's per-column partials -- is pooled && ent_col, so (GROUP && !POOLED) never runs, and fn is not
+// instantiated for it: the family has no such kernel.
+template <typename Kernel, typename F>
+Kernel pooled_form(bool pooled, const int32_t *ent_col, F &&fn) {
+    return by_bools(
+        [&](auto po, auto gr) -> Kernel {
+            if constexpr (gr() && !po())
+                return nullptr;
+            else
+                return fn(po, gr);
+        },
+        pooled, pooled && ent_col);
 }
 
 }  // namespace

@@ -2,14 +2,12 @@
 // (shpl_upconv_grad.hip) share: the argument checks, in shpl_conv3x3's order, and the tiling of the INPUT map.
 #pragma once
 
-#include "shpl_conv_stage.h"
+#include "shpl_conv_tile.h"
 
 namespace shpl {
 namespace {
 
-struct UpPlan {
-    int ck, qa, qb, n_cob, tiles_x, tiles_y, tiles_per_frame;
-    int64_t n_tiles;
+struct UpPlan : TilePlan {
     size_t wp, row_ptr, part, total;  // the workspace: packed weights, row pointers (pooled), statistics partials
 };
 

@@ -37,35 +37,23 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_upconv3x3(const ConvArgs p) {
     static_assert(NP == 2, "two 16-byte pieces per LDS row (the swizzle)");
     constexpr int IN_BYTES = UH * UW * NP * 16, W_BYTES = W_ROWS * NP * 16;
     // the output rows' transpose (epilogue) reuses the chunk buffers: 4 waves x 32 pixels x OPITCH
-    constexpr int OPITCH = NCO * (int)sizeof(T) + 16;
-    static_assert(4 * 32 * OPITCH <= IN_BYTES + W_BYTES, "epilogue rows fit the chunk buffers");
+    static_assert(4 * 32 * OPITCH<T> <= IN_BYTES + W_BYTES, "epilogue rows fit the chunk buffers");
     __shared__ __attribute__((aligned(16))) uint8_t s_buf[IN_BYTES + W_BYTES];
     uint8_t *const s_in = s_buf, *const s_w = s_buf + IN_BYTES;
     __shared__ float s_red[4][2][NCO];
-    __shared__ __attribute__((aligned(16))) float s_par[2][NCO];  // scale, shift - center * scale
+    __shared__ __attribute__((aligned(16))) float s_par[1][2][NCO];  // scale, shift - center * scale
     const HaloRuns runs = halo_runs_lds<POOLED, UH, UW>();
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int pl = lane & 31, hf = lane >> 5;
     const int tile = (int)xcd_block((int)blockIdx.x, p.n_tiles);
     const int cob = blockIdx.y;
-    const int f = tile / p.tiles_per_frame;
-    const int t_in = tile - f * p.tiles_per_frame;
-    const int ty = t_in / p.tiles_x, tx = t_in - ty * p.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
+    int f, y0, x0;
+    tile_origin<TH>(p, tile, f, y0, x0);
     const int H = p.h, W = p.w;
     const int Q = p.qa + p.qb;
 
-    // epilogue coefficients, as k_conv3x3: scale (1 when absent) and shift - center * scale, applied as one fma
-    if (tid < NCO) {
-        const int c = cob * NCO + tid;
-        const bool in = c < p.c_out;
-        const float sc = p.scale && in ? p.scale[c] : 1.0f;
-        const float ce = p.center && in ? p.center[c] : 0.0f;
-        const float sh = p.shift && in ? p.shift[c] : 0.0f;
-        s_par[0][tid] = sc;
-        s_par[1][tid] = __fsub_rn(sh, __fmul_rn(ce, sc));
-    }
+    epilogue_coeffs<1>(p, cob, s_par, tid);
     const int n_run = POOLED ? find_runs<UH, UW>(p, f, y0, x0, runs) : 0;  // (s_par: published by the next barrier)
 
     f32x16 acc[4][RPW];  // [2 py + px][input row of the wave]
@@ -96,126 +84,46 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_upconv3x3(const ConvArgs p) {
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 const int par = 2 * (ky & 1) + (kx & 1), dy = ky >> 1, dx = kx >> 1;
-                const uint8_t *brow = s_w + piece_off<true, 0>((8 - (ky * 3 + kx)) * NCO + pl, hf);
-                if constexpr (sizeof(T) == 4) {
-                    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(brow);
+                const Frag<T> b = lds_frag<T>(s_w + piece_off<true, 0>((8 - (ky * 3 + kx)) * NCO + pl, hf));
 #pragma unroll
-                    for (int m = 0; m < RPW; ++m) {
-                        // lane half h supplies channels 4h+s of the chunk to MFMA s (both operands)
-                        const f32x4 a4 = *reinterpret_cast<const f32x4 *>(
-                            s_in + piece_off<true, 0>((RPW * wave + m + 1 - dy) * UW + pl + 1 - dx, hf));
-#pragma unroll
-                        for (int s = 0; s < 4; ++s)
-                            acc[par][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4[s], a4[s], acc[par][m], 0, 0, 0);
-                    }
-                } else {
-                    const bf16x8 b8 = *reinterpret_cast<const bf16x8 *>(brow);
-#pragma unroll
-                    for (int m = 0; m < RPW; ++m) {
-                        const bf16x8 a8 = *reinterpret_cast<const bf16x8 *>(
-                            s_in + piece_off<true, 0>((RPW * wave + m + 1 - dy) * UW + pl + 1 - dx, hf));
-                        acc[par][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b8, a8, acc[par][m], 0, 0, 0);
-                    }
+                for (int m = 0; m < RPW; ++m) {
+                    const Frag<T> a =
+                        lds_frag<T>(s_in + piece_off<true, 0>((RPW * wave + m + 1 - dy) * UW + pl + 1 - dx, hf));
+                    acc[par][m] = mfma_tap<T>(b, a, acc[par][m]);
                 }
             }
         }
         __syncthreads();  // the chunk's buffers are restaged next
     }
 
-    // ---- epilogue, k_conv3x3's: acc element i of (par, m) is channel cob*32 + 8(i>>2) + 4h + (i&3) of output
-    // pixel (2 (y0 + RPW w + m) + py, 2 (x0 + pl) + px). A row of 32 pixels (every second output pixel of one
-    // output row) goes through LDS (wave-private) and out as 16-byte pieces; blocks whose channels are not whole
-    // or whose rows are not 16-byte aligned store channel by channel.
-    // Its arguments are read again here, through a kernel-argument pointer the compiler cannot see through: read
-    // once at the kernel's start they would sit in scalar registers across the whole K loop (and spill).
-    uint64_t kargs = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kargs));
-    const auto &pe = *(const __attribute__((address_space(4))) ConvArgs *)kargs;
-    constexpr int HE = E::HE, PPP = NCO / HE;  // channels per piece, pieces per pixel
-    const int x = x0 + pl;
+    // ---- epilogue (epilogue_row): acc element i of (par, m) is channel cob*32 + 8(i>>2) + 4h + (i&3) of output
+    // pixel (2 (y0 + RPW w + m) + py, 2 (x0 + pl) + px); a row of 32 pixels is every second output pixel of one
+    // output row. The lane's 8 output pixels are summed parities first, then rows: the statistics' fixed order.
+    // The arguments are read again here: read once at the kernel's start they would sit in scalar registers
+    // across the whole K loop (and spill).
+    const ConvArgs pe = kernarg_again<ConvArgs>(0);
     const int64_t out_row0 = (int64_t)f * 4 * H * W;  // the frame's first output row: 2H x 2W pixels per frame
-    uint8_t *const s_o = s_buf + wave * 32 * OPITCH;
-    const bool fast = pe.vec_out && cob * NCO + NCO <= pe.c_out;
-    float s1[16], s2[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s1[i] = s2[i] = 0.0f;
+    uint8_t *const s_o = s_buf + wave * 32 * OPITCH<T>;
+    ChanSums sums;
+    sums.zero();
 #pragma unroll
     for (int par = 0; par < 4; ++par) {
         const int py = par >> 1, px = par & 1;
 #pragma unroll
         for (int m = 0; m < RPW; ++m) {
             const int y = y0 + RPW * wave + m;
-            const bool ok = y < H && x < W;
             const int64_t orow = out_row0 + (int64_t)(2 * y + py) * (2 * W) + px;  // + 2 * input column
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int cl = 8 * g + 4 * hf, c = cob * NCO + cl;  // first channel of the run
-                const f32x4 scl = *reinterpret_cast<const f32x4 *>(&s_par[0][cl]);
-                const f32x4 sft = *reinterpret_cast<const f32x4 *>(&s_par[1][cl]);
-                T o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = acc[par][m][4 * g + j];
-                    if (STATS && ok) {
-                        s1[4 * g + j] = __fadd_rn(s1[4 * g + j], v);
-                        s2[4 * g + j] = __fadd_rn(s2[4 * g + j], __fmul_rn(v, v));
-                    }
-                    o[j] = relu_bits(E::back(__builtin_fmaf(v, scl[j], sft[j])), pe.act == 1);
-                }
-                if (fast) {
-                    __builtin_memcpy(s_o + pl * OPITCH + cl * sizeof(T), o, sizeof(o));
-                } else if (ok) {
-                    T *dst = reinterpret_cast<T *>(pe.out) + (orow + 2 * x) * pe.out_stride + c;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (c + j >= pe.c_out) break;
-                        dst[j] = o[j];
-                    }
-                }
-            }
-            if (fast) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's row is in LDS (one wave: in order)
-#pragma unroll
-                for (int k = 0; k < 32 * PPP / 64; ++k) {
-                    const int pc = lane + 64 * k, pxl = pc / PPP, pi = pc % PPP;
-                    const u32x4 v = *reinterpret_cast<const u32x4 *>(s_o + pxl * OPITCH + pi * 16);
-                    if (y < H && x0 + pxl < W)
-                        *reinterpret_cast<u32x4 *>(reinterpret_cast<T *>(pe.out) +
-                                                   (orow + 2 * (x0 + pxl)) * pe.out_stride + cob * NCO + pi * HE) = v;
-                }
-            }
+            epilogue_row<T, true, STATS>(pe, acc[par][m], s_par[0], s_o, cob * NCO, y < H, x0, W, &sums,
+                                         [orow, x0](const ConvArgs &a, int col, int c) {
+                                             return reinterpret_cast<T *>(a.out) +
+                                                    (orow + 2 * (x0 + col)) * a.out_stride + c;
+                                         });
         }
     }
     if (STATS) {
-        // per channel: the lane's 8 output pixels are summed above (parities, then rows, a fixed order); over the
-        // 32 pixels of the lane half by k_conv3x3's halving butterfly, then over the 4 waves in double
-#pragma unroll
-        for (int n = 8, off = 16; n >= 1; n >>= 1, off >>= 1) {
-            const bool up = (pl & off) != 0;
-#pragma unroll
-            for (int i = 0; i < n; ++i) {
-                const float g1 = up ? s1[i] : s1[i + n], k1 = up ? s1[i + n] : s1[i];
-                const float g2 = up ? s2[i] : s2[i + n], k2 = up ? s2[i + n] : s2[i];
-                s1[i] = __fadd_rn(k1, __shfl_xor(g1, off, 64));
-                s2[i] = __fadd_rn(k2, __shfl_xor(g2, off, 64));
-            }
-        }
-        s1[0] = __fadd_rn(s1[0], __shfl_xor(s1[0], 1, 64));
-        s2[0] = __fadd_rn(s2[0], __shfl_xor(s2[0], 1, 64));
-        if ((pl & 1) == 0) {
-            const int i = pl >> 1, cl = 8 * (i >> 2) + 4 * hf + (i & 3);
-            s_red[wave][0][cl] = s1[0];
-            s_red[wave][1][cl] = s2[0];
-        }
-        __syncthreads();
         int te = tid;  // (opaque, as the staging's: `tid < 64` is not kept as a lane mask from the kernel's start)
         asm volatile("" : "+v"(te));
-        if (te < 2 * NCO) {
-            const int st = te >> 5, c = te & 31;
-            double sum = 0.0;
-            for (int w = 0; w < 4; ++w) sum += (double)s_red[w][st][c];
-            pe.part[((int64_t)(cob * NCO + c) * 2 + st) * pe.n_tiles + tile] = sum;
-        }
+        stats_reduce_tile(pe, sums, s_red, te, cob * NCO, tile);
     }
 }
 
@@ -223,26 +131,14 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_upconv3x3(const ConvArgs p) {
 template <typename T>
 int up_launch(const UpPlan &pl, const ConvArgs &a, bool pooled, bool stats, const void *w, const int64_t *frame_off,
               double *d_stats, hipStream_t s) {
-    T *wp = reinterpret_cast<T *>(const_cast<void *>(a.wp));
-    const int64_t wtot = (int64_t)pl.n_cob * (pl.qa + pl.qb) * W_ROWS * Elem<T>::CK;
-    hipLaunchKernelGGL(k_pack_w<T>, dim3(grid_for(wtot, SHPL_BLOCK, 4096)), dim3(SHPL_BLOCK), 0, s,
-                       reinterpret_cast<const T *>(w), a.c_a, pl.qa, a.c_b, pl.qb, a.c_out, pl.n_cob, 1, wp);
-    SHPL_LAUNCH_CHECK();
+    if (const int rc = pack_weights<T>(a, w, pl.n_cob, 1, s)) return rc;
     if (pooled) {
-        hipLaunchKernelGGL(k_row_ptr, dim3(16, a.n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, frame_off, a.h, a.w,
-                           const_cast<int32_t *>(a.row_ptr));
-        SHPL_LAUNCH_CHECK();
+        if (const int rc = row_pointers(a, frame_off, s)) return rc;
     }
-    const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
     using Kernel = void (*)(const ConvArgs);
-    const Kernel kernel = by_bools(
-        [](auto po, auto st, auto gr) -> Kernel {
-            if constexpr (gr() && !po())
-                return nullptr;  // no such form: `group` never says so
-            else
-                return k_upconv3x3<T, po(), st(), gr()>;
-        },
-        pooled, stats, group);
+    const Kernel kernel = pooled_form<Kernel>(pooled, a.ent_col, [&](auto po, auto gr) {
+        return stats ? k_upconv3x3<T, po(), true, gr()> : k_upconv3x3<T, po(), false, gr()>;
+    });
     hipLaunchKernelGGL(kernel, dim3((unsigned)pl.n_tiles, (unsigned)pl.n_cob), dim3(CONV_BLOCK), 0, s, a);
     SHPL_LAUNCH_CHECK();
     if (stats) {
@@ -287,30 +183,7 @@ extern "C" int shpl_upconv3x3(int dtype, int n_frames, int64_t h, int64_t w, con
     if (rc) return rc;
     if (pl.n_tiles == 0) return SHPL_OK;
     if (!d_out || (c_a > 0 && !d_a)) return SHPL_ERR_ARG;
-    const int he = piece_elems(dtype);
-    ConvArgs a = {};
-    a.n_frames = n_frames;
-    a.h = (int)h;
-    a.w = (int)w;
-    a.tiles_x = pl.tiles_x;
-    a.tiles_per_frame = pl.tiles_per_frame;
-    a.n_tiles = (int)pl.n_tiles;
-    a.a = d_a;
-    a.a_stride = a_stride;
-    a.a_off = a_off;
-    a.c_a = (int)c_a;
-    a.qa = pl.qa;
-    a.b = d_b;
-    a.b_stride = b_stride;
-    a.b_off = b_off;
-    a.c_b = (int)c_b;
-    a.qb = pl.qb;
-    a.vec_a = vec16(A, he);
-    a.vec_b = vec16(B, he);
-    a.ent_dst = pooled ? pool->ent_dst : nullptr;
-    a.ent_src = pooled ? pool->ent_src : nullptr;
-    a.ent_val = pooled ? pool->ent_val : nullptr;
-    a.ent_col = pooled ? pool->ent_col : nullptr;
+    ConvArgs a = conv_args(dtype, n_frames, h, w, pl, A, B, pool);
     a.wp = region<void>(d_ws, pl.wp);
     a.row_ptr = pooled ? region<int32_t>(d_ws, pl.row_ptr) : nullptr;
     a.part = stats ? region<double>(d_ws, pl.part) : nullptr;
@@ -321,7 +194,7 @@ extern "C" int shpl_upconv3x3(int dtype, int n_frames, int64_t h, int64_t w, con
     a.out = d_out;
     a.out_stride = out_stride;
     a.c_out = (int)c_out;
-    a.vec_out = vec16({d_out, out_stride, 0, c_out}, he);
+    a.vec_out = vec16({d_out, out_stride, 0, c_out}, piece_elems(dtype));
     hipStream_t s = (hipStream_t)stream;
     return by_dtype(dtype, [&](auto t) {
         return up_launch<typename decltype(t)::T>(pl, a, pooled, stats, d_weights, d_frame_off, d_stats, s);

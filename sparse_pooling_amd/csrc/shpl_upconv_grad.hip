@@ -75,11 +75,10 @@ constexpr int DPW = TW + 1, DPLN = (TH + 1) * DPW;  // a parity plane of the 8 x
 template <typename T, int NB>
 __global__ __launch_bounds__(CONV_BLOCK, 2) void k_upconv3x3_dgrad(const ConvArgs p) {
     typedef Elem<T> E;
-    constexpr int CK = E::CK, HE = E::HE, NP = E::NP;
+    constexpr int CK = E::CK, NP = E::NP;
     static_assert(NP == 2, "two 16-byte pieces per LDS row (the swizzle)");
     constexpr int G_BYTES = 4 * DPLN * NP * 16, W_PIECES = W_ROWS * NP, W_BYTES = NB * W_PIECES * 16;
-    constexpr int OPITCH = NCO * (int)sizeof(T) + 16;  // the epilogue's rows reuse the chunk buffers
-    static_assert(4 * 32 * OPITCH <= G_BYTES + W_BYTES, "epilogue rows fit the chunk buffers");
+    static_assert(4 * 32 * OPITCH<T> <= G_BYTES + W_BYTES, "the epilogue's rows reuse the chunk buffers");
     __shared__ __attribute__((aligned(16))) uint8_t s_buf[G_BYTES + W_BYTES];
     uint8_t *const s_g = s_buf, *const s_w = s_buf + G_BYTES;
 
@@ -87,10 +86,8 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_upconv3x3_dgrad(const ConvArg
     const int pl = lane & 31, hf = lane >> 5;
     const int tile = (int)xcd_block((int)blockIdx.x, p.n_tiles);
     const int cib0 = blockIdx.y * NB;  // the workgroup's first dx block
-    const int f = tile / p.tiles_per_frame;
-    const int t_in = tile - f * p.tiles_per_frame;
-    const int ty = t_in / p.tiles_x, tx = t_in - ty * p.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
+    int f, y0, x0;
+    tile_origin<TH>(p, tile, f, y0, x0);
     const int H = p.h, W = p.w, Q = p.qa;
 
     f32x16 acc[NB][RPW];
@@ -102,20 +99,16 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_upconv3x3_dgrad(const ConvArg
             for (int i = 0; i < 16; ++i) acc[cb][m][i] = 0.0f;
 
     const T *gy = reinterpret_cast<const T *>(p.a);
-    const T *wq = reinterpret_cast<const T *>(p.wp) + (int64_t)cib0 * Q * W_ROWS * CK;
+    const int64_t wq_cb = (int64_t)Q * W_ROWS * CK;  // one dx block further in the packed weights
+    const T *wq = reinterpret_cast<const T *>(p.wp) + cib0 * wq_cb;
     for (int q = 0; q < Q; ++q) {
-#pragma unroll
-        for (int cb = 0; cb < NB; ++cb) {  // the chunk's weight rows of each dx block, W_PIECES slots apart
-#pragma unroll
-            for (int u = 0; u < (W_PIECES + CONV_BLOCK - 1) / CONV_BLOCK; ++u) {
-                const int base = u * CONV_BLOCK + wave * 64;
-                if (base >= W_PIECES) break;
-                const int k = base + lane, row = k >> 1, g = (k & 1) ^ ((row >> 3) & 1);
-                if (k < W_PIECES)
-                    dma16(wq + (((int64_t)cb * Q + q) * W_ROWS + row) * CK + g * HE, s_w + (cb * W_PIECES + base) * 16);
-            }
-        }
-        stage_planes<T, TH, NP, true>(gy, p.a_stride, p.c_a, p.vec_a, q * CK, f, y0, x0, H, W, s_g, tid);
+        stage_weights<T, NB>(wq, wq_cb, q, s_w, tid);
+        // the tile's origin and the thread's index, opaque per chunk, as in k_upconv3x3: each lane's part of the
+        // planes' addresses is worked out per chunk, not kept in some 20 registers across the loop (which the
+        // compiler does or does not do at the slightest change here; at NB = 4 that is past the 256 there are)
+        int yq = y0, xq = x0, tq = tid;
+        asm volatile("" : "+s"(yq), "+s"(xq), "+v"(tq));
+        stage_planes<T, TH, NP, true>(gy, p.a_stride, p.c_a, p.vec_a, q * CK, f, yq, xq, H, W, s_g, tq);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMAs have landed
         __syncthreads();
 #pragma unroll
@@ -123,95 +116,38 @@ __global__ __launch_bounds__(CONV_BLOCK, 2) void k_upconv3x3_dgrad(const ConvArg
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 const int par = 2 * (ky & 1) + (kx & 1), dy = ky >> 1, dx = kx >> 1;
-                if constexpr (sizeof(T) == 4) {
-                    f32x4 a4[RPW];
+                Frag<T> a[RPW];
 #pragma unroll
-                    for (int m = 0; m < RPW; ++m)
-                        a4[m] = *reinterpret_cast<const f32x4 *>(
-                            s_g + piece_off<true, 0>(par * DPLN + (RPW * wave + m + dy) * DPW + pl + dx, hf));
+                for (int m = 0; m < RPW; ++m)
+                    a[m] = lds_frag<T>(s_g +
+                                       piece_off<true, 0>(par * DPLN + (RPW * wave + m + dy) * DPW + pl + dx, hf));
 #pragma unroll
-                    for (int cb = 0; cb < NB; ++cb) {
-                        // lane half h supplies channels 4h+s of the chunk to MFMA s (both operands)
-                        const f32x4 b4 = *reinterpret_cast<const f32x4 *>(
-                            s_w + cb * W_PIECES * 16 + piece_off<true, 0>((ky * 3 + kx) * NCO + pl, hf));
+                for (int cb = 0; cb < NB; ++cb) {
+                    const Frag<T> b =
+                        lds_frag<T>(s_w + cb * W_PIECES * 16 + piece_off<true, 0>((ky * 3 + kx) * NCO + pl, hf));
 #pragma unroll
-                        for (int m = 0; m < RPW; ++m)
-#pragma unroll
-                            for (int s = 0; s < 4; ++s)
-                                acc[cb][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4[s], a4[m][s], acc[cb][m], 0, 0, 0);
-                    }
-                } else {
-                    bf16x8 a8[RPW];
-#pragma unroll
-                    for (int m = 0; m < RPW; ++m)
-                        a8[m] = *reinterpret_cast<const bf16x8 *>(
-                            s_g + piece_off<true, 0>(par * DPLN + (RPW * wave + m + dy) * DPW + pl + dx, hf));
-#pragma unroll
-                    for (int cb = 0; cb < NB; ++cb) {
-                        const bf16x8 b8 = *reinterpret_cast<const bf16x8 *>(
-                            s_w + cb * W_PIECES * 16 + piece_off<true, 0>((ky * 3 + kx) * NCO + pl, hf));
-#pragma unroll
-                        for (int m = 0; m < RPW; ++m)
-                            acc[cb][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b8, a8[m], acc[cb][m], 0, 0, 0);
-                    }
+                    for (int m = 0; m < RPW; ++m) acc[cb][m] = mfma_tap<T>(b, a[m], acc[cb][m]);
                 }
             }
         }
         __syncthreads();  // the chunk's buffers are restaged next
     }
 
-    // ---- epilogue: acc element i of (cb, m) is dx channel (cib0 + cb) * 32 + 8 (i >> 2) + 4 h + (i & 3) of input
-    // pixel (y0 + RPW w + m, x0 + pl). A row of 32 pixels goes through LDS (wave-private) and out as 16-byte
-    // pieces, each to the map its channels belong to (vec_out: c_split is a whole number of pieces); blocks whose
-    // channels are not whole or whose rows are not 16-byte aligned store channel by channel.
-    constexpr int PPP = NCO / HE;  // pieces per pixel
-    const int x = x0 + pl;
-    uint8_t *const s_o = s_buf + wave * 32 * OPITCH;
-    T *const out = reinterpret_cast<T *>(p.out), *const out2 = reinterpret_cast<T *>(p.out2);
+    // ---- epilogue (epilogue_row, without the fma): acc element i of (cb, m) is dx channel (cib0 + cb) * 32 +
+    // 8 (i >> 2) + 4 h + (i & 3) of input pixel (y0 + RPW w + m, x0 + pl); each 16-byte piece goes to the map its
+    // channels belong to (out_ptr; vec_out: c_split is a whole number of pieces).
+    uint8_t *const s_o = s_buf + wave * 32 * OPITCH<T>;
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) {
         const int cb0 = (cib0 + cb) * NCO;
         if (cb0 >= p.c_out) break;
-        const bool fast = p.vec_out && cb0 + NCO <= p.c_out;
 #pragma unroll
         for (int m = 0; m < RPW; ++m) {
             const int y = y0 + RPW * wave + m;
-            const bool ok = y < H && x < W;
-            const int64_t row = ((int64_t)f * H + y) * W;  // + column
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int cl = 8 * g + 4 * hf, c = cb0 + cl;  // first channel of the run
-                T o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = E::back(acc[cb][m][4 * g + j]);
-                if (fast) {
-                    __builtin_memcpy(s_o + pl * OPITCH + cl * sizeof(T), o, sizeof(o));
-                } else if (ok) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int cc = c + j;
-                        if (cc >= p.c_out) break;
-                        if (cc < p.c_split)
-                            out[(row + x) * p.out_stride + cc] = o[j];
-                        else
-                            out2[(row + x) * p.out2_stride + cc - p.c_split] = o[j];
-                    }
-                }
-            }
-            if (fast) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's row is in LDS (one wave: in order)
-#pragma unroll
-                for (int k = 0; k < 32 * PPP / 64; ++k) {
-                    const int pc = lane + 64 * k, pxl = pc / PPP, pi = pc % PPP;
-                    const u32x4 v = *reinterpret_cast<const u32x4 *>(s_o + pxl * OPITCH + pi * 16);
-                    const int cc = cb0 + pi * HE;
-                    if (y < H && x0 + pxl < W) {
-                        T *dst = cc < p.c_split ? out + (row + x0 + pxl) * p.out_stride + cc
-                                                : out2 + (row + x0 + pxl) * p.out2_stride + cc - p.c_split;
-                        *reinterpret_cast<u32x4 *>(dst) = v;
-                    }
-                }
-            }
+            const int64_t row = ((int64_t)f * H + y) * W + x0;  // + column of the tile
+            epilogue_row<T, false, false>(
+                p, acc[cb][m], nullptr, s_o, cb0, y < H, x0, W, nullptr,
+                [row](const ConvArgs &a, int col, int c) { return out_ptr<T>(a, row + col, c); });
         }
     }
 }
@@ -252,33 +188,6 @@ __device__ __forceinline__ bf16x8 tr_pixels(const uint8_t *at) {
     return out;
 }
 
-// A kernel argument read again from the kernel-argument segment (at: its byte offset there), word by word, through
-// a pointer the compiler cannot see through.
-template <typename S>
-__device__ __forceinline__ S kernarg_again(unsigned at) {
-    static_assert(sizeof(S) % 4 == 0, "whole words");
-    uint64_t kargs = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kargs));
-    const __attribute__((address_space(4))) uint32_t *src =
-        (const __attribute__((address_space(4))) uint32_t *)(kargs + at);
-    uint32_t w[sizeof(S) / 4];
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(S) / 4; ++i) w[i] = src[i];
-    S out;
-    __builtin_memcpy(&out, w, sizeof(S));
-    return out;
-}
-
-// Frame and origin of a tile, worked out again (from an opaque copy of its index) wherever the arguments are read
-// again, instead of held in three scalar registers across the tile's steps.
-__device__ __forceinline__ void tile_origin(const ConvArgs &p, int tile, int &f, int &y0, int &x0) {
-    asm volatile("" : "+s"(tile));
-    f = tile / p.tiles_per_frame;
-    const int t_in = tile - f * p.tiles_per_frame;
-    const int ty = t_in / p.tiles_x;
-    y0 = ty * WTH;
-    x0 = (t_in - ty * p.tiles_x) * TW;
-}
 
 // ConvArgs as the forward fills them (the sources, the pool, the row pointers), tiled by WTH x 32.
 template <typename T, bool POOLED, bool GROUP>
@@ -310,7 +219,7 @@ __global__ __launch_bounds__(CONV_BLOCK, sizeof(T) == 4 ? 1 : 2) void k_upconv3x
         // loop, and read once per tile across all of its steps (and spill)
         ConvArgs pq = kernarg_again<ConvArgs>(0);
         int f, y0, x0;
-        tile_origin(pq, tile, f, y0, x0);
+        tile_origin<WTH, true>(pq, tile, f, y0, x0);
         // the thread's index, opaque per tile: the staging's per-lane conditions on it (a piece of the tile, inside
         // the map, a pooled chunk) are then worked out per tile instead of kept across the tile loop as lane masks,
         // two scalar registers each, which ran the pooled forms out of scalar registers (as in k_upconv3x3)
@@ -322,7 +231,7 @@ __global__ __launch_bounds__(CONV_BLOCK, sizeof(T) == 4 ? 1 : 2) void k_upconv3x
         const int n_run = pooled_blk ? find_runs<WTH, TW>(pq, f, y0 + 1, x0 + 1, runs, tq) : 0;
         // ---- x: [pixel][chunk of the block][2 pieces]; chunks past the last one hold zeros
         pq = kernarg_again<ConvArgs>(0);
-        tile_origin(pq, tile, f, y0, x0);
+        tile_origin<WTH, true>(pq, tile, f, y0, x0);
         const int H = pq.h, W = pq.w, Q = pq.qa + pq.qb;
         const int64_t frame_row0 = (int64_t)f * H * W;
 #pragma unroll
@@ -348,14 +257,14 @@ __global__ __launch_bounds__(CONV_BLOCK, sizeof(T) == 4 ? 1 : 2) void k_upconv3x
             for (int j = 0; j < NQ; ++j) {
                 const int q = cib * NQ + j;
                 pq = kernarg_again<ConvArgs>(0);
-                tile_origin(pq, tile, f, y0, x0);
+                tile_origin<WTH, true>(pq, tile, f, y0, x0);
                 if (q >= pq.qa && q < pq.qa + pq.qb)
                     stage_halo<T, true, PB, false, GROUP, WTH, TW>(pq, q, f, y0 + 1, x0 + 1, s_x + j * E::CB, runs,
                                                                    n_run, tq);
             }
         }
         pq = kernarg_again<ConvArgs>(0);
-        tile_origin(pq, tile, f, y0, x0);
+        tile_origin<WTH, true>(pq, tile, f, y0, x0);
         const UwArgs gq = kernarg_again<UwArgs>(UW_AT);
         stage_planes<T, WTH, NPP, false>(reinterpret_cast<const T *>(gq.gy), gq.gy_stride, pq.c_out, gq.vec_g,
                                          __builtin_amdgcn_readfirstlane(cob_v) * NCO, f,
@@ -515,19 +424,7 @@ extern "C" int shpl_upconv3x3_dgrad(int dtype, int n_frames, int64_t h, int64_t 
     const UpPlan &pl = dp.up;
     if (pl.n_tiles == 0) return SHPL_OK;
     if (!d_gy || (c_split > 0 && !d_dx)) return SHPL_ERR_ARG;
-    const int he = piece_elems(dtype);
-    ConvArgs a = {};
-    a.n_frames = n_frames;
-    a.h = (int)h;
-    a.w = (int)w;
-    a.tiles_x = pl.tiles_x;
-    a.tiles_per_frame = pl.tiles_per_frame;
-    a.n_tiles = (int)pl.n_tiles;
-    a.a = d_gy;
-    a.a_stride = gy_stride;
-    a.c_a = (int)c_gy;
-    a.qa = pl.qa;
-    a.vec_a = vec16({d_gy, gy_stride, 0, c_gy}, he);
+    ConvArgs a = conv_args(dtype, n_frames, h, w, pl, {d_gy, gy_stride, 0, c_gy}, {}, nullptr);
     a.wp = region<void>(d_ws, dp.wp);
     a.out = d_dx;
     a.out_stride = dx_stride;
@@ -535,17 +432,12 @@ extern "C" int shpl_upconv3x3_dgrad(int dtype, int n_frames, int64_t h, int64_t 
     a.out2 = d_dx_b;
     a.out2_stride = dx_b_stride;
     a.c_split = (int)c_split;
-    a.vec_out = (!d_dx || (aligned16(d_dx) && dx_stride % he == 0)) &&
-                (!d_dx_b || (aligned16(d_dx_b) && dx_b_stride % he == 0 && c_split % he == 0));
+    a.vec_out = vec_out_split(d_dx, dx_stride, d_dx_b, dx_b_stride, c_split, piece_elems(dtype));
     hipStream_t s = (hipStream_t)stream;
     const int n_blk = dp.n_cbg * dp.nb;
     return by_dtype(dtype, [&](auto t) -> int {
         typedef typename decltype(t)::T T;
-        const int64_t wtot = (int64_t)n_blk * pl.qa * W_ROWS * Elem<T>::CK;
-        hipLaunchKernelGGL(k_pack_w<T>, dim3(grid_for(wtot, SHPL_BLOCK, 4096)), dim3(SHPL_BLOCK), 0, s,
-                           reinterpret_cast<const T *>(d_weights), a.c_a, pl.qa, 0, 0, a.c_out, n_blk, 0,
-                           reinterpret_cast<T *>(const_cast<void *>(a.wp)));
-        SHPL_LAUNCH_CHECK();
+        if (const int rc = pack_weights<T>(a, d_weights, n_blk, 0, s)) return rc;
         using Kernel = void (*)(const ConvArgs);
         const Kernel kernel = dp.nb == 4   ? k_upconv3x3_dgrad<T, 4>
                               : dp.nb == 2 ? k_upconv3x3_dgrad<T, 2>
@@ -585,29 +477,9 @@ extern "C" int shpl_upconv3x3_wgrad(int dtype, int n_frames, int64_t h, int64_t 
     if (!d_gy || (c_a > 0 && !d_a)) return SHPL_ERR_ARG;
     const UpPlan &pl = wp.up;
     const int he = piece_elems(dtype);
-    ConvArgs a = {};
-    a.n_frames = n_frames;
-    a.h = (int)h;
-    a.w = (int)w;
-    a.tiles_x = pl.tiles_x;
-    a.tiles_per_frame = wp.tiles_per_frame;
+    ConvArgs a = conv_args(dtype, n_frames, h, w, pl, A, B, pool);
+    a.tiles_per_frame = wp.tiles_per_frame;  // the WTH x 32 tiling
     a.n_tiles = (int)wp.n_tiles;
-    a.a = d_a;
-    a.a_stride = a_stride;
-    a.a_off = a_off;
-    a.c_a = (int)c_a;
-    a.qa = pl.qa;
-    a.b = d_b;
-    a.b_stride = b_stride;
-    a.b_off = b_off;
-    a.c_b = (int)c_b;
-    a.qb = pl.qb;
-    a.vec_a = vec16(A, he);
-    a.vec_b = vec16(B, he);
-    a.ent_dst = pooled ? pool->ent_dst : nullptr;
-    a.ent_src = pooled ? pool->ent_src : nullptr;
-    a.ent_val = pooled ? pool->ent_val : nullptr;
-    a.ent_col = pooled ? pool->ent_col : nullptr;
     a.row_ptr = pooled ? region<int32_t>(d_ws, wp.row_ptr) : nullptr;
     a.c_out = (int)c_out;
     UwArgs g = {};
@@ -620,22 +492,14 @@ extern "C" int shpl_upconv3x3_wgrad(int dtype, int n_frames, int64_t h, int64_t 
     g.part = region<float>(d_ws, wp.part);
     hipStream_t s = (hipStream_t)stream;
     if (pooled) {
-        hipLaunchKernelGGL(k_row_ptr, dim3(16, n_frames), dim3(SHPL_BLOCK), 0, s, a.ent_dst, d_frame_off, a.h, a.w,
-                           const_cast<int32_t *>(a.row_ptr));
-        SHPL_LAUNCH_CHECK();
+        rc = row_pointers(a, d_frame_off, s);
+        if (rc) return rc;
     }
-    const bool group = pooled && a.ent_col;  // the pixel-keyed CSR's per-column partials
     using Kernel = void (*)(const ConvArgs, const UwArgs);
     const Kernel kernel = by_dtype(dtype, [&](auto t) {
         typedef typename decltype(t)::T T;
-        return by_bools(
-            [](auto po, auto gr) -> Kernel {
-                if constexpr (gr() && !po())
-                    return nullptr;  // no such form: `group` never says so
-                else
-                    return k_upconv3x3_wgrad<T, po(), gr()>;
-            },
-            pooled, group);
+        return pooled_form<Kernel>(pooled, a.ent_col,
+                                   [](auto po, auto gr) -> Kernel { return k_upconv3x3_wgrad<T, po(), gr()>; });
     });
     hipLaunchKernelGGL(kernel, dim3((unsigned)wp.n_groups, (unsigned)wp.n_cib, (unsigned)pl.n_cob), dim3(CONV_BLOCK),
                        0, s, a, g);
