@@ -262,18 +262,21 @@ def workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
-def index_ws_bytes(n_frames, max_points):
+def ws_bytes(symbol, *args):
+    """The size a ``<symbol>_workspace_bytes`` query of the library reports for these arguments (the size_t
+    out-parameter is appended here); None, a pooling CSR's entry capacity without a pool, goes as -1."""
     out = ctypes.c_size_t()
-    check(lib().shpl_build_index_workspace_bytes(int(n_frames), int(max_points), ctypes.byref(out)),
-          "shpl_build_index_workspace_bytes")
+    name = symbol + "_workspace_bytes"
+    check(getattr(lib(), name)(*[-1 if a is None else int(a) for a in args], ctypes.byref(out)), name)
     return out.value
+
+
+def index_ws_bytes(n_frames, max_points):
+    return ws_bytes("shpl_build_index", n_frames, max_points)
 
 
 def csr_ws_bytes(n_keys, nnz_cap):
-    out = ctypes.c_size_t()
-    check(lib().shpl_csr_workspace_bytes(int(n_keys), int(nnz_cap), ctypes.byref(out)),
-          "shpl_csr_workspace_bytes")
-    return out.value
+    return ws_bytes("shpl_csr", n_keys, nnz_cap)
 
 
 def dtype_code(t):
@@ -285,10 +288,7 @@ def dtype_code(t):
 
 
 def bucket_ws_bytes(n_frames, max_points, nnz_cap, cells_per_frame, pix_per_frame):
-    out = ctypes.c_size_t()
-    check(lib().shpl_bucket_workspace_bytes(int(n_frames), int(max_points), int(nnz_cap), int(cells_per_frame),
-                                            int(pix_per_frame), ctypes.byref(out)), "shpl_bucket_workspace_bytes")
-    return out.value
+    return ws_bytes("shpl_bucket", n_frames, max_points, nnz_cap, cells_per_frame, pix_per_frame)
 
 
 def bucket_workspace(n_frames, max_points, nnz_cap, cells_per_frame, pix_per_frame, device):

@@ -116,10 +116,7 @@ def bev_slices_batch(points, point_offsets, planes, area_extents, voxel_size, he
     dm = torch.empty((F, nz, nx), dtype=torch.float64, device=dev) if maps else None
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     if ws is None:
-        import ctypes
-        nb = ctypes.c_size_t()
-        L.check(L.lib().shpl_bev_workspace_bytes(N, int(num_slices), ctypes.byref(nb)), "shpl_bev_workspace_bytes")
-        ws = L.workspace(nb.value, dev)
+        ws = L.workspace(L.ws_bytes("shpl_bev", N, num_slices), dev)
     p = lambda a: a.ctypes.data_as(L.ctypes.c_void_p)  # noqa: E731
     L.check(L.lib().shpl_bev_slices(F, L.ptr(point_offsets), L.ptr(point_counts), N, L.ptr(points), L.F64, L.ptr(planes), p(ext),
                                     float(voxel_size), int(num_slices), p(lo_a), p(hi_a), float(height_lo),

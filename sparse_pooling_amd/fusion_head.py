@@ -86,27 +86,18 @@ def _csr_ref(csr):
     return None if csr is None else csr.ref()
 
 
-def _ws_bytes(symbol, dtype, rows, c_a, rows_b, c_b, c_out, pooled):
-    out = ctypes.c_size_t()
-    L.check(getattr(L.lib(), symbol)(dtype, int(rows), int(c_a), int(rows_b), int(c_b), int(c_out), int(bool(pooled)),
-                                     ctypes.byref(out)), symbol)
-    return out.value
-
-
 def _workspace(mask, kind, device, *shape):
-    return L.workspace(_ws_bytes(_symbol(mask is not None, kind) + "_workspace_bytes", *shape), device)
+    return L.workspace(L.ws_bytes(_symbol(mask is not None, kind), *shape), device)
 
 
 def head_ws_bytes(dtype, rows, c_a, rows_b, c_b, c_out, pooled, wgrad=False):
     """Workspace of shpl_head1x1 / shpl_head1x1_dgrad (wgrad: of shpl_head1x1_wgrad)."""
-    return _ws_bytes(_symbol(False, "_wgrad" if wgrad else "") + "_workspace_bytes", dtype, rows, c_a, rows_b,
-                     c_b, c_out, pooled)
+    return L.ws_bytes(_symbol(False, "_wgrad" if wgrad else ""), dtype, rows, c_a, rows_b, c_b, c_out, bool(pooled))
 
 
 def head_drop_ws_bytes(dtype, rows, c_a, rows_b, c_b, c_out, pooled, wgrad=False):
     """Workspace of shpl_head1x1_drop / shpl_head1x1_drop_dgrad (wgrad: of shpl_head1x1_drop_wgrad)."""
-    return _ws_bytes(_symbol(True, "_wgrad" if wgrad else "") + "_workspace_bytes", dtype, rows, c_a, rows_b,
-                     c_b, c_out, pooled)
+    return L.ws_bytes(_symbol(True, "_wgrad" if wgrad else ""), dtype, rows, c_a, rows_b, c_b, c_out, bool(pooled))
 
 
 def _forward(a, weights, b, pool, bias, out, mask):

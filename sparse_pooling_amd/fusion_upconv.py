@@ -38,15 +38,14 @@ One stream, plain calls; neither route stores the fused map.
 """
 from __future__ import annotations
 
-import ctypes
-
-import numpy as np
 import torch
 
 from . import _lib as L
-from . import shpl_map as sm
-from .fusion_conv import (SIDE_BEV, SIDE_IMG, FusionConv, batch_norm_backward, batch_norm_train, conv3x3,
-                          conv3x3_dgrad, conv3x3_wgrad)
+from .fusion_conv import (FusionConv, _beta_bias_grads, _bn_relu_backward, _Call, _fused_call, _pull_back,
+                          _split_outputs, _TwoScopes, _wgrad_call, batch_norm_train, conv3x3, conv3x3_dgrad,
+                          conv3x3_wgrad)
+
+_UPCONV = _Call("shpl_upconv3x3", 2, 3, 2, "transposed conv", " (HWOI)")  # HWOI weights, 2H x 2W out
 
 # Per axis: tap k' of the stride-1 phase conv (it reads x[i + k' - 1]) -> tap k of the transposed conv, by
 # output parity. Parity 0 (o = 2i): k = 0 from x[i] (k' = 1), k = 2 from x[i-1] (k' = 0); parity 1 (o = 2i + 1):
@@ -96,12 +95,7 @@ def space_to_depth(y):
 
 def upconv_ws_bytes(dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap, stats):
     """Workspace of shpl_upconv3x3; pool_cap: the pooling CSR's entry capacity, or None without a pool."""
-    out = ctypes.c_size_t()
-    L.check(L.lib().shpl_upconv3x3_workspace_bytes(dtype, int(n_frames), int(h), int(w), int(c_a), int(c_b),
-                                                   int(c_out), -1 if pool_cap is None else int(pool_cap),
-                                                   int(bool(stats)), ctypes.byref(out)),
-            "shpl_upconv3x3_workspace_bytes")
-    return out.value
+    return L.ws_bytes("shpl_upconv3x3", dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap, bool(stats))
 
 
 def upconv3x3(a, weights, b=None, pool=None, frame_off=None, center=None, scale=None, shift=None, relu=True,
@@ -112,56 +106,18 @@ def upconv3x3(a, weights, b=None, pool=None, frame_off=None, center=None, scale=
     exactly as ``fusion_conv.conv3x3`` takes it (dense, pooled through the cell-keyed or the pixel-keyed CSR,
     or absent); stats: optional [2,Cout] float64 tensor receiving per-channel sum / sum of squares of the
     pre-epilogue output over the B*2H*2W rows."""
-    dt = L.dtype_code(a)
-    a = a if a.is_contiguous() else a.contiguous()
-    B, H, W, Ca = (int(s) for s in a.shape)
-    Cb = 0
-    if b is not None:
-        b = b if b.is_contiguous() else b.contiguous()
-        if b.dtype != a.dtype:
-            raise TypeError("both inputs of the transposed conv must share one dtype")
-        Cb = int(b.shape[-1])
-        if pool is None and tuple(b.shape[:3]) != (B, H, W):
-            raise ValueError(f"dense second input {tuple(b.shape)} does not match {tuple(a.shape)}")
-    if weights.dtype != a.dtype:
-        weights = weights.to(a.dtype)
-    weights = weights.contiguous()
-    Cout = int(weights.shape[2])
-    if tuple(weights.shape[:2]) != (3, 3) or int(weights.shape[3]) != Ca + Cb:
-        raise ValueError(f"weights {tuple(weights.shape)} (HWOI) do not match {Ca}+{Cb} input channels")
-    if out is None:
-        out = torch.empty((B, 2 * H, 2 * W, Cout), dtype=a.dtype, device=a.device)
-    if ws is None:
-        ws = L.workspace(upconv_ws_bytes(dt, B, H, W, Ca, Cb, Cout, None if pool is None else pool.nnz_cap,
-                                         stats is not None), a.device)
-    f32 = [None if v is None else v.to(device=a.device, dtype=torch.float32).contiguous()
-           for v in (center, scale, shift)]
-    L.check(L.lib().shpl_upconv3x3(dt, B, H, W, L.ptr(a), Ca, 0, Ca, L.ptr(b), Cb, 0, Cb,
-                                   None if pool is None else pool.ref(), L.ptr(frame_off), L.ptr(weights), Cout,
-                                   *[L.ptr(v) for v in f32], L.ACT_RELU if relu else L.ACT_NONE, L.ptr(out),
-                                   int(out.stride(2)), L.ptr(stats), L.ptr(ws), ws.numel(),
-                                   L.stream_of(a.device)), "shpl_upconv3x3")
-    return out
+    return _fused_call(_UPCONV, a, weights, b, pool, frame_off, center, scale, shift, relu, stats, out, ws)
 
 
 def upconv_grad_ws_bytes(which, dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap=None):
     """Workspace of shpl_upconv3x3_dgrad (which = "dgrad": c_a = c_gy, c_out = c_dx, c_b and pool_cap unused) or
     of shpl_upconv3x3_wgrad (which = "wgrad"; pool_cap: the pooling CSR's entry capacity, or None without a pool).
     h, w: the INPUT map's size."""
-    out = ctypes.c_size_t()
     if which == "dgrad":
-        L.check(L.lib().shpl_upconv3x3_dgrad_workspace_bytes(dtype, int(n_frames), int(h), int(w), int(c_a),
-                                                             int(c_out), ctypes.byref(out)),
-                "shpl_upconv3x3_dgrad_workspace_bytes")
-    elif which == "wgrad":
-        L.check(L.lib().shpl_upconv3x3_wgrad_workspace_bytes(dtype, int(n_frames), int(h), int(w), int(c_a),
-                                                             int(c_b), int(c_out),
-                                                             -1 if pool_cap is None else int(pool_cap),
-                                                             ctypes.byref(out)),
-                "shpl_upconv3x3_wgrad_workspace_bytes")
-    else:
-        raise ValueError(f"which = {which!r}: 'dgrad' or 'wgrad'")
-    return out.value
+        return L.ws_bytes("shpl_upconv3x3_dgrad", dtype, n_frames, h, w, c_a, c_out)
+    if which == "wgrad":
+        return L.ws_bytes("shpl_upconv3x3_wgrad", dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap)
+    raise ValueError(f"which = {which!r}: 'dgrad' or 'wgrad'")
 
 
 def upconv3x3_dgrad(gy, weights, c_dx, split=None, ws=None):
@@ -181,14 +137,11 @@ def upconv3x3_dgrad(gy, weights, c_dx, split=None, ws=None):
     if tuple(weights.shape) != (3, 3, Cg, c_dx):
         raise ValueError(f"weights {tuple(weights.shape)} (HWOI) do not match {Cg} -> {c_dx} channels")
     dt = L.dtype_code(gy)
-    c0 = c_dx if split is None else int(split)
-    dx = torch.empty((B, H, W, c0), dtype=gy.dtype, device=gy.device)
-    dx_b = None if split is None else torch.empty((B, H, W, c_dx - c0), dtype=gy.dtype, device=gy.device)
+    dx, dx_b, outs = _split_outputs(gy, (B, H, W), c_dx, split)
     if ws is None:
         ws = L.workspace(upconv_grad_ws_bytes("dgrad", dt, B, H, W, Cg, 0, c_dx), gy.device)
-    L.check(L.lib().shpl_upconv3x3_dgrad(dt, B, H, W, L.ptr(gy), int(gy.stride(2)), Cg, L.ptr(weights), c_dx,
-                                         L.ptr(dx), max(c0, 1), c0, L.ptr(dx_b), max(c_dx - c0, 1), L.ptr(ws),
-                                         ws.numel(), L.stream_of(gy.device)), "shpl_upconv3x3_dgrad")
+    L.check(L.lib().shpl_upconv3x3_dgrad(dt, B, H, W, L.ptr(gy), int(gy.stride(2)), Cg, L.ptr(weights), c_dx, *outs,
+                                         L.ptr(ws), ws.numel(), L.stream_of(gy.device)), "shpl_upconv3x3_dgrad")
     return dx if split is None else (dx, dx_b)
 
 
@@ -196,25 +149,10 @@ def upconv3x3_wgrad(a, gy, b=None, pool=None, frame_off=None, ws=None):
     """Weight gradient (f32 HWOI [3,3,Cout,Ca+Cb]) of ``upconv3x3`` of [a || b]: b dense, pooled through ``pool``
     (recomputed in the staging, never stored) or absent, as ``upconv3x3`` takes it; gy the gradient of the raw
     output, [B,2H,2W,Cout] (shpl_upconv3x3_wgrad)."""
-    a = a.contiguous()
-    gy = gy.contiguous()
-    dt = L.dtype_code(a)
-    B, H, W, Ca = (int(s) for s in a.shape)
-    Cb = 0 if b is None else int(b.shape[-1])
-    if b is not None:
-        b = b.contiguous()
-    Cout = int(gy.shape[-1])
+    B, H, W = (int(s) for s in a.shape[:3])
     if tuple(gy.shape[:3]) != (B, 2 * H, 2 * W) or gy.dtype != a.dtype:
         raise ValueError(f"the output gradient {tuple(gy.shape)} {gy.dtype} does not match the input {tuple(a.shape)}")
-    dw = torch.empty((3, 3, Cout, Ca + Cb), dtype=torch.float32, device=a.device)
-    if ws is None:
-        ws = L.workspace(upconv_grad_ws_bytes("wgrad", dt, B, H, W, Ca, Cb, Cout,
-                                              None if pool is None else pool.nnz_cap), a.device)
-    L.check(L.lib().shpl_upconv3x3_wgrad(dt, B, H, W, L.ptr(a), Ca, 0, Ca, L.ptr(b), Cb, 0, Cb,
-                                         None if pool is None else pool.ref(), L.ptr(frame_off), L.ptr(gy), Cout,
-                                         Cout, L.ptr(dw), L.ptr(ws), ws.numel(), L.stream_of(a.device)),
-            "shpl_upconv3x3_wgrad")
-    return dw
+    return _wgrad_call(_UPCONV, "shpl_upconv3x3_wgrad", a, gy, b, pool, frame_off, ws)
 
 
 class _FusionUpconvFn(torch.autograd.Function):
@@ -242,13 +180,7 @@ class _FusionUpconvFn(torch.autograd.Function):
         pooled = side is not None
         Ca = int(a.shape[-1])
         Cb = 0 if b is None else int(b.shape[-1])
-        gy = gy.contiguous().to(a.dtype)
-        if up.batch_norm or up.relu:
-            g_raw, dbeta, _ = batch_norm_backward(gy, y=y, raw=raw, mean=mean if up.batch_norm else None,
-                                                  scale=scale if up.batch_norm else None, relu=up.relu,
-                                                  training=ctx.train_bn, beta=beta)
-        else:
-            g_raw, dbeta = gy, None
+        g_raw, dbeta = _bn_relu_backward(up, ctx.train_bn, gy.contiguous().to(a.dtype), y, raw, mean, scale, beta)
         pool = smap.csr(*side.fwd) if pooled else None
         frame_off = smap.frame_off if pooled else None
         direct = up.backward == "direct"
@@ -269,9 +201,7 @@ class _FusionUpconvFn(torch.autograd.Function):
             else:
                 d_a, dx_b = dx
                 if ctx.needs_input_grad[1]:
-                    # the pooled channels' gradient back to the pooled source (_Side.grad), as FusionConv's
-                    d_b = torch.empty(b.shape, dtype=dx_b.dtype, device=dx_b.device)
-                    sm.pull(smap, *side.grad, dx_b, Cb, 0, Cb, d_b, Cb)
+                    d_b = _pull_back(smap, side, dx_b, b)
             if not ctx.needs_input_grad[0]:
                 d_a = None
         if ctx.needs_input_grad[2]:
@@ -282,17 +212,21 @@ class _FusionUpconvFn(torch.autograd.Function):
                 dw = upconv3x3_wgrad(a, g_raw, b=b, pool=pool, frame_off=frame_off, ws=ws).to(weights.dtype)
             else:
                 dw = phase_weight_grad(conv3x3_wgrad(a, g_ph, b=b, pool=pool, frame_off=frame_off)).to(weights.dtype)
-        d_beta = dbeta if (up.batch_norm and ctx.needs_input_grad[3]) else None
+        d_beta, _ = _beta_bias_grads(up, dbeta, ctx.needs_input_grad[3], False)
         return d_a, d_b, dw, d_beta, None, None, None, None, None
 
 
 class FusionUpconv(FusionConv):
     """slim.conv2d_transpose(x, c_out, [3,3], stride=2) with slim.batch_norm and ReLU: the variables of one
     ``upconv3`` scope and its forward. ``weights`` is slim's HWOI variable [3,3,c_out,c_in] (xavier-uniform);
-    beta, the moving statistics and the device-resident inference scale are kept as ``FusionConv`` keeps them."""
+    beta, the moving statistics and the device-resident inference scale are kept as ``FusionConv`` keeps them.
+    The entry points are ``FusionConv``'s, with upconv3 for the conv: ``__call__`` on a materialised fused map or
+    on plain conv4 (the image side of a non-dual layer), ``fused`` / ``fused_img`` (``smap`` at conv4's stride)
+    without writing the concat, ``fused_csr`` / ``fused_img_csr`` over an already built CSR, forward only."""
 
     DEFAULT_BACKWARD = "direct"
     BACKWARDS = ("direct", "phases")
+    _CALL, _WS_KEY = _UPCONV, ("up",)
 
     def __init__(self, c_in, c_out, batch_norm=True, relu=True, eps=1e-3, decay=0.999, dtype=torch.float32,
                  device="cuda", seed=0, backward=None):
@@ -304,69 +238,9 @@ class FusionUpconv(FusionConv):
         self.backward = backward
         super().__init__(c_in, c_out, batch_norm=batch_norm, bias=False, relu=relu, eps=eps, decay=decay,
                          dtype=dtype, device=device, seed=seed)
-        g = np.random.default_rng(seed)
-        # xavier_initializer (uniform) over the variable's shape [3,3,c_out,c_in]: fans 9*c_out and 9*c_in
-        lim = float(np.sqrt(6.0 / (9 * c_in + 9 * c_out)))
-        w = g.uniform(-lim, lim, size=(3, 3, c_out, c_in)).astype(np.float32)
-        self.weights = torch.from_numpy(w).to(self.device, dtype)
-
-    def _forward(self, a, b, pool, frame_off, is_training, out, keep=False):
-        """The forward; keep: also what the backward needs -- (y, raw, mean, scale)."""
-        B, H, W, Ca = (int(s) for s in a.shape)
-        Cb = 0 if b is None else int(b.shape[-1])
-        dt = L.dtype_code(a)
-        train_bn = self.batch_norm and is_training
-        cap = None if pool is None else pool.nnz_cap
-        ws = self._ws_for(("up", dt, B, H, W, Cb, cap, train_bn),
-                          upconv_ws_bytes(dt, B, H, W, Ca, Cb, self.c_out, cap, train_bn))
-        if not train_bn:
-            center, scale, shift = self._inference_epilogue()
-            if keep and scale is not None:  # saved for the backward: a copy, not the buffer a training step rewrites
-                scale = scale.clone()
-            y = upconv3x3(a, self.weights, b=b, pool=pool, frame_off=frame_off, center=center, scale=scale,
-                          shift=shift, relu=self.relu, out=out, ws=ws)
-            return (y, None, center, scale) if keep else y
-        stats = torch.empty((2, self.c_out), dtype=torch.float64, device=a.device)
-        raw = upconv3x3(a, self.weights, b=b, pool=pool, frame_off=frame_off, relu=False, stats=stats,
-                        out=None if keep else out, ws=ws)
-        bn_ws = torch.empty(2 * self.c_out, dtype=torch.float32, device=a.device)
-        y = (out if out is not None else torch.empty_like(raw)) if keep else None
-        y = batch_norm_train(raw, stats, B * 4 * H * W, eps=self.eps, beta=self.beta, relu=self.relu,
-                             moving_mean=self.moving_mean, moving_var=self.moving_var, decay=self.decay, out=y,
-                             ws=bn_ws)
-        self._refresh_scale()  # batch_norm_train updated the moving statistics through their device pointers
-        return (y, raw, bn_ws[:self.c_out], bn_ws[self.c_out:]) if keep else y
-
-    def _run(self, a, b, pool, frame_off, is_training, out):
-        return self._forward(a, b, pool, frame_off, is_training, out)
 
     def _apply(self, a, b, smap, side, is_training, out):
         return _FusionUpconvFn.apply(a, b, self.weights, self.beta, self, smap, side, is_training, out)
-
-    def __call__(self, x, is_training=False, out=None):
-        """upconv3 of a materialised fused map, or of plain conv4 (the image side of a non-dual layer)."""
-        if self._grad_wanted(x):
-            return self._apply(x, None, None, None, is_training, out)
-        return self._run(x, None, None, None, is_training, out)
-
-    def fused(self, bev, img, smap, is_training=False, out=None):
-        """upconv3 of [bev || _sparse_pool_op(M, img)] without writing the concat: ``smap`` is the ShplMap of the
-        frames of ``bev`` (at conv4's stride). Differentiable in bev, img, the weights and beta."""
-        if self._grad_wanted(bev, img):
-            return self._apply(bev, img, smap, SIDE_BEV, is_training, out)
-        return self.fused_csr(bev, img, smap.csr(*SIDE_BEV.fwd), smap.frame_off, is_training, out)
-
-    def fused_img(self, img, bev, smap, is_training=False, out=None):
-        """upconv3 of [img || _sparse_pool_trans_op(M, bev)] (the dual layer's image side) without writing the
-        concat. Differentiable in img, bev, the weights and beta."""
-        if int(bev.numel()) // max(int(bev.shape[-1]), 1) != smap.n_cells:
-            raise ValueError(f"BEV map {tuple(bev.shape)} has {int(bev.numel()) // max(int(bev.shape[-1]), 1)} rows, "
-                             f"the map {smap.n_cells} cells")
-        if self._grad_wanted(img, bev):
-            return self._apply(img, bev, smap, SIDE_IMG, is_training, out)
-        return self.fused_img_csr(img, bev, smap.csr(*SIDE_IMG.fwd), smap.frame_off, is_training, out)
-
-    # fused_csr / fused_img_csr: FusionConv's (forward only, over an already built CSR), through _run above
 
     def forward_phases(self, a, b=None, pool=None, frame_off=None, is_training=False):
         """The forward by the phase route: ``conv3x3`` with ``phase_weights`` to 4*c_out channels, then
@@ -390,7 +264,7 @@ class FusionUpconv(FusionConv):
                                 decay=self.decay)
 
 
-class AfterVggFusion:
+class AfterVggFusion(_TwoScopes):
     """Both ``upconv3`` scopes that follow the SHPL under rpn_sparse_pooling_after_vgg
     (fusion_vgg_pyramid.py:53-60, :198-206, one feature extractor per side): the BEV one over
     [conv4_bev || pool(conv4_img)], the image one over [conv4_img || trans(conv4_bev)] for a dual layer
@@ -398,31 +272,12 @@ class AfterVggFusion:
     image scope's input channels, as it fixes the graph in the reference."""
 
     def __init__(self, c_bev=256, c_img=256, c_out=128, dual=True, dtype=torch.float32, device="cuda", seed=0, **kw):
-        self.c_bev, self.c_img, self.dual = int(c_bev), int(c_img), bool(dual)
-        self.bev = FusionUpconv(c_bev + c_img, c_out, dtype=dtype, device=device, seed=seed, **kw)
-        self.img = FusionUpconv(c_img + (c_bev if dual else 0), c_out, dtype=dtype, device=device, seed=seed + 1,
-                                **kw)
-        self._side = None
+        super().__init__(c_bev, c_img, dual,
+                         FusionUpconv(c_bev + c_img, c_out, dtype=dtype, device=device, seed=seed, **kw),
+                         FusionUpconv(c_img + (c_bev if dual else 0), c_out, dtype=dtype, device=device,
+                                      seed=seed + 1, **kw))
 
     def __call__(self, conv4_bev, conv4_img, smap, is_training=False):
         """(upconv3_bev, upconv3_img): the BEV scope on the current stream, the image scope on the module's side
         stream, which the current stream then waits for (as ``PostFusion`` issues its two convs)."""
-        cur = torch.cuda.current_stream(conv4_bev.device)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=conv4_bev.device)
-        side = self._side
-        if self.dual:  # both CSRs on the current stream, before the fork: the map builds each once, stream-ordered
-            smap.csr(*SIDE_IMG.fwd)
-        smap.csr(*SIDE_BEV.fwd)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            if self.dual:
-                img_out = self.img.fused_img(conv4_img, conv4_bev, smap, is_training)
-            else:
-                img_out = self.img(conv4_img, is_training)
-        bev_out = self.bev.fused(conv4_bev, conv4_img, smap, is_training)
-        for t in (conv4_bev, conv4_img, self.img.weights):
-            t.record_stream(side)
-        cur.wait_stream(side)
-        img_out.record_stream(cur)
-        return bev_out, img_out
+        return super().__call__(conv4_bev, conv4_img, smap, is_training)

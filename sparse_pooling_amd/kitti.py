@@ -17,7 +17,6 @@ batch goes from raw scans to the fused SHPL layer without leaving the GPU
 """
 from __future__ import annotations
 
-import ctypes
 import os
 
 import numpy as np
@@ -135,10 +134,7 @@ def velo_to_cam_batch(xyzi, point_offsets, rect, P=None, im_size=None, min_inten
     if max_points_per_frame is None:
         max_points_per_frame = int((point_offsets[1:] - point_offsets[:-1]).max().item()) if F else 0
     if ws is None:
-        nb = ctypes.c_size_t()
-        L.check(L.lib().shpl_velo_workspace_bytes(F, int(max_points_per_frame), ctypes.byref(nb)),
-                "shpl_velo_workspace_bytes")
-        ws = L.workspace(nb.value, dev)
+        ws = L.workspace(L.ws_bytes("shpl_velo", F, max_points_per_frame), dev)
     pts = out if out is not None else torch.empty((max(N, 1), 3), dtype=torch.float64, device=dev)
     counts = torch.empty(F, dtype=torch.int64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)

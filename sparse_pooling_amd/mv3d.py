@@ -251,9 +251,7 @@ def mv3d_voxels_batch(points, point_offsets, img_index2=None, P=None, ranges=PED
     fn = torch.empty(F, dtype=torch.int64, device=dev)
     nb = torch.empty(cap, dtype=torch.int32, device=dev) if number_buffer else None
     nvox = torch.empty(F, dtype=torch.int64, device=dev) if number_buffer else None
-    nbytes = ctypes.c_size_t()
-    L.check(L.lib().shpl_mv3d_workspace_bytes(n_out, ctypes.byref(nbytes)), "shpl_mv3d_workspace_bytes")
-    ws = L.workspace(nbytes.value, dev)
+    ws = L.workspace(L.ws_bytes("shpl_mv3d", n_out), dev)
     rng = np.ascontiguousarray(ranges, dtype=np.float64)
     out = {"img_index": img, "bv_index": bv, "M_val": mv, "frame_n": fn, "number_buffer": nb, "frame_nvox": nvox}
     if vox_aug is None:

@@ -546,11 +546,7 @@ class FramePipeline(FusedPipeline):
                          dtype=dtype, device=device, dual=dual, live=True)
         self.bev_args = (area_extents, voxel_size, height_lo, height_hi, num_slices)
         self.maps = maps
-        import ctypes
-        nb = ctypes.c_size_t()
-        L.check(self._lib.shpl_bev_workspace_bytes(self.N, int(num_slices), ctypes.byref(nb)),
-                "shpl_bev_workspace_bytes")
-        self.bev_ws = L.workspace(nb.value, self.dev)
+        self.bev_ws = L.workspace(L.ws_bytes("shpl_bev", self.N, num_slices), self.dev)
         self.bev = None
         self._velo_ws = None
 
@@ -684,10 +680,6 @@ class FramePipeline(FusedPipeline):
 
     def _velo(self, frames):
         if self._velo_ws is None:
-            import ctypes
-            nb = ctypes.c_size_t()
-            L.check(self._lib.shpl_velo_workspace_bytes(frames.n_frames, frames.max_points, ctypes.byref(nb)),
-                    "shpl_velo_workspace_bytes")
-            self._velo_ws = L.workspace(nb.value, self.dev)
+            self._velo_ws = L.workspace(L.ws_bytes("shpl_velo", frames.n_frames, frames.max_points), self.dev)
             self._velo_pts = torch.empty((max(self.N, 1), 3), dtype=torch.float64, device=self.dev)
         self.velo = frames.point_clouds(ws=self._velo_ws, out=self._velo_pts)
