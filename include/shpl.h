@@ -42,7 +42,8 @@ typedef enum {
 } shpl_status;
 
 /* bits of the device error word */
-#define SHPL_EBIT_ROW 1u     /* M row (BEV cell) outside [0, M_size[0]) */
+#define SHPL_EBIT_ROW 1u     /* M row (BEV cell) outside [0, M_size[0]); shpl_bev_slices: a point's cell
+                                outside the voxel grid */
 #define SHPL_EBIT_COL 2u     /* M column outside [0, M_size[1]) */
 #define SHPL_EBIT_PIXEL 4u   /* source index (b,v,u) outside the image */
 #define SHPL_EBIT_VALUES 8u  /* len(M_val) != nnz */
@@ -169,7 +170,13 @@ int shpl_produce_index(int64_t nv, const void *d_bv_index, int bv_itype, int64_t
  *   d_height_maps   optional [n_frames, num_slices, nz, nx] f64 (rotated like the reference)
  *   d_density_map   optional [n_frames, nz, nx] f64
  * Slices are emitted in order and cells in (x, z) order, matching
- * np.vstack(voxel_indices_stack). Workspace: shpl_bev_workspace_bytes. */
+ * np.vstack(voxel_indices_stack). Workspace: shpl_bev_workspace_bytes.
+ * d_err (optional): SHPL_EBIT_ROW is set when a frame has more voxels than
+ * points, and also when a point inside the extents, in a slice or in the
+ * density range, floors to a cell outside the nx x nz grid (ext_max /
+ * voxel_size rounding to an integer, e.g. voxel_size 0.3: the reference raises
+ * ValueError there); that point is left out of every slice and of the density
+ * map. */
 int shpl_bev_workspace_bytes(int64_t total_points, int num_slices, size_t *bytes);
 int shpl_bev_slices(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
                     int64_t total_points,

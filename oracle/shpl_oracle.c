@@ -346,7 +346,11 @@ int shplo_pool_trans_grad_bev(const float *dZ, int64_t B, int64_t H, int64_t W, 
  * through OpenBLAS dgemv whose accumulation order is not reproduced here
  * (an FMA chain is used): results can differ only for points within one ulp
  * of a slice plane. Slices with <= 1 point are voxelized too (the reference
- * reuses the previous slice's grid there, bev_slices.py:79-93, a bug). */
+ * reuses the previous slice's grid there, bev_slices.py:79-93, a bug).
+ * A point inside the extents whose cell lies outside the grid (possible when
+ * ext_max / vs rounds to an integer, e.g. vs = 0.3) makes the reference raise
+ * ValueError("Extents are smaller than max_voxel_coord") (voxel_grid_2d.py:
+ * 135-140): nothing is written for it and -2 is returned. */
 typedef struct { int32_t x, y, z; int64_t i; } shplo_vox;
 
 static int cmp_vox(const void *pa, const void *pb)
@@ -369,7 +373,8 @@ static int plane_below(const double *pl, double off, double x, double y, double 
 
 /* pts n x 3; ext [3][2]; outputs: vox (cap x 2: x, nz - z), upts (cap x 3),
  * hmaps [num_slices][nz][nx] (zero-filled here), dmap [nz][nx]; returns the
- * number of voxel rows (all slices) or -1 if cap is too small. */
+ * number of voxel rows (all slices), -1 if cap is too small, or -2 if a point
+ * of a slice or of the density range falls in a cell outside the grid. */
 int64_t shplo_bev_slices(int64_t n, const double *pts, const double *plane, const double *ext, double vs,
                          int num_slices, const double *lo, const double *hi, double dlo, double dhi,
                          double hpd, const double *dens_table, int64_t cap, int64_t *vox, double *upts,
@@ -393,6 +398,10 @@ int64_t shplo_bev_slices(int64_t n, const double *pts, const double *plane, cons
             buf[m].y = (int32_t)floor(y / vs);
             buf[m].z = (int32_t)floor(z / vs);
             buf[m].i = i;
+            if (buf[m].x < min_x || buf[m].x - min_x >= nx || buf[m].z < min_z || buf[m].z - min_z >= nz) {
+                free(buf);
+                return -2;
+            }
             ++m;
         }
         qsort(buf, (size_t)m, sizeof(shplo_vox), cmp_vox);

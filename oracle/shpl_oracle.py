@@ -130,7 +130,8 @@ def density_table(norm_value=np.log(16)):
 
 def bev_slices(point_cloud, ground_plane, area_extents, voxel_size, height_lo, height_hi, num_slices):
     """Restates BevSlices.generate_bev(output_indices=True): returns
-    (height_maps [S,nz,nx], density_map [nz,nx], voxel_indices [M,2], pts_in_voxel [M,3])."""
+    (height_maps [S,nz,nx], density_map [nz,nx], voxel_indices [M,2], pts_in_voxel [M,3]).
+    Raises ValueError, as the reference does, when a point inside the extents floors to a cell outside the grid."""
     pts = _c(np.asarray(point_cloud).T, np.float64)
     ext = _c(area_extents, np.float64).reshape(3, 2)
     n = pts.shape[0]
@@ -147,6 +148,10 @@ def bev_slices(point_cloud, ground_plane, area_extents, voxel_size, height_lo, h
                                num_slices, _p(_c(lo, np.float64)), _p(_c(hi, np.float64)), float(height_lo),
                                float(height_hi), float(hpd), _p(_c(density_table(), np.float64)), cap,
                                _p(vox), _p(upts), _p(hm), _p(dm))
+    if m == -2:  # voxel_grid_2d.py:138-140
+        raise ValueError("Extents are smaller than max_voxel_coord")
+    if m < 0:
+        raise OracleError("voxel capacity too small")
     return hm, dm, vox[:m].copy(), upts[:m].copy()
 
 

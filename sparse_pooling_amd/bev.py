@@ -144,7 +144,9 @@ class BevSlices:
     def generate_bev(self, source, point_cloud, ground_plane, area_extents, voxel_size, output_indices=False):
         """point_cloud (3, N) camera frame. Returns {'height_maps': [S x (nz, nx)], 'density_map': (nz, nx)}
         (device f64 tensors, rotated like the reference) and, with output_indices,
-        also voxel_indices [M,2] and pts_in_voxel [M,3]."""
+        also voxel_indices [M,2] and pts_in_voxel [M,3] -- or, like the reference, ValueError when a point inside
+        the extents floors to a cell outside the grid (the device drops the point and sets EBIT_ROW, read here
+        together with the voxel count; bev_slices_batch hands the word back in BevBatch.err unread)."""
         dev = torch.device("cuda", torch.cuda.current_device())
         pc = point_cloud if isinstance(point_cloud, torch.Tensor) else torch.as_tensor(np.asarray(point_cloud))
         pts = pc.to(device=dev, dtype=torch.float64).t().contiguous()
@@ -156,5 +158,7 @@ class BevSlices:
                     'density_map': b.density_map[0]}
         if not output_indices:
             return bev_maps
-        m = int(b.frame_nvox[0].item())
+        m, err = (int(v) for v in torch.cat((b.frame_nvox[:1], b.err.to(torch.int64))).tolist())
+        if err & L.EBIT_ROW:  # voxel_grid_2d.py:138-140
+            raise ValueError("Extents are smaller than max_voxel_coord")
         return bev_maps, b.voxel_indices[:m].to(torch.int64), b.pts_in_voxel[:m]

@@ -26,6 +26,12 @@
 // the words; the first word of each key run is the cell's point and the run
 // length its count. Outputs keep the reference's order: slice-major, then
 // (x, z) ascending, exactly np.vstack(voxel_indices_stack).
+//
+// A point strictly inside the extents can still floor to a cell one past the
+// grid when ext_max / voxel_size rounds to an integer (0.3, 0.15, 0.12, ...:
+// floor(nextafter(0.9, 0) / 0.3) = 3 on a grid of 3 columns). The reference
+// raises ValueError there; here such a point forms no key in any slice or in
+// the density range and sets SHPL_EBIT_ROW in the error word.
 #include "shpl_tilesort.h"
 
 namespace shpl {
@@ -67,10 +73,11 @@ struct Pt {
     }
 };
 
-// Entries of one point: calls emit(word) for each slice it is in and for the density range.
+// Entries of one point: calls emit(word) for each slice it is in and for the density range. A point whose
+// cell lies outside the grid emits nothing (every key stays below n_keys) and sets SHPL_EBIT_ROW instead.
 template <typename PT, typename F>
 __device__ __forceinline__ void point_entries(const BevGeom &g, const double *plane, const void *pts, int64_t i,
-                                              uint32_t li, int64_t n_cells, F &&emit) {
+                                              uint32_t li, int64_t n_cells, uint32_t *err, F &&emit) {
     double x, y, z;
     Pt<PT>::load(pts, i, x, y, z);
     const bool inside = x > g.ext[0][0] && x < g.ext[0][1] && y > g.ext[1][0] && y < g.ext[1][1] &&
@@ -80,12 +87,18 @@ __device__ __forceinline__ void point_entries(const BevGeom &g, const double *pl
     const int xd = (int)floor(__ddiv_rn(x, g.vs));
     const int yd = (int)floor(__ddiv_rn(y, g.vs));
     const int zd = (int)floor(__ddiv_rn(z, g.vs));
-    const int64_t cell = (int64_t)(xd - g.min_x) * g.nz + (zd - g.min_z);
+    const int xi = xd - g.min_x, zi = zd - g.min_z;
+    const bool in_grid = (uint32_t)xi < (uint32_t)g.nx && (uint32_t)zi < (uint32_t)g.nz;
+    const int64_t cell = (int64_t)xi * g.nz + zi;
     const uint64_t low = ((uint64_t)(uint32_t)(yd - g.min_y) << 32) | li;
     for (int s = 0; s <= g.num_slices; ++s) {
         // create_slice_filter: xor(filter(hi), filter(lo)), both inside the extents
-        if (below(plane, g.hi[s], x, y, z) != below(plane, g.lo[s], x, y, z))
-            emit(((uint64_t)(s * n_cells + cell) << KEY_SHIFT) | low);
+        if (below(plane, g.hi[s], x, y, z) != below(plane, g.lo[s], x, y, z)) {
+            if (in_grid)
+                emit(((uint64_t)(s * n_cells + cell) << KEY_SHIFT) | low);
+            else if (err)
+                atomicOr(err, SHPL_EBIT_ROW);
+        }
     }
 }
 
@@ -111,7 +124,7 @@ __global__ __launch_bounds__(BEV_BLOCK) void k_bev_frame(BevGeom g, const int64_
         lds, n_tiles, tmp + t0, srt + t0,
         [&](auto &&emit) {
             for (int64_t i = p0 + threadIdx.x; i < p1; i += BEV_BLOCK)
-                point_entries<PT>(g, plane, pts, i, (uint32_t)(i - p0), n_cells, emit);
+                point_entries<PT>(g, plane, pts, i, (uint32_t)(i - p0), n_cells, err, emit);
         },
         [&](uint64_t w) { return (int)((w >> KEY_SHIFT) >> g.log_tile); });
     int32_t *wsum = lds.wsum;

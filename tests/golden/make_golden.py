@@ -151,6 +151,51 @@ def _bev_slices_case():
     print(f"bev_slices: N={n} voxel_indices={vox.shape} maps={np.stack(maps['height_maps']).shape}")
 
 
+def _bev_edges_case():
+    """BevSlices.generate_bev(output_indices=True) on the planted edge cases of tests/bev_cases.py (its GOLDEN
+    list): inputs and the four outputs under "<case>/<name>". On the `overflow` case the reference raises
+    (a point inside the extents floors to a cell past the grid): the exception's type and message are recorded
+    instead of outputs."""
+    from avod.core.bev_generators.bev_slices import BevSlices
+    from wavedata.tools.obj_detection import obj_utils
+    sys.path.insert(0, os.path.dirname(HERE))
+    import bev_cases as bc
+
+    class _Utils:  # KittiUtils.create_slice_filter, as in _bev_slices_case
+        @staticmethod
+        def create_slice_filter(pc, ext, gp, lo, hi):
+            return np.logical_xor(obj_utils.get_point_filter(pc, ext, gp, hi),
+                                  obj_utils.get_point_filter(pc, ext, gp, lo))
+
+    def run(name):
+        pts, gp, area, vs, hlo, hhi, S = bc.case(name)
+        rec = {f"{name}/point_cloud": pts, f"{name}/ground_plane": gp, f"{name}/area_extents": area,
+               f"{name}/voxel_size": np.array(vs), f"{name}/height_lo": np.array(hlo),
+               f"{name}/height_hi": np.array(hhi), f"{name}/num_slices": np.array(S)}
+        bev = BevSlices(types.SimpleNamespace(height_lo=hlo, height_hi=hhi, num_slices=S), _Utils())
+        return rec, lambda: bev.generate_bev("lidar", pts.copy(), gp.copy(), area.copy(), vs, output_indices=True)
+
+    out = {}
+    for name in bc.GOLDEN:
+        rec, gen = run(name)
+        maps, vox, upts = gen()
+        rec.update({f"{name}/voxel_indices": vox, f"{name}/pts_in_voxel": upts,
+                    f"{name}/height_maps": np.stack(maps["height_maps"]), f"{name}/density_map": maps["density_map"]})
+        out.update(rec)
+        print(f"bev_edges {name}: N={rec[f'{name}/point_cloud'].shape[1]} voxel_indices={vox.shape}")
+    rec, gen = run("overflow")
+    try:
+        gen()
+        raise RuntimeError("the reference did not raise on the overflow case")
+    except ValueError as ex:
+        rec.update({"overflow/raised": np.array(type(ex).__name__), "overflow/message": np.array(str(ex))})
+        print("bev_edges overflow: reference raised", type(ex).__name__, ex)
+    out.update(rec)
+    path = os.path.join(HERE, "bev_edges.npz")
+    np.savez_compressed(path, **out)
+    print(f"bev_edges: {os.path.getsize(path)} bytes")
+
+
 def _mv3d_voxel_case(dense=False):
     """MV3D point_cloud_2_top_sparse: img_index, bv_index and M_val = 1/count.
     dense: clustered points so that many voxels exceed VOXEL_POINT_COUNT (45)."""
@@ -370,6 +415,7 @@ def main():
         print("empty frame: reference raised", type(ex).__name__, ex)
     _single_case()
     _bev_slices_case()
+    _bev_edges_case()
     _mv3d_voxel_case()
     _mv3d_voxel_case(dense=True)
     _kitti_case()

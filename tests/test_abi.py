@@ -176,6 +176,29 @@ def test_argument_validation_is_host_side():
     for ns in (0, 9):
         assert lib.shpl_bev_slices(1, P, N, 10, P, L.F64, P, ext, 0.1, ns, lo, lo, 0., 1., 0.5, tab, P, P, P, N, N,
                                    N, P, 1 << 20, N) in (L.ERR_BAD_SHAPE, L.ERR_ARG)
+    # bev_geom's refusals, each before any device work: voxel size, key field (2^22), discrete-y field (1024)
+    def bev(vs=0.1, e=ext, ws=1 << 20):
+        return lib.shpl_bev_slices(1, P, N, 10, P, L.F64, P, e, vs, 5, lo, lo, 0., 1., 0.5, tab, P, P, P, N, N, N, P,
+                                   ws, N)
+    assert bev(vs=0.0) == L.ERR_BAD_SHAPE and bev(vs=math.nan) == L.ERR_BAD_SHAPE and bev(vs=-0.1) == L.ERR_BAD_SHAPE
+    assert bev(vs=0.05) == L.ERR_BAD_SHAPE  # 1600 x 1400 x 6 keys >= 2^22
+    assert bev(e=(ctypes.c_double * 6)(-52, 52, -5, 3, 0, 70)) == L.ERR_BAD_SHAPE  # 1040 x 700 x 6: just over 2^22
+    assert bev(e=(ctypes.c_double * 6)(-2, 2, -60, 45, 0, 4)) == L.ERR_BAD_SHAPE  # 1051 discrete y, the field: 1024
+    need = ctypes.c_size_t()
+    assert lib.shpl_bev_workspace_bytes(10, 5, ctypes.byref(need)) == L.OK and need.value > 2 * 10 * 6 * 8
+    assert bev(ws=need.value - 1) == L.ERR_WORKSPACE
+    # the deferred maps / network input: the frame table holds 4096 frames; the input tensor is required
+    for nf, want in ((4097, L.ERR_BAD_SHAPE), (0, L.ERR_ARG)):
+        assert lib.shpl_bev_maps(nf, P, 10, P, L.F64, P, ext, 0.1, 5, lo, lo, 0., 1., 0.5, tab, P, P, 1, P, 1 << 20,
+                                 N) == want
+        assert lib.shpl_bev_input(nf, P, 10, P, L.F64, P, ext, 0.1, 5, lo, lo, 0., 1., 0.5, tab, P, P, 1 << 20,
+                                  N) == want
+    assert lib.shpl_bev_input(1, P, 10, P, L.F64, P, ext, 0.1, 5, lo, lo, 0., 1., 0.5, tab, N, P, 1 << 20,
+                              N) == L.ERR_ARG
+    assert lib.shpl_bev_maps(1, P, 10, P, L.F64, P, ext, 0.1, 5, lo, lo, 0., 1., 0.5, tab, P, P, 1, P, need.value - 1,
+                             N) == L.ERR_WORKSPACE
+    assert lib.shpl_bev_input(1, P, 10, P, L.F64, P, ext, 0.05, 5, lo, lo, 0., 1., 0.5, tab, P, P, 1 << 20,
+                              N) == L.ERR_BAD_SHAPE
     rng = (ctypes.c_double * 6)(0, 48, -20, 20, -1, 3)
     assert lib.shpl_mv3d_voxels(1, P, 10, P, 4, N, N, N, rng, 0.2, 0.4, 45, P, 10, P, P, P, N, N, P, 1 << 20,
                                 N) == L.ERR_ARG
