@@ -21,7 +21,7 @@ SHORT = (("k_conv_wide", "k_conv_wide"), ("k_pool_runs_wide", "k_pool_runs_wide"
          ("k_conv3x3<float, true", "k_conv3x3_pooled_f32"), ("k_conv3x3<float, false", "k_conv3x3_dense_f32"),
          ("k_conv3x3<unsigned short, true", "k_conv3x3_pooled_bf16"),
          ("k_conv3x3<unsigned short, false", "k_conv3x3_dense_bf16"),
-         ("k_dense", "k_dense"), ("k_clear", "k_clear"), ("k_sparse_long", "k_sparse_long"), ("k_sparse", "k_sparse"), ("k_csr_frame", "k_csr_frame"), ("k_compact", "k_compact"),
+         ("k_copy_rows", "k_copy_rows"), ("k_dense", "k_dense"), ("k_clear", "k_clear"), ("k_sparse_long", "k_sparse_long"), ("k_sparse", "k_sparse"), ("k_csr_frame", "k_csr_frame"), ("k_compact", "k_compact"),
          ("k_count", "k_count"))
 
 
@@ -114,7 +114,7 @@ def main(key):
     print(json.dumps(tj[key], indent=1))
 
 
-LAYER = ("k_dense", "k_clear", "k_sparse", "k_sparse_long", "k_rows", "k_bpull", "k_once")
+LAYER = ("k_dense", "k_copy_rows", "k_clear", "k_sparse", "k_sparse_long", "k_rows", "k_bpull", "k_once")
 
 
 def step_traffic(key, tag, layer_kernels=LAYER, anchor="k_count", skip_after=None):

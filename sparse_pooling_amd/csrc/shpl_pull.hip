@@ -24,7 +24,8 @@
 // Work unit: one 16-byte chunk (4 f32 / 8 bf16); a 64-lane wave stores 1 KiB
 // contiguous. k_dense is a full grid, one chunk per thread (no grid-stride
 // loop): the fastest streaming shape measured on MI355X for this traffic
-// (read 1 : write 2) -- see DESIGN.md.
+// (read 1 : write 2) -- see DESIGN.md. A concat without pooled channels is a
+// plain row copy (read 1 : write 1) and takes k_copy_rows, shaped for that.
 #include <algorithm>
 #include <type_traits>
 
@@ -135,6 +136,32 @@ __global__ __launch_bounds__(SHPL_BLOCK) void k_dense(const Feat f, uint32_t row
         v = C::zero();
     }
     C::store_nt(reinterpret_cast<T *>(f.out) + ((uint64_t)row * (uint32_t)f.out_stride + ch * VEC), v);
+}
+
+// ---------------------------------------------------------------- k_copy_rows
+// k_dense's pass-through copy alone (CONCAT without pooled channels: the kept-zeros step's copy, config 6's
+// split copy, the bucketless pass copies): chunk ch of row r goes from pass + r * pass_stride to
+// out + r * out_stride, one chunk per thread, non-temporal both ways -- bitwise k_dense's output. Its launch
+// shape is the one measured fastest for a 1 : 1 stream (scripts/calib_copy_rows.py, docs/HISTORY.md §21):
+// * workgroup ids are remapped so that each of the 8 XCDs, which take a launch's workgroups round-robin by
+//   id, walks one contiguous eighth of the chunks in order (k_once's order; the grid is a multiple of 8);
+// * at most 6 waves per SIMD.
+// 36 bytes of kernarg: the pointers come with pass_off and the launch's first row applied.
+// CONT: pass rows are contiguous (pass_stride == the row's width), so chunk g sits at pass + g * VEC.
+constexpr int COPY_WAVES = 6;
+template <typename T, int VEC, bool POW2, bool CONT>
+__global__ __launch_bounds__(SHPL_BLOCK) __attribute__((amdgpu_waves_per_eu(COPY_WAVES, COPY_WAVES)))
+void k_copy_rows(const T *__restrict__ pass, T *__restrict__ out, uint32_t n, uint32_t cpr, int cpr_shift,
+                 uint32_t pass_stride, uint32_t out_stride) {
+    typedef Chunk<T, VEC> C;
+    const uint32_t b = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const uint32_t g = b * SHPL_BLOCK + threadIdx.x;  // n <= 2^31 and at most 7 workgroups past it: 32 bits
+    if (g >= n) return;
+    const uint32_t r = POW2 ? g >> cpr_shift : g / cpr;
+    const uint32_t ch = g - r * cpr;
+    // row < 2^31 and row widths < 2^31 (plan() checks): 32 x 32 -> 64-bit offsets
+    const uint64_t pass_at = CONT ? (uint64_t)g * VEC : (uint64_t)r * pass_stride + ch * VEC;
+    C::store_nt(out + ((uint64_t)r * out_stride + ch * VEC), C::load_nt(pass + pass_at));
 }
 
 // ---------------------------------------------------------------- k_sparse
@@ -947,6 +974,20 @@ int dense(const Plan &pl, hipStream_t s) {
         const int64_t blocks = (nr * pl.f.cpr + SHPL_BLOCK - 1) / SHPL_BLOCK;
         by_elems(pl.dtype, pl.v16, [&](auto el) {
             typedef decltype(el) E;
+            if (pl.f.mode == SHPL_OUT_CONCAT && pl.f.cpool == 0) {
+                // the pass-through copy alone: k_copy_rows over this launch's rows, a grid of whole eighths
+                typedef typename E::T T;
+                const T *pass = reinterpret_cast<const T *>(pl.f.pass) + pl.f.pass_off + r0 * pl.f.pass_stride;
+                T *out = reinterpret_cast<T *>(pl.f.out) + r0 * pl.f.out_stride;
+                const bool cont = pl.f.pass_stride == (int64_t)pl.f.cpr * E::VEC;
+                by_bools([&](auto POW2, auto CONT) {
+                    hipLaunchKernelGGL((k_copy_rows<T, E::VEC, POW2.value, CONT.value>),
+                                       dim3((unsigned)((blocks + 7) & ~(int64_t)7)), dim3(SHPL_BLOCK), 0, s, pass, out,
+                                       (uint32_t)(nr * pl.f.cpr), pl.f.cpr, pl.f.cpr_shift, (uint32_t)pl.f.pass_stride,
+                                       (uint32_t)pl.f.out_stride);
+                }, pl.f.cpr_shift >= 0, cont);
+                return;
+            }
             by_bools([&](auto POW2) {
                 hipLaunchKernelGGL((k_dense<typename E::T, E::VEC, POW2.value>), dim3((unsigned)blocks),
                                    dim3(SHPL_BLOCK), 0, s, pl.f, (uint32_t)r0, (uint32_t)nr);
