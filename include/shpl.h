@@ -176,7 +176,9 @@ int shpl_produce_index(int64_t nv, const void *d_bv_index, int bv_itype, int64_t
  * density range, floors to a cell outside the nx x nz grid (ext_max /
  * voxel_size rounding to an integer, e.g. voxel_size 0.3: the reference raises
  * ValueError there); that point is left out of every slice and of the density
- * map. */
+ * map. A points_dtype other than SHPL_F64 is SHPL_ERR_ARG, answered behind the
+ * other argument checks and before anything is written: a refused call leaves
+ * the maps as they were. */
 int shpl_bev_workspace_bytes(int64_t total_points, int num_slices, size_t *bytes);
 int shpl_bev_slices(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
                     int64_t total_points,

@@ -14,6 +14,8 @@ is voxelized from its own points.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -48,7 +50,16 @@ class BevBatch:
     def __init__(self, voxel_indices, pts_in_voxel, frame_nvox, height_maps, density_map, err, call=None):
         self.voxel_indices, self.pts_in_voxel, self.frame_nvox = voxel_indices, pts_in_voxel, frame_nvox
         self.height_maps, self.density_map, self.err = height_maps, density_map, err
-        self._call = call  # the voxelizer call's arguments, for write_maps
+        self._call = call  # the voxelizer call's arguments (bev_slices_batch), for write_maps
+
+    def _run(self, symbol, counts, *outputs):
+        """symbol(frames, *counts, the shared arguments, *outputs, workspace, its bytes, the current stream)."""
+        c = self._call
+        L.check(getattr(L.lib(), symbol)(*c.frames, *counts, *c.shared, *outputs, L.ptr(c.ws), c.ws.numel(),
+                                         L.stream_of(c.dev)), symbol)
+
+    def _fits(self, t, dtype, shape):
+        return t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == self._call.dev
 
     def write_maps(self, height_maps, density_map, zero=True):
         """The height / density maps of this batch (shpl_bev_maps) into the given [F,S,nz,nx] /
@@ -56,17 +67,11 @@ class BevBatch:
         workspace (the workspace must not be reused in between): bitwise the maps bev_slices_batch
         writes with maps=True."""
         c = self._call
-        nx, nz = grid_divisions(c["ext"].reshape(3, 2), c["vs"])
-        for t, shape in ((height_maps, (c["F"], c["S"], nz, nx)), (density_map, (c["F"], nz, nx))):
-            if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape
-                                  or t.device != c["pts"].device):
-                raise ValueError(f"map tensors must be contiguous f64 {shape} on {c['pts'].device}, "
+        for t, shape in ((height_maps, (c.F, c.S, c.nz, c.nx)), (density_map, (c.F, c.nz, c.nx))):
+            if t is not None and not self._fits(t, torch.float64, shape):
+                raise ValueError(f"map tensors must be contiguous f64 {shape} on {c.dev}, "
                                  f"got {tuple(t.shape)} {t.dtype}")
-        L.check(L.lib().shpl_bev_maps(c["F"], L.ptr(c["off"]), c["N"], L.ptr(c["pts"]), L.F64, L.ptr(c["planes"]),
-                                      c["p"](c["ext"]), c["vs"], c["S"], c["p"](c["lo"]), c["p"](c["hi"]), c["hlo"],
-                                      c["hhi"], c["hpd"], c["p"](c["table"]), L.ptr(height_maps),
-                                      L.ptr(density_map), int(bool(zero)), L.ptr(c["ws"]), c["ws"].numel(),
-                                      L.stream_of(c["pts"].device)), "shpl_bev_maps")
+        self._run("shpl_bev_maps", (), L.ptr(height_maps), L.ptr(density_map), int(bool(zero)))
         self.height_maps, self.density_map = height_maps, density_map
         return height_maps, density_map
 
@@ -75,16 +80,11 @@ class BevBatch:
         np.dstack((*height_maps, density_map)) (kitti_dataset.py:368) as the tf.float32 placeholder holds it
         (each map value rounded to f32 once), from the voxelizer's sorted words like write_maps."""
         c = self._call
-        nx, nz = grid_divisions(c["ext"].reshape(3, 2), c["vs"])
-        shape = (c["F"], nz, nx, c["S"] + 1)
-        if (bev_input.dtype != torch.float32 or not bev_input.is_contiguous() or tuple(bev_input.shape) != shape
-                or bev_input.device != c["pts"].device):
-            raise ValueError(f"bev_input must be a contiguous f32 {shape} tensor on {c['pts'].device}, "
+        shape = (c.F, c.nz, c.nx, c.S + 1)
+        if not self._fits(bev_input, torch.float32, shape):
+            raise ValueError(f"bev_input must be a contiguous f32 {shape} tensor on {c.dev}, "
                              f"got {tuple(bev_input.shape)} {bev_input.dtype}")
-        L.check(L.lib().shpl_bev_input(c["F"], L.ptr(c["off"]), c["N"], L.ptr(c["pts"]), L.F64, L.ptr(c["planes"]),
-                                       c["p"](c["ext"]), c["vs"], c["S"], c["p"](c["lo"]), c["p"](c["hi"]), c["hlo"],
-                                       c["hhi"], c["hpd"], c["p"](c["table"]), L.ptr(bev_input), L.ptr(c["ws"]),
-                                       c["ws"].numel(), L.stream_of(c["pts"].device)), "shpl_bev_input")
+        self._run("shpl_bev_input", (), L.ptr(bev_input))
         self.bev_input = bev_input
         return bev_input
 
@@ -118,15 +118,16 @@ def bev_slices_batch(points, point_offsets, planes, area_extents, voxel_size, he
     if ws is None:
         ws = L.workspace(L.ws_bytes("shpl_bev", N, num_slices), dev)
     p = lambda a: a.ctypes.data_as(L.ctypes.c_void_p)  # noqa: E731
-    L.check(L.lib().shpl_bev_slices(F, L.ptr(point_offsets), L.ptr(point_counts), N, L.ptr(points), L.F64, L.ptr(planes), p(ext),
-                                    float(voxel_size), int(num_slices), p(lo_a), p(hi_a), float(height_lo),
-                                    float(height_hi), float(hpd), p(table), L.ptr(vox), L.ptr(upts), L.ptr(nvox),
-                                    L.ptr(hm), L.ptr(dm), L.ptr(err), L.ptr(ws), ws.numel(),
-                                    L.stream_of(dev)), "shpl_bev_slices")
-    call = dict(F=F, off=point_offsets, N=N, pts=points, planes=planes, p=p, ext=ext, vs=float(voxel_size),
-                S=int(num_slices), lo=lo_a, hi=hi_a, hlo=float(height_lo), hhi=float(height_hi), hpd=float(hpd),
-                table=table, ws=ws)
-    return BevBatch(vox, upts, nvox, hm, dm, err, call)
+    # the call, kept for the calls that read its sorted words back: the C arguments all three share in front of their
+    # own (frames, then shared), the workspace, the maps' sizes, the device, and what the pointers point into
+    shared = (N, L.ptr(points), L.F64, L.ptr(planes), p(ext), float(voxel_size), int(num_slices), p(lo_a), p(hi_a),
+              float(height_lo), float(height_hi), float(hpd), p(table))
+    b = BevBatch(vox, upts, nvox, hm, dm, err, SimpleNamespace(
+        frames=(F, L.ptr(point_offsets)), shared=shared, ws=ws, F=F, S=int(num_slices), nz=nz, nx=nx, dev=dev,
+        alive=(point_offsets, points, planes, ext, lo_a, hi_a, table)))
+    b._run("shpl_bev_slices", (L.ptr(point_counts),), L.ptr(vox), L.ptr(upts), L.ptr(nvox), L.ptr(hm), L.ptr(dm),
+           L.ptr(err))
+    return b
 
 
 class BevSlices:

@@ -38,7 +38,6 @@ namespace shpl {
 namespace {
 
 constexpr int BEV_BLOCK = TS_BLOCK;
-constexpr int BEV_TILES = TS_TILES;
 constexpr int BEV_MAX_SLICES = 8;
 constexpr int KEY_SHIFT = 42;  // [63:42] key, [41:32] discrete y - y0, [31:0] point index in frame
 
@@ -63,23 +62,19 @@ __device__ __forceinline__ bool below(const double *pl, double off, double x, do
     return s < 0.0;
 }
 
-template <typename PT>
-struct Pt {
-    static __device__ __forceinline__ void load(const void *p, int64_t i, double &x, double &y, double &z) {
-        const PT *q = reinterpret_cast<const PT *>(p) + 3 * i;
-        x = (double)q[0];
-        y = (double)q[1];
-        z = (double)q[2];
-    }
-};
+__device__ __forceinline__ void load_point(const double *pts, int64_t i, double &x, double &y, double &z) {
+    x = pts[3 * i];
+    y = pts[3 * i + 1];
+    z = pts[3 * i + 2];
+}
 
 // Entries of one point: calls emit(word) for each slice it is in and for the density range. A point whose
 // cell lies outside the grid emits nothing (every key stays below n_keys) and sets SHPL_EBIT_ROW instead.
-template <typename PT, typename F>
-__device__ __forceinline__ void point_entries(const BevGeom &g, const double *plane, const void *pts, int64_t i,
+template <typename F>
+__device__ __forceinline__ void point_entries(const BevGeom &g, const double *plane, const double *pts, int64_t i,
                                               uint32_t li, int64_t n_cells, uint32_t *err, F &&emit) {
     double x, y, z;
-    Pt<PT>::load(pts, i, x, y, z);
+    load_point(pts, i, x, y, z);
     const bool inside = x > g.ext[0][0] && x < g.ext[0][1] && y > g.ext[1][0] && y < g.ext[1][1] &&
                         z > g.ext[2][0] && z < g.ext[2][1];
     if (!inside) return;
@@ -102,13 +97,37 @@ __device__ __forceinline__ void point_entries(const BevGeom &g, const double *pl
     }
 }
 
-template <typename PT>
+// What k_bev_frame's step 5 and k_bev_maps both make of a key run's first word. Its key's range v (slice, or
+// num_slices = density), its cell (xi, zi) and its element pix in a map of the frame:
+__device__ __forceinline__ void decode_key(const BevGeom &g, int64_t n_cells, uint64_t key, int &v, int &xi, int &zi,
+                                           int64_t &pix) {
+    v = (int)((int64_t)key / n_cells);
+    const int64_t cell = (int64_t)key - (int64_t)v * n_cells;
+    xi = (int)(cell / g.nz);
+    zi = (int)(cell - (int64_t)xi * g.nz);
+    pix = (int64_t)(g.nz - 1 - zi) * g.nx + xi;  // np.flip(map.T, axis=0)
+}
+
+// A point's height in slice v as the height map holds it: dist_to_plane over the frame's plane, above lo[v],
+// in divisions.
+__device__ __forceinline__ double slice_height(const BevGeom &g, const double *plane, int v, double x, double y,
+                                               double z) {
+    const double a = plane[0], b = plane[1], c = plane[2], d = plane[3];
+    const double norm = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)), __dmul_rn(c, c)));
+    // dist_to_plane: (a*x + b*y + c*z + d) / sqrt(a^2 + b^2 + c^2)
+    const double dist =
+        __ddiv_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(a, x), __dmul_rn(b, y)), __dmul_rn(c, z)), d), norm);
+    return __ddiv_rn(__dsub_rn(dist, g.lo[v]), g.hpd);
+}
+
+// The density map's value for a cell of n points.
+__device__ __forceinline__ double density(const BevGeom &g, int32_t n) { return n < 16 ? g.dens[n] : 1.0; }
+
 __global__ __launch_bounds__(BEV_BLOCK) void k_bev_frame(BevGeom g, const int64_t *pt_off, const int64_t *pt_count,
-                                                         const void *pts,
-                                                         const double *planes, uint64_t *tmp, uint64_t *srt,
-                                                         int64_t ent_per_point, int32_t *vox_out, double *pts_out,
-                                                         int64_t *frame_nvox, double *hmaps, double *dmap,
-                                                         int32_t *frame_nent, uint32_t *err) {
+                                                         const double *pts, const double *planes, uint64_t *tmp,
+                                                         uint64_t *srt, int64_t ent_per_point, int32_t *vox_out,
+                                                         double *pts_out, int64_t *frame_nvox, double *hmaps,
+                                                         double *dmap, int32_t *frame_nent, uint32_t *err) {
     __shared__ TileSortLds lds;
     const int f = blockIdx.x;
     const int64_t p0 = pt_off[f], cap_end = pt_off[f + 1];
@@ -124,68 +143,41 @@ __global__ __launch_bounds__(BEV_BLOCK) void k_bev_frame(BevGeom g, const int64_
         lds, n_tiles, tmp + t0, srt + t0,
         [&](auto &&emit) {
             for (int64_t i = p0 + threadIdx.x; i < p1; i += BEV_BLOCK)
-                point_entries<PT>(g, plane, pts, i, (uint32_t)(i - p0), n_cells, err, emit);
+                point_entries(g, plane, pts, i, (uint32_t)(i - p0), n_cells, err, emit);
         },
         [&](uint64_t w) { return (int)((w >> KEY_SHIFT) >> g.log_tile); });
-    int32_t *wsum = lds.wsum;
     // 5. one output per key run, slice cells compacted in sorted order
-    const double a = plane[0], b = plane[1], c = plane[2], d = plane[3];
-    const double norm = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)), __dmul_rn(c, c)));
+    const uint64_t *words = srt + t0;
     const int64_t cap = cap_end - p0;
     int64_t kept = 0;
-    const int wid = threadIdx.x >> 6;
     for (int32_t base = 0; base < n_ent; base += BEV_BLOCK) {
         const int32_t s = base + threadIdx.x;
-        bool first = false, slice_cell = false;
-        uint64_t me = 0, key = 0;
-        if (s < n_ent) {
-            me = srt[t0 + s];
-            key = me >> KEY_SHIFT;
-            first = s == 0 || (srt[t0 + s - 1] >> KEY_SHIFT) != key;
-            slice_cell = first && (int64_t)key < (int64_t)g.num_slices * n_cells;
-        }
-        const uint64_t m = __ballot(slice_cell);
-        if ((threadIdx.x & 63) == 0) wsum[wid] = (int32_t)__popcll(m);
-        __syncthreads();
-        int32_t before = 0, tot = 0;
-        for (int w = 0; w < BEV_BLOCK / 64; ++w) {
-            before += w < wid ? wsum[w] : 0;
-            tot += wsum[w];
-        }
-        if (first) {
-            const int v = (int)((int64_t)key / n_cells);
-            const int64_t cell = (int64_t)key - (int64_t)v * n_cells;
-            const int xi = (int)(cell / g.nz), zi = (int)(cell - (int64_t)xi * g.nz);
-            const int64_t pix = (int64_t)(g.nz - 1 - zi) * g.nx + xi;  // np.flip(map.T, axis=0)
-            if (v < g.num_slices) {
-                const int64_t pos = kept + before + lane_rank(m);
-                const int64_t li = (int64_t)(uint32_t)me;
-                double x, y, z;
-                Pt<PT>::load(pts, p0 + li, x, y, z);
-                if (pos < cap) {
-                    vox_out[2 * (p0 + pos)] = xi;
-                    vox_out[2 * (p0 + pos) + 1] = g.nz - zi;  // bev_slices.py:108 (num_div_z - z)
-                    pts_out[3 * (p0 + pos)] = x;
-                    pts_out[3 * (p0 + pos) + 1] = y;
-                    pts_out[3 * (p0 + pos) + 2] = z;
-                } else if (err) {
-                    atomicOr(err, SHPL_EBIT_ROW);
-                }
-                if (hmaps) {
-                    // dist_to_plane: (a*x + b*y + c*z + d) / sqrt(a^2 + b^2 + c^2)
-                    const double dist =
-                        __ddiv_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(a, x), __dmul_rn(b, y)), __dmul_rn(c, z)), d),
-                                  norm);
-                    hmaps[((int64_t)f * g.num_slices + v) * n_cells + pix] = __ddiv_rn(__dsub_rn(dist, g.lo[v]), g.hpd);
-                }
-            } else if (dmap) {
-                int32_t n = 1;
-                while (s + n < n_ent && (srt[t0 + s + n] >> KEY_SHIFT) == key) ++n;
-                dmap[(int64_t)f * n_cells + pix] = n < 16 ? g.dens[n] : 1.0;
+        const bool first = s < n_ent && run_head(words, s, KEY_SHIFT);
+        const uint64_t me = first ? words[s] : 0;
+        int v = 0, xi = 0, zi = 0;
+        int64_t pix = 0;
+        if (first) decode_key(g, n_cells, me >> KEY_SHIFT, v, xi, zi, pix);
+        const bool slice_cell = first && v < g.num_slices;
+        int32_t tot;
+        const int64_t pos = kept + block_rank(slice_cell, lds.wsum, tot);
+        if (slice_cell) {
+            double x, y, z;
+            load_point(pts, p0 + (int64_t)(uint32_t)me, x, y, z);
+            if (pos < cap) {
+                vox_out[2 * (p0 + pos)] = xi;
+                vox_out[2 * (p0 + pos) + 1] = g.nz - zi;  // bev_slices.py:108 (num_div_z - z)
+                pts_out[3 * (p0 + pos)] = x;
+                pts_out[3 * (p0 + pos) + 1] = y;
+                pts_out[3 * (p0 + pos) + 2] = z;
+            } else if (err) {
+                atomicOr(err, SHPL_EBIT_ROW);
             }
+            if (hmaps) hmaps[((int64_t)f * g.num_slices + v) * n_cells + pix] = slice_height(g, plane, v, x, y, z);
+        } else if (first && dmap) {
+            dmap[(int64_t)f * n_cells + pix] = density(g, run_len(words, s, n_ent, KEY_SHIFT));
         }
         kept += tot;
-        __syncthreads();
+        __syncthreads();  // block_rank's second barrier
     }
     if (threadIdx.x == 0) {
         frame_nvox[f] = kept < cap ? kept : cap;
@@ -194,45 +186,37 @@ __global__ __launch_bounds__(BEV_BLOCK) void k_bev_frame(BevGeom g, const int64_
 }
 
 // The height and density maps from the sorted words a k_bev_frame launch left in the workspace
-// (shpl_bev_maps): the same values step 5 above writes, by a grid of BEV_MAP_SPLIT workgroups per
+// (shpl_bev_maps): the values step 5 above writes, by a grid of BEV_MAP_SPLIT workgroups per
 // frame over its words -- a cell's first word writes its height (slices) or count-derived density.
 constexpr int BEV_MAP_SPLIT = 16;
 // bev_in (shpl_bev_input): the same values, rounded to f32, interleaved [F, nz, nx, S + 1] instead of the
 // planar f64 maps (channel v < S: height slice v, channel S: density).
-template <typename PT>
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bev_maps(BevGeom g, const int64_t *pt_off, const void *pts,
+__global__ __launch_bounds__(SHPL_BLOCK) void k_bev_maps(BevGeom g, const int64_t *pt_off, const double *pts,
                                                         const double *planes, const uint64_t *srt,
                                                         int64_t ent_per_point, const int32_t *frame_nent,
                                                         double *hmaps, double *dmap, float *bev_in) {
     const int f = blockIdx.y;
-    const int64_t p0 = pt_off[f], t0 = p0 * ent_per_point;
+    const int64_t p0 = pt_off[f];
+    const uint64_t *words = srt + p0 * ent_per_point;
     const int32_t n_ent = frame_nent[f];
     const int64_t n_cells = (int64_t)g.nx * g.nz;
     const double *plane = planes + 4 * f;
-    const double a = plane[0], b = plane[1], c = plane[2], d = plane[3];
-    const double norm = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)), __dmul_rn(c, c)));
     for (int32_t s = blockIdx.x * SHPL_BLOCK + threadIdx.x; s < n_ent; s += BEV_MAP_SPLIT * SHPL_BLOCK) {
-        const uint64_t me = srt[t0 + s];
-        const uint64_t key = me >> KEY_SHIFT;
-        if (s > 0 && (srt[t0 + s - 1] >> KEY_SHIFT) == key) continue;  // not the cell's first word
-        const int v = (int)((int64_t)key / n_cells);
-        const int64_t cell = (int64_t)key - (int64_t)v * n_cells;
-        const int xi = (int)(cell / g.nz), zi = (int)(cell - (int64_t)xi * g.nz);
-        const int64_t pix = (int64_t)(g.nz - 1 - zi) * g.nx + xi;  // np.flip(map.T, axis=0)
+        if (!run_head(words, s, KEY_SHIFT)) continue;  // not the cell's first word
+        const uint64_t me = words[s];
+        int v, xi, zi;
+        int64_t pix;
+        decode_key(g, n_cells, me >> KEY_SHIFT, v, xi, zi, pix);
         const int64_t in_at = ((int64_t)f * n_cells + pix) * (g.num_slices + 1) + v;  // bev_in element
         if (v < g.num_slices) {
             if (!hmaps && !bev_in) continue;
             double x, y, z;
-            Pt<PT>::load(pts, p0 + (int64_t)(uint32_t)me, x, y, z);
-            const double dist =
-                __ddiv_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(a, x), __dmul_rn(b, y)), __dmul_rn(c, z)), d), norm);
-            const double h = __ddiv_rn(__dsub_rn(dist, g.lo[v]), g.hpd);
+            load_point(pts, p0 + (int64_t)(uint32_t)me, x, y, z);
+            const double h = slice_height(g, plane, v, x, y, z);
             if (hmaps) hmaps[((int64_t)f * g.num_slices + v) * n_cells + pix] = h;
             if (bev_in) bev_in[in_at] = __double2float_rn(h);
         } else if (dmap || bev_in) {
-            int32_t n = 1;
-            while (s + n < n_ent && (srt[t0 + s + n] >> KEY_SHIFT) == key) ++n;
-            const double dn = n < 16 ? g.dens[n] : 1.0;
+            const double dn = density(g, run_len(words, s, n_ent, KEY_SHIFT));
             if (dmap) dmap[(int64_t)f * n_cells + pix] = dn;
             if (bev_in) bev_in[in_at] = __double2float_rn(dn);
         }
@@ -247,13 +231,30 @@ size_t bev_half_bytes(int64_t total_points, int num_slices) {
     const size_t n = (size_t)(total_points > 0 ? total_points : 1) * (size_t)(num_slices + 1);
     return align_up(n * sizeof(uint64_t), 256);
 }
+size_t bev_ws_bytes(int64_t total_points, int num_slices) {
+    return 2 * bev_half_bytes(total_points, num_slices) + align_up(sizeof(int32_t) * BEV_MAX_FRAMES, 256);
+}
 
-// BevGeom of the call's host arguments (SHPL_OK or a status).
-int bev_geom(const double *area_extents, double voxel_size, int num_slices, const double *slice_lo,
-             const double *slice_hi, double density_lo, double density_hi, double height_per_division,
-             const double *density_table, BevGeom &g) {
+// What the three entry points launch with: the geometry, the carved workspace and a map's elements per frame.
+struct BevCall {
+    BevGeom g;
+    uint64_t *tmp, *srt;
+    int32_t *nent;  // null past BEV_MAX_FRAMES frames (shpl_bev_slices only)
+    int64_t per_map;
+};
+
+// The set-up of the three entry points from the call's host arguments: SHPL_OK and c filled, or the status the
+// geometry and the workspace get. ws_first: a short workspace is answered before the grid's shape
+// (shpl_bev_slices' order; shpl_bev_maps and shpl_bev_input answer the shape first).
+int bev_setup(const double *area_extents, double voxel_size, int num_slices, const double *slice_lo,
+              const double *slice_hi, double density_lo, double density_hi, double height_per_division,
+              const double *density_table, int n_frames, int64_t total_points, const void *d_ws, size_t ws_bytes,
+              bool ws_first, BevCall &c) {
     if (!area_extents || !slice_lo || !slice_hi || !density_table) return SHPL_ERR_ARG;
     if (num_slices < 1 || num_slices > BEV_MAX_SLICES || !(voxel_size > 0)) return SHPL_ERR_BAD_SHAPE;
+    const bool ws_short = bev_ws_bytes(total_points, num_slices) > ws_bytes;
+    if (ws_first && ws_short) return SHPL_ERR_WORKSPACE;
+    BevGeom &g = c.g;
     g = BevGeom{};
     for (int i = 0; i < 3; ++i) {
         g.ext[i][0] = area_extents[2 * i];
@@ -279,8 +280,21 @@ int bev_geom(const double *area_extents, double voxel_size, int num_slices, cons
     if (g.nx < 1 || g.nz < 1 || ny < 1 || ny >= 1024) return SHPL_ERR_BAD_SHAPE;
     const int64_t n_keys = (int64_t)g.nx * g.nz * (num_slices + 1);
     if (n_keys >= ((int64_t)1 << 22)) return SHPL_ERR_BAD_SHAPE;  // key field of the packed word
-    g.log_tile = 0;
-    while (((n_keys - 1) >> g.log_tile) + 1 > BEV_TILES) ++g.log_tile;
+    g.log_tile = ts_log_tile(n_keys);
+    if (ws_short) return SHPL_ERR_WORKSPACE;
+    const size_t half = bev_half_bytes(total_points, num_slices);
+    c.tmp = (uint64_t *)d_ws;
+    c.srt = (uint64_t *)((char *)d_ws + half);
+    c.nent = n_frames <= BEV_MAX_FRAMES ? (int32_t *)((char *)d_ws + 2 * half) : nullptr;
+    c.per_map = (int64_t)g.nx * g.nz;
+    return SHPL_OK;
+}
+
+// The maps' zeros: a streaming kernel (hipMemsetAsync's fill ran at ~2.2 TB/s, beside k_dense)
+int zero_maps(const BevCall &c, int n_frames, double *d_height_maps, double *d_density_map, hipStream_t s) {
+    if (d_height_maps)
+        SHPL_HIP_CHECK(zero_fill(d_height_maps, sizeof(double) * (size_t)(c.per_map * c.g.num_slices * n_frames), s));
+    if (d_density_map) SHPL_HIP_CHECK(zero_fill(d_density_map, sizeof(double) * (size_t)(c.per_map * n_frames), s));
     return SHPL_OK;
 }
 
@@ -291,7 +305,7 @@ using namespace shpl;
 
 extern "C" int shpl_bev_workspace_bytes(int64_t total_points, int num_slices, size_t *bytes) {
     if (!bytes || total_points < 0 || num_slices < 1 || num_slices > BEV_MAX_SLICES) return SHPL_ERR_ARG;
-    *bytes = 2 * bev_half_bytes(total_points, num_slices) + align_up(sizeof(int32_t) * BEV_MAX_FRAMES, 256);
+    *bytes = bev_ws_bytes(total_points, num_slices);
     return SHPL_OK;
 }
 
@@ -310,30 +324,16 @@ extern "C" int shpl_bev_slices(int n_frames, const int64_t *d_point_offsets, con
     if (num_slices < 1 || num_slices > BEV_MAX_SLICES || !(voxel_size > 0)) return SHPL_ERR_BAD_SHAPE;
     if (total_points > 0 && (!d_points || !d_voxel_indices || !d_pts_in_voxel)) return SHPL_ERR_ARG;
     if (total_points >= ((int64_t)1 << 31)) return SHPL_ERR_BAD_SHAPE;
-    size_t need;
-    shpl_bev_workspace_bytes(total_points, num_slices, &need);
-    if (need > ws_bytes) return SHPL_ERR_WORKSPACE;
-    BevGeom g;
-    const int rc = bev_geom(area_extents, voxel_size, num_slices, slice_lo, slice_hi, density_lo, density_hi,
-                            height_per_division, density_table, g);
+    BevCall c;
+    int rc = bev_setup(area_extents, voxel_size, num_slices, slice_lo, slice_hi, density_lo, density_hi,
+                       height_per_division, density_table, n_frames, total_points, d_ws, ws_bytes, true, c);
     if (rc) return rc;
-    const size_t half = bev_half_bytes(total_points, num_slices);
-    uint64_t *tmp = (uint64_t *)d_ws;
-    uint64_t *srt = (uint64_t *)((char *)d_ws + half);
-    int32_t *nent = n_frames <= BEV_MAX_FRAMES ? (int32_t *)((char *)d_ws + 2 * half) : nullptr;
+    if (points_dtype != SHPL_F64) return SHPL_ERR_ARG;  // before the fills: a refused call writes nothing
     hipStream_t s = (hipStream_t)stream;
-    const int64_t per_map = (int64_t)g.nx * g.nz;
-    // the maps' zeros: a streaming kernel (hipMemsetAsync's fill ran at ~2.2 TB/s, beside k_dense)
-    if (d_height_maps)
-        SHPL_HIP_CHECK(zero_fill(d_height_maps, sizeof(double) * (size_t)(per_map * num_slices * n_frames), s));
-    if (d_density_map) SHPL_HIP_CHECK(zero_fill(d_density_map, sizeof(double) * (size_t)(per_map * n_frames), s));
-    if (points_dtype == SHPL_F64)
-        hipLaunchKernelGGL(k_bev_frame<double>, dim3(n_frames), dim3(BEV_BLOCK), 0, s, g, d_point_offsets,
-                           d_point_counts, d_points,
-                           d_planes, tmp, srt, (int64_t)(num_slices + 1), d_voxel_indices, d_pts_in_voxel,
-                           d_frame_nvox, d_height_maps, d_density_map, nent, d_err);
-    else
-        return SHPL_ERR_ARG;
+    if ((rc = zero_maps(c, n_frames, d_height_maps, d_density_map, s)) != SHPL_OK) return rc;
+    hipLaunchKernelGGL(k_bev_frame, dim3(n_frames), dim3(BEV_BLOCK), 0, s, c.g, d_point_offsets, d_point_counts,
+                       (const double *)d_points, d_planes, c.tmp, c.srt, (int64_t)(num_slices + 1), d_voxel_indices,
+                       d_pts_in_voxel, d_frame_nvox, d_height_maps, d_density_map, c.nent, d_err);
     SHPL_LAUNCH_CHECK();
     return SHPL_OK;
 }
@@ -347,27 +347,16 @@ extern "C" int shpl_bev_maps(int n_frames, const int64_t *d_point_offsets, int64
     if (n_frames < 1 || !d_point_offsets || !d_planes || !d_ws) return SHPL_ERR_ARG;
     if (points_dtype != SHPL_F64 || (total_points > 0 && !d_points)) return SHPL_ERR_ARG;
     if (total_points < 0 || total_points >= ((int64_t)1 << 31) || n_frames > BEV_MAX_FRAMES) return SHPL_ERR_BAD_SHAPE;
-    BevGeom g;
-    const int rc = bev_geom(area_extents, voxel_size, num_slices, slice_lo, slice_hi, density_lo, density_hi,
-                            height_per_division, density_table, g);
+    BevCall c;
+    int rc = bev_setup(area_extents, voxel_size, num_slices, slice_lo, slice_hi, density_lo, density_hi,
+                       height_per_division, density_table, n_frames, total_points, d_ws, ws_bytes, false, c);
     if (rc) return rc;
-    size_t need;
-    shpl_bev_workspace_bytes(total_points, num_slices, &need);
-    if (need > ws_bytes) return SHPL_ERR_WORKSPACE;
-    const size_t half = bev_half_bytes(total_points, num_slices);
-    const uint64_t *srt = (const uint64_t *)((const char *)d_ws + half);
-    const int32_t *nent = (const int32_t *)((const char *)d_ws + 2 * half);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t per_map = (int64_t)g.nx * g.nz;
-    if (zero) {
-        if (d_height_maps)
-            SHPL_HIP_CHECK(zero_fill(d_height_maps, sizeof(double) * (size_t)(per_map * num_slices * n_frames), s));
-        if (d_density_map) SHPL_HIP_CHECK(zero_fill(d_density_map, sizeof(double) * (size_t)(per_map * n_frames), s));
-    }
+    if (zero && (rc = zero_maps(c, n_frames, d_height_maps, d_density_map, s)) != SHPL_OK) return rc;
     if (!d_height_maps && !d_density_map) return SHPL_OK;
-    hipLaunchKernelGGL(k_bev_maps<double>, dim3(BEV_MAP_SPLIT, n_frames), dim3(SHPL_BLOCK), 0, s, g, d_point_offsets,
-                       d_points, d_planes, srt, (int64_t)(num_slices + 1), nent, d_height_maps, d_density_map,
-                       (float *)nullptr);
+    hipLaunchKernelGGL(k_bev_maps, dim3(BEV_MAP_SPLIT, n_frames), dim3(SHPL_BLOCK), 0, s, c.g, d_point_offsets,
+                       (const double *)d_points, d_planes, (const uint64_t *)c.srt, (int64_t)(num_slices + 1),
+                       (const int32_t *)c.nent, d_height_maps, d_density_map, (float *)nullptr);
     SHPL_LAUNCH_CHECK();
     return SHPL_OK;
 }
@@ -380,22 +369,15 @@ extern "C" int shpl_bev_input(int n_frames, const int64_t *d_point_offsets, int6
     if (n_frames < 1 || !d_point_offsets || !d_planes || !d_ws || !d_bev_input) return SHPL_ERR_ARG;
     if (points_dtype != SHPL_F64 || (total_points > 0 && !d_points)) return SHPL_ERR_ARG;
     if (total_points < 0 || total_points >= ((int64_t)1 << 31) || n_frames > BEV_MAX_FRAMES) return SHPL_ERR_BAD_SHAPE;
-    BevGeom g;
-    const int rc = bev_geom(area_extents, voxel_size, num_slices, slice_lo, slice_hi, density_lo, density_hi,
-                            height_per_division, density_table, g);
+    BevCall c;
+    const int rc = bev_setup(area_extents, voxel_size, num_slices, slice_lo, slice_hi, density_lo, density_hi,
+                             height_per_division, density_table, n_frames, total_points, d_ws, ws_bytes, false, c);
     if (rc) return rc;
-    size_t need;
-    shpl_bev_workspace_bytes(total_points, num_slices, &need);
-    if (need > ws_bytes) return SHPL_ERR_WORKSPACE;
-    const size_t half = bev_half_bytes(total_points, num_slices);
-    const uint64_t *srt = (const uint64_t *)((const char *)d_ws + half);
-    const int32_t *nent = (const int32_t *)((const char *)d_ws + 2 * half);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t per_map = (int64_t)g.nx * g.nz;
-    SHPL_HIP_CHECK(zero_fill(d_bev_input, sizeof(float) * (size_t)(per_map * (num_slices + 1) * n_frames), s));
-    hipLaunchKernelGGL(k_bev_maps<double>, dim3(BEV_MAP_SPLIT, n_frames), dim3(SHPL_BLOCK), 0, s, g, d_point_offsets,
-                       d_points, d_planes, srt, (int64_t)(num_slices + 1), nent, (double *)nullptr, (double *)nullptr,
-                       d_bev_input);
+    SHPL_HIP_CHECK(zero_fill(d_bev_input, sizeof(float) * (size_t)(c.per_map * (num_slices + 1) * n_frames), s));
+    hipLaunchKernelGGL(k_bev_maps, dim3(BEV_MAP_SPLIT, n_frames), dim3(SHPL_BLOCK), 0, s, c.g, d_point_offsets,
+                       (const double *)d_points, d_planes, (const uint64_t *)c.srt, (int64_t)(num_slices + 1),
+                       (const int32_t *)c.nent, (double *)nullptr, (double *)nullptr, d_bev_input);
     SHPL_LAUNCH_CHECK();
     return SHPL_OK;
 }

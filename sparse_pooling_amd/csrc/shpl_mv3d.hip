@@ -145,7 +145,22 @@ __device__ __forceinline__ bool frame_point(const Mv3dAug<AUG> &ag, const T *pts
 }
 
 constexpr int AUG_UNROLL = 4;            // points per thread in flight while the augmented words are formed
-constexpr uint64_t NO_WORD = ~0ull;      // a rejected point's parked word (keys are below 2^31)
+constexpr uint64_t NO_WORD = ~0ull;      // a rejected point's word (keys are below 2^31)
+
+// The sort word of a frame's out point i -- (voxel key, point index in the frame) -- into w; false, and w as it
+// was, for a point outside the ranges or without a source.
+template <typename T, bool AUG>
+__device__ __forceinline__ bool point_word(const Mv3dGeom &g, const Mv3dAug<AUG> &ag, const T *pts, int64_t pt_stride,
+                                           int f, int64_t i, int64_t p0, int64_t p1, int64_t q0, int64_t nq,
+                                           uint64_t &w) {
+    T x, y, z, ox, oy, oz;
+    int64_t src;
+    if (!frame_point<T, AUG>(ag, pts, pt_stride, f, i, p0, p1, q0, nq, x, y, z, ox, oy, oz, src)) return false;
+    int si, fi;
+    const int64_t key = voxel_key<T>(g, x, y, z, si, fi);
+    if (key >= 0) w = ((uint64_t)key << 32) | (uint32_t)(i - p0);
+    return key >= 0;
+}
 
 template <typename T, bool AUG>
 __global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64_t *pt_off, const T *pts,
@@ -181,13 +196,7 @@ __global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64
             for (int u = 0; u < AUG_UNROLL; ++u) {
                 const int64_t i = b + (int64_t)u * TS_BLOCK;
                 w[u] = NO_WORD;
-                T x, y, z, ox, oy, oz;
-                int64_t src;
-                if (i < p1 && frame_point<T, AUG>(ag, pts, pt_stride, f, i, p0, p1, q0, nq, x, y, z, ox, oy, oz, src)) {
-                    int si, fi;
-                    const int64_t key = voxel_key<T>(g, x, y, z, si, fi);
-                    if (key >= 0) w[u] = ((uint64_t)key << 32) | (uint32_t)(i - p0);
-                }
+                if (i < p1) point_word<T, AUG>(g, ag, pts, pt_stride, f, i, p0, p1, q0, nq, w[u]);
             }
 #pragma unroll
             for (int u = 0; u < AUG_UNROLL; ++u) {
@@ -200,28 +209,22 @@ __global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64
         lds, n_tiles, tmp + p0, srt + p0,
         [&](auto &&emit) {
             for (int64_t i = p0 + threadIdx.x; i < p1; i += TS_BLOCK) {
+                uint64_t w;
                 if constexpr (AUG) {
-                    const uint64_t w = srt[i];
-                    if (w != NO_WORD) emit(w);
-                } else {
-                    T x, y, z, ox, oy, oz;
-                    int64_t src;
-                    frame_point<T, AUG>(ag, pts, pt_stride, f, i, p0, p1, q0, nq, x, y, z, ox, oy, oz, src);
-                    int si, fi;
-                    const int64_t key = voxel_key<T>(g, x, y, z, si, fi);
-                    if (key >= 0) emit(((uint64_t)key << 32) | (uint32_t)(i - p0));
+                    if ((w = srt[i]) != NO_WORD) emit(w);
+                } else if (point_word<T, AUG>(g, ag, pts, pt_stride, f, i, p0, p1, q0, nq, w)) {
+                    emit(w);
                 }
             }
         },
         [&](uint64_t w) { return (int)((w >> 32) >> g.log_tile); });
+    const uint64_t *words = srt + p0;
     // run starts: accept the first `cap` points of every voxel (point order = word order)
     for (int32_t s = threadIdx.x; s < n; s += TS_BLOCK) {
-        const uint64_t key = srt[p0 + s] >> 32;
-        if (s > 0 && (srt[p0 + s - 1] >> 32) == key) continue;
-        int32_t run = 1;
-        while (s + run < n && (srt[p0 + s + run] >> 32) == key) ++run;
+        if (!run_head(words, s, 32)) continue;
+        const int32_t run = run_len(words, s, n, 32);
         const int32_t a = run < g.cap ? run : g.cap;
-        for (int32_t u = 0; u < a; ++u) acc[p0 + (uint32_t)srt[p0 + s + u]] = a;
+        for (int32_t u = 0; u < a; ++u) acc[p0 + (uint32_t)words[s + u]] = a;
     }
     block_publish();
     // optional VFE buffers: number_buffer per voxel in voxel order
@@ -229,27 +232,13 @@ __global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64
         int64_t base = 0;
         for (int32_t b0 = 0; b0 < n; b0 += TS_BLOCK) {
             const int32_t s = b0 + threadIdx.x;
-            bool first = false;
-            int32_t run = 0;
-            if (s < n) {
-                const uint64_t key = srt[p0 + s] >> 32;
-                first = s == 0 || (srt[p0 + s - 1] >> 32) != key;
-                if (first) {
-                    run = 1;
-                    while (s + run < n && (srt[p0 + s + run] >> 32) == key) ++run;
-                }
-            }
-            const uint64_t m = __ballot(first);
-            if ((threadIdx.x & 63) == 0) lds.wsum[threadIdx.x >> 6] = (int32_t)__popcll(m);
-            __syncthreads();
-            int32_t before = 0, tot = 0;
-            for (int w = 0; w < TS_BLOCK / 64; ++w) {
-                before += w < (int)(threadIdx.x >> 6) ? lds.wsum[w] : 0;
-                tot += lds.wsum[w];
-            }
-            if (first) vox_count[p0 + base + before + lane_rank(m)] = run < g.cap ? run : g.cap;
+            const bool first = s < n && run_head(words, s, 32);
+            const int32_t run = first ? run_len(words, s, n, 32) : 0;
+            int32_t tot;
+            const int32_t rank = block_rank(first, lds.wsum, tot);
+            if (first) vox_count[p0 + base + rank] = run < g.cap ? run : g.cap;
             base += tot;
-            __syncthreads();
+            __syncthreads();  // block_rank's second barrier
         }
         if (threadIdx.x == 0) frame_nvox[f] = base;
     }
@@ -259,19 +248,13 @@ __global__ __launch_bounds__(TS_BLOCK) void k_mv3d_frame(Mv3dGeom g, const int64
         const int64_t i = b0 + threadIdx.x;
         const int32_t a = i < p1 ? acc[i] : 0;
         const bool keep = a > 0;
-        const uint64_t m = __ballot(keep);
-        if ((threadIdx.x & 63) == 0) lds.wsum[threadIdx.x >> 6] = (int32_t)__popcll(m);
-        __syncthreads();
-        int32_t before = 0, tot = 0;
-        for (int w = 0; w < TS_BLOCK / 64; ++w) {
-            before += w < (int)(threadIdx.x >> 6) ? lds.wsum[w] : 0;
-            tot += lds.wsum[w];
-        }
+        int32_t tot;
+        const int32_t rank = block_rank(keep, lds.wsum, tot);
         T x, y, z, ox, oy, oz;
         int64_t src;
         // (an accepted point was read in the key pass; AUG bounds its remain entry again before this read)
         if (keep && frame_point<T, AUG>(ag, pts, pt_stride, f, i, p0, p1, q0, nq, x, y, z, ox, oy, oz, src)) {
-            const int64_t pos = p0 + kept + before + lane_rank(m);
+            const int64_t pos = p0 + kept + rank;
             int si = 0, fi = 0;
             voxel_key<T>(g, x, y, z, si, fi);
             int64_t u, v;
@@ -350,9 +333,31 @@ int make_aug(const int64_t *d_point_offsets, int64_t total_points, const void *d
     return SHPL_OK;
 }
 
-// voxel_full_size and the sort's tiling from the ranges (construct_voxel.py:77-80)
-int make_geom(const double *ranges, double res, double zres, int voxel_point_count, bool has_proj, Mv3dGeom *out) {
-    Mv3dGeom g{};
+// The workspace of n_slots point slots: tmp at 0, srt at `words` and acc at 2 * words bytes (a word per slot
+// twice, then a count per slot). Returns its size.
+size_t mv3d_ws(int64_t n_slots, size_t &words) {
+    const size_t n = (size_t)(n_slots > 0 ? n_slots : 1);
+    words = align_up(n * sizeof(uint64_t), 256);
+    return 2 * words + align_up(n * sizeof(int32_t), 256);
+}
+
+// What shpl_mv3d_voxels and shpl_mv3d_voxels_aug check behind their own pointers, over the call's n_slots point
+// slots (its points, or the augmented call's out points), in this order -- the outputs, the source of the image
+// index, number_buffer's companion, the shapes, the workspace -- and then voxel_full_size and the sort's tiling
+// from the ranges. SHPL_OK and g filled, or the status the arguments get.
+int check_producer(int64_t n_slots, const double *d_img_index, const int64_t *d_bv_index, const double *d_mval,
+                   const int64_t *d_img_index2, const double *d_P, const int32_t *d_number_buffer,
+                   const int64_t *d_frame_nvox, int64_t point_stride, int64_t ld, const double *ranges, double res,
+                   double zres, int voxel_point_count, size_t ws_bytes, Mv3dGeom &g) {
+    if (n_slots > 0 && (!d_img_index || !d_bv_index || !d_mval)) return SHPL_ERR_ARG;
+    if (!d_img_index2 && !d_P) return SHPL_ERR_ARG;
+    if (d_number_buffer && !d_frame_nvox) return SHPL_ERR_ARG;
+    if (point_stride < 3 || ld < n_slots || !(res > 0) || !(zres > 0) || voxel_point_count < 1 ||
+        n_slots >= ((int64_t)1 << 31))
+        return SHPL_ERR_BAD_SHAPE;
+    size_t words;
+    if (mv3d_ws(n_slots, words) > ws_bytes) return SHPL_ERR_WORKSPACE;
+    g = Mv3dGeom{};
     g.fwd_lo = ranges[0];
     g.fwd_hi = ranges[1];
     g.side_lo = ranges[2];
@@ -366,26 +371,25 @@ int make_geom(const double *ranges, double res, double zres, int voxel_point_cou
     g.n_fwd = (int)((g.fwd_hi - g.fwd_lo) / res) + 1;
     g.n_h = (int)((g.h_hi - g.h_lo) / zres) + 1;
     g.cap = voxel_point_count;
-    g.has_proj = has_proj ? 1 : 0;
+    g.has_proj = d_img_index2 ? 0 : 1;
     const int64_t n_keys = (int64_t)g.n_side * g.n_fwd * g.n_h;
     if (n_keys >= ((int64_t)1 << 31)) return SHPL_ERR_BAD_SHAPE;
-    g.log_tile = 0;
-    while (((n_keys - 1) >> g.log_tile) + 1 > TS_TILES) ++g.log_tile;
-    *out = g;
+    g.log_tile = ts_log_tile(n_keys);
     return SHPL_OK;
 }
 
-// One workgroup per frame; the workspace holds tmp / srt / acc for n_slots point slots (shpl_mv3d_workspace_bytes).
+// One workgroup per frame over the workspace's n_slots point slots.
 template <typename T, bool AUG>
 int launch_frames(const Mv3dGeom &g, int n_frames, const int64_t *d_point_offsets, const void *d_points,
                   int64_t point_stride, const int64_t *d_img_index2, int64_t img2_ld, const double *d_P,
                   const double *d_fv_aug, int64_t n_slots, double *d_img_index, int64_t ld, int64_t *d_bv_index,
                   double *d_mval, int64_t *d_frame_n, int32_t *d_number_buffer, int64_t *d_frame_nvox, void *d_ws,
                   const Mv3dAug<AUG> &ag, hipStream_t stream) {
-    const size_t n = (size_t)(n_slots > 0 ? n_slots : 1);
+    size_t words;
+    mv3d_ws(n_slots, words);
     uint64_t *tmp = (uint64_t *)d_ws;
-    uint64_t *srt = (uint64_t *)((char *)d_ws + align_up(n * sizeof(uint64_t), 256));
-    int32_t *acc = (int32_t *)((char *)d_ws + 2 * align_up(n * sizeof(uint64_t), 256));
+    uint64_t *srt = (uint64_t *)((char *)d_ws + words);
+    int32_t *acc = (int32_t *)((char *)d_ws + 2 * words);
     hipLaunchKernelGGL((k_mv3d_frame<T, AUG>), dim3(n_frames), dim3(TS_BLOCK), 0, stream, g, d_point_offsets,
                        (const T *)d_points, point_stride, d_img_index2, img2_ld, d_P, d_fv_aug, tmp, srt, acc,
                        d_img_index, ld, d_bv_index, d_mval, d_frame_n, d_number_buffer, d_frame_nvox, ag);
@@ -400,8 +404,8 @@ using namespace shpl;
 
 extern "C" int shpl_mv3d_workspace_bytes(int64_t total_points, size_t *bytes) {
     if (!bytes || total_points < 0) return SHPL_ERR_ARG;
-    const size_t n = (size_t)(total_points > 0 ? total_points : 1);
-    *bytes = 2 * align_up(n * sizeof(uint64_t), 256) + align_up(n * sizeof(int32_t), 256);
+    size_t words;
+    *bytes = mv3d_ws(total_points, words);
     return SHPL_OK;
 }
 
@@ -412,17 +416,10 @@ extern "C" int shpl_mv3d_voxels(int n_frames, const int64_t *d_point_offsets, in
                                 double *d_mval, int64_t *d_frame_n, int32_t *d_number_buffer,
                                 int64_t *d_frame_nvox, void *d_ws, size_t ws_bytes, void *stream) {
     if (n_frames < 1 || !d_point_offsets || !ranges || !d_frame_n || !d_ws) return SHPL_ERR_ARG;
-    if (total_points > 0 && (!d_points || !d_img_index || !d_bv_index || !d_mval)) return SHPL_ERR_ARG;
-    if (!d_img_index2 && !d_P) return SHPL_ERR_ARG;
-    if (d_number_buffer && !d_frame_nvox) return SHPL_ERR_ARG;
-    if (point_stride < 3 || ld < total_points || !(res > 0) || !(zres > 0) || voxel_point_count < 1 ||
-        total_points >= ((int64_t)1 << 31))
-        return SHPL_ERR_BAD_SHAPE;
-    size_t need;
-    shpl_mv3d_workspace_bytes(total_points, &need);
-    if (need > ws_bytes) return SHPL_ERR_WORKSPACE;
+    if (total_points > 0 && !d_points) return SHPL_ERR_ARG;
     Mv3dGeom g;
-    const int st = make_geom(ranges, res, zres, voxel_point_count, !d_img_index2, &g);
+    const int st = check_producer(total_points, d_img_index, d_bv_index, d_mval, d_img_index2, d_P, d_number_buffer,
+                                  d_frame_nvox, point_stride, ld, ranges, res, zres, voxel_point_count, ws_bytes, g);
     if (st != SHPL_OK) return st;
     return launch_frames<double, false>(g, n_frames, d_point_offsets, d_points, point_stride, d_img_index2, total_points,
                                         d_P, d_fv_aug, total_points, d_img_index, ld, d_bv_index, d_mval, d_frame_n,
@@ -469,22 +466,12 @@ extern "C" int shpl_mv3d_voxels_aug(int n_frames, const int64_t *d_point_offsets
     int st = make_aug(d_point_offsets, total_points, d_points, point_dtype, d_vox_aug, d_remain_index, d_remain_offsets,
                       total_out, d_err, &ag);
     if (st != SHPL_OK) return st;
-    if (total_out > 0 && (!d_img_index || !d_bv_index || !d_mval)) return SHPL_ERR_ARG;
-    if (!d_img_index2 && !d_P) return SHPL_ERR_ARG;
-    if (d_number_buffer && !d_frame_nvox) return SHPL_ERR_ARG;
-    if (point_stride < 3 || ld < total_out || !(res > 0) || !(zres > 0) || voxel_point_count < 1)
-        return SHPL_ERR_BAD_SHAPE;
-    size_t need;
-    shpl_mv3d_workspace_bytes(total_out, &need);
-    if (need > ws_bytes) return SHPL_ERR_WORKSPACE;
     Mv3dGeom g;
-    st = make_geom(ranges, res, zres, voxel_point_count, !d_img_index2, &g);
+    st = check_producer(total_out, d_img_index, d_bv_index, d_mval, d_img_index2, d_P, d_number_buffer, d_frame_nvox,
+                        point_stride, ld, ranges, res, zres, voxel_point_count, ws_bytes, g);
     if (st != SHPL_OK) return st;
-    if (point_dtype == SHPL_F32)
-        return launch_frames<float, true>(g, n_frames, d_point_offsets, d_points, point_stride, d_img_index2, total_points,
-                                          d_P, d_fv_aug, total_out, d_img_index, ld, d_bv_index, d_mval, d_frame_n,
-                                          d_number_buffer, d_frame_nvox, d_ws, ag, (hipStream_t)stream);
-    return launch_frames<double, true>(g, n_frames, d_point_offsets, d_points, point_stride, d_img_index2, total_points,
-                                       d_P, d_fv_aug, total_out, d_img_index, ld, d_bv_index, d_mval, d_frame_n,
-                                       d_number_buffer, d_frame_nvox, d_ws, ag, (hipStream_t)stream);
+    const auto launch = point_dtype == SHPL_F32 ? launch_frames<float, true> : launch_frames<double, true>;
+    return launch(g, n_frames, d_point_offsets, d_points, point_stride, d_img_index2, total_points, d_P, d_fv_aug,
+                  total_out, d_img_index, ld, d_bv_index, d_mval, d_frame_n, d_number_buffer, d_frame_nvox, d_ws, ag,
+                  (hipStream_t)stream);
 }

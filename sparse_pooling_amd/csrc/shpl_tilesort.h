@@ -39,6 +39,13 @@ __device__ __forceinline__ void ts_scan(TileSortLds &l) {
     }
 }
 
+// Host side: the smallest log2 tile width at which n_keys keys fit TS_TILES tiles.
+inline int ts_log_tile(int64_t n_keys) {
+    int log_tile = 0;
+    while (((n_keys - 1) >> log_tile) + 1 > TS_TILES) ++log_tile;
+    return log_tile;
+}
+
 // Sorts the words produced by `each(emit)` (every thread enumerates its share
 // and calls emit(word) per word) into srt[0..n), using tmp[0..n) as scratch.
 // tile(word) -> tile index in [0, n_tiles). Returns n (same in every thread).
@@ -74,6 +81,35 @@ __device__ int32_t tile_sort(TileSortLds &l, int n_tiles, uint64_t *tmp, uint64_
     }
     block_publish();
     return n;
+}
+
+// Ballot compaction: the thread's rank among the block's threads with `flag` set, and in `total` their count.
+// One barrier inside, between the waves' counts in wsum (TileSortLds::wsum) and their sums; the caller owes a
+// second one before wsum is written again (the next block_rank), since a slower wave may still be summing.
+__device__ __forceinline__ int32_t block_rank(bool flag, int32_t *wsum, int32_t &total) {
+    const uint64_t m = __ballot(flag);
+    const int wid = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) wsum[wid] = (int32_t)__popcll(m);
+    __syncthreads();
+    int32_t before = 0;
+    total = 0;
+    for (int w = 0; w < TS_BLOCK / 64; ++w) {
+        before += w < wid ? wsum[w] : 0;
+        total += wsum[w];
+    }
+    return before + (int32_t)lane_rank(m);
+}
+
+// Key runs of the sorted words srt[0..n), key = word >> shift: is word s the first of its key, and the number
+// of words of the run that starts at s.
+__device__ __forceinline__ bool run_head(const uint64_t *srt, int32_t s, int shift) {
+    return s == 0 || (srt[s - 1] >> shift) != (srt[s] >> shift);
+}
+__device__ __forceinline__ int32_t run_len(const uint64_t *srt, int32_t s, int32_t n, int shift) {
+    const uint64_t key = srt[s] >> shift;
+    int32_t len = 1;
+    while (s + len < n && (srt[s + len] >> shift) == key) ++len;
+    return len;
 }
 
 }  // namespace shpl

@@ -254,22 +254,19 @@ def mv3d_voxels_batch(points, point_offsets, img_index2=None, P=None, ranges=PED
     ws = L.workspace(L.ws_bytes("shpl_mv3d", n_out), dev)
     rng = np.ascontiguousarray(ranges, dtype=np.float64)
     out = {"img_index": img, "bv_index": bv, "M_val": mv, "frame_n": fn, "number_buffer": nb, "frame_nvox": nvox}
+    # what the two C calls share; the augmented one has its dtype, draws, gather and error word in between
+    head = (F, L.ptr(point_offsets), N, L.ptr(points))
+    source = (int(points.stride(0)), L.ptr(img_index2), L.ptr(P), L.ptr(fv_aug))
+    grid = (rng.ctypes.data_as(ctypes.c_void_p), float(res), float(zres), int(voxel_point_count))
+    outputs = (L.ptr(img), cap, L.ptr(bv), L.ptr(mv), L.ptr(fn), L.ptr(nb), L.ptr(nvox))
+    tail = (L.ptr(ws), ws.numel(), L.stream_of(dev))
     if vox_aug is None:
-        L.check(L.lib().shpl_mv3d_voxels(F, L.ptr(point_offsets), N, L.ptr(points), int(points.stride(0)),
-                                         L.ptr(img_index2), L.ptr(P), L.ptr(fv_aug),
-                                         rng.ctypes.data_as(ctypes.c_void_p), float(res),
-                                         float(zres), int(voxel_point_count), L.ptr(img), cap, L.ptr(bv), L.ptr(mv),
-                                         L.ptr(fn), L.ptr(nb), L.ptr(nvox), L.ptr(ws), ws.numel(),
-                                         L.stream_of(dev)), "shpl_mv3d_voxels")
+        L.check(L.lib().shpl_mv3d_voxels(*head, *source, *grid, *outputs, *tail), "shpl_mv3d_voxels")
         return out
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.check(L.lib().shpl_mv3d_voxels_aug(F, L.ptr(point_offsets), N, L.ptr(points), code, int(points.stride(0)),
-                                         L.ptr(img_index2), L.ptr(P), L.ptr(fv_aug), L.ptr(vox_aug),
-                                         L.ptr(remain_index), L.ptr(remain_offsets), n_out,
-                                         rng.ctypes.data_as(ctypes.c_void_p), float(res), float(zres),
-                                         int(voxel_point_count), L.ptr(img), cap, L.ptr(bv), L.ptr(mv), L.ptr(fn),
-                                         L.ptr(nb), L.ptr(nvox), L.ptr(err), L.ptr(ws), ws.numel(),
-                                         L.stream_of(dev)), "shpl_mv3d_voxels_aug")
+    L.check(L.lib().shpl_mv3d_voxels_aug(*head, code, *source, L.ptr(vox_aug), L.ptr(remain_index),
+                                         L.ptr(remain_offsets), n_out, *grid, *outputs, L.ptr(err), *tail),
+            "shpl_mv3d_voxels_aug")
     out["offsets"] = point_offsets if remain_offsets is None else remain_offsets
     out["err"] = err
     return out

@@ -577,10 +577,8 @@ class FramePipeline(FusedPipeline):
     def _input_buffer(self):
         """The step's BEV input tensor [F,nz,nx,S+1] f32 (maps_form "bev_input"), allocated once."""
         if getattr(self, "_bev_input", None) is None:
-            from . import bev as _bev
-            area, vs, _, _, S = self.bev_args
-            nx, nz = _bev.grid_divisions(area, vs)
-            self._bev_input = torch.empty((self.B, nz, nx, int(S) + 1), dtype=torch.float32, device=self.dev)
+            (nz, nx), S = self.bv_size, int(self.bev_args[4])
+            self._bev_input = torch.empty((self.B, nz, nx, S + 1), dtype=torch.float32, device=self.dev)
         return self._bev_input
 
     def _write_maps(self, b):
@@ -592,11 +590,9 @@ class FramePipeline(FusedPipeline):
     def _map_buffers(self):
         """The step's height / density maps, allocated once (velo_step writes them off the chain)."""
         if getattr(self, "_maps", None) is None:
-            from . import bev as _bev
-            area, vs, _, _, S = self.bev_args
-            nx, nz = _bev.grid_divisions(area, vs)
+            (nz, nx), S = self.bv_size, int(self.bev_args[4])
             f64 = dict(dtype=torch.float64, device=self.dev)
-            self._maps = (torch.empty((self.B, int(S), nz, nx), **f64), torch.empty((self.B, nz, nx), **f64))
+            self._maps = (torch.empty((self.B, S, nz, nx), **f64), torch.empty((self.B, nz, nx), **f64))
         return self._maps
 
     def frame_step(self, points, point_offsets, planes, P, bev_feat, img_feat, point_counts=None):
