@@ -4,6 +4,7 @@ The product path has no fallback: if the HIP library is missing or cannot be
 loaded, every SHPL op raises ``ShplLibraryError``. Tensors cross the C ABI as
 raw device pointers plus the current HIP stream of the calling thread.
 """
+import collections
 import ctypes
 import os
 
@@ -117,11 +118,37 @@ class ShplPassCopy(ctypes.Structure):
                 ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int64), ("channels", ctypes.c_int64)]
 
 
-def pull_desc(dtype, src, src_stride, src_off, c_pool, pass_, pass_stride, pass_off, c_pass, mode, out, out_stride):
+def _addr(t, col=0):
+    """Device pointer of a tensor as an integer, `col` elements on (None for None)."""
+    return None if t is None else t.data_ptr() + (col and col * t.element_size())
+
+
+class Pull(collections.namedtuple("Pull", [n for n, _ in ShplPullDesc._fields_])):
+    """shpl_pull's twelve arguments after its csr, pointers as integers (None: NULL)."""
+
+    @classmethod
+    def of(cls, src, src_stride, src_off, c_pool, pass_, pass_stride, pass_off, c_pass, mode, out, out_stride,
+           out_col=0, dtype=None):
+        """From tensors, in shpl_pull's order. out_col: the pull writes out's rows from that column on (the pooled
+        half of a fused row: the one place its pointer is formed). dtype: out's, unless given."""
+        return cls(dtype_code(out) if dtype is None else dtype, _addr(src), src_stride, src_off, c_pool, _addr(pass_),
+                   pass_stride, pass_off, c_pass, mode, _addr(out, out_col), out_stride)
+
+    def args(self, direction, csr):
+        """The arguments of shpl_pull / _dense / _sparse / _once before the stream."""
+        p = ctypes.c_void_p  # (c_void_p(None) is NULL)
+        dtype, src, src_stride, src_off, c_pool, pass_, pass_stride, pass_off, c_pass, mode, out, out_stride = self
+        return (direction, dtype, csr.ref(), p(src), src_stride, src_off, c_pool, p(pass_), pass_stride, pass_off,
+                c_pass, mode, p(out), out_stride)
+
+    def desc(self):
+        """The ShplPullDesc of shpl_pull_pair."""
+        return ShplPullDesc(*self)
+
+
+def pull_desc(dtype, *fields):
     """A ShplPullDesc from tensors (the same argument order as shpl_pull after its csr)."""
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    return ShplPullDesc(dtype, p(src), src_stride, src_off, c_pool, p(pass_), pass_stride, pass_off, c_pass, mode,
-                        p(out), out_stride)
+    return Pull.of(*fields, dtype=dtype).desc()
 
 
 def _declare(lib):
@@ -252,6 +279,25 @@ def ptr(t):
     if t is None:
         return None
     return ctypes.c_void_p(t.data_ptr())
+
+
+def index_args(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_size, bv_size, stride, mval,
+               cell, pix, val):
+    """The twenty leading arguments shpl_build_index and shpl_build_index_buckets share."""
+    return (n_frames, ptr(point_offsets), ptr(point_counts), int(max_points), ptr(points),
+            F64 if points.dtype == torch.float64 else F32, ptr(voxels), I64 if voxels.dtype == torch.int64 else I32,
+            int(voxels.stride(0)), ptr(P), float(im_size[0]), float(im_size[1]), float(bv_size[0]), float(bv_size[1]),
+            float(stride[0]), float(stride[1]), ptr(mval), ptr(cell), ptr(pix), ptr(val))
+
+
+# Row-keyed pulls (shpl_csr.key_range: one launch per pull) are the default for batches of fewer than ROWS_FRAMES
+# frames with at most ROWS_MAX_KEYS destinations per frame: latency-bound layers (config 3). The range CSR carries
+# entry offsets in 24 bits: capacities under ROWS_MAX_CAP slots.
+ROWS_FRAMES, ROWS_MAX_KEYS, ROWS_MAX_CAP = 32, 65536, 1 << 24
+
+
+def row_pulls(n_frames, keys_per_frame, nnz_cap):
+    return n_frames < ROWS_FRAMES and keys_per_frame <= ROWS_MAX_KEYS and nnz_cap < ROWS_MAX_CAP
 
 
 def stream_of(device=None):

@@ -13,6 +13,7 @@ synchronises inside ``step``.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
@@ -20,6 +21,45 @@ import torch
 
 from . import _lib as L
 from .shpl_map import ShplMap, raise_for_bits
+
+
+def _mark(events, i, stream):
+    """The caller's timing event i, where it gave any."""
+    if events:
+        events[i].record(stream)
+
+
+class _Side(collections.namedtuple("_Side", "csr direction order n_keys pooled passed c_pool c_pass out dtype")):
+    """One direction of the layer: out = [passed input || pool(pooled input)] through csr (n_keys destinations per
+    frame); dtype: out's code. pooled / passed index a (bev, img) pair. The four pulls the pipeline issues over it,
+    and the pass-through half as a rider of the bucketed index build:"""
+
+    def concat(self, feats):
+        """The whole fused row."""
+        return L.Pull.of(feats[self.pooled], self.c_pool, 0, self.c_pool, feats[self.passed], self.c_pass, 0,
+                         self.c_pass, L.OUT_CONCAT, self.out, self.c_pass + self.c_pool, dtype=self.dtype)
+
+    def pass_only(self, feats):
+        """The pass-through half alone (no pooled channels: no index read)."""
+        return L.Pull.of(None, 0, 0, 0, feats[self.passed], self.c_pass, 0, self.c_pass, L.OUT_CONCAT, self.out,
+                         self.c_pass + self.c_pool, dtype=self.dtype)
+
+    def rider(self, feats):
+        """The same half as a shpl_pass_copy."""
+        return L.ShplPassCopy(self.dtype, feats[self.passed].data_ptr(), self.c_pass, self.out.data_ptr(),
+                              self.c_pass + self.c_pool, self.c_pass)
+
+    def pooled_half(self, feats):
+        """The pooled half alone (SHPL_OUT_POOL into the output rows' pooled columns)."""
+        return L.Pull.of(feats[self.pooled], self.c_pool, 0, self.c_pool, None, 0, 0, 0, L.OUT_POOL, self.out,
+                         self.c_pass + self.c_pool, out_col=self.c_pass, dtype=self.dtype)
+
+    def grad_add(self, grads, d):
+        """The gradient of the passed input: its own fused gradient's pass-through columns + the pull of the
+        other one's pooled columns (d and grads: (bev, img) pairs like feats)."""
+        w = self.c_pass + self.c_pool
+        return L.Pull.of(grads[self.pooled], w, self.c_pool, self.c_pass, grads[self.passed], w, 0, self.c_pass,
+                         L.OUT_ADD, d[self.passed], self.c_pass)
 
 
 class FusedPipeline:
@@ -39,9 +79,6 @@ class FusedPipeline:
     # kept zeros in step_overlapped: the sparse pass after the side stream's copy (True) or beside it (False;
     # disjoint columns, so it need not wait)
     KEEP_ZEROS_SERIAL = False
-    # row-keyed pulls (one launch per pull, shpl_csr.key_range) for batches under this many frames whose
-    # maps have at most ROWS_MAX_KEYS destinations per frame: latency-bound layers (config 3)
-    ROWS_FRAMES, ROWS_MAX_KEYS, ROWS_MAX_CAP = 32, 65536, 1 << 24
     # bucketed pixel-keyed CSRs with ent_col (per-column partials in the pulls; A/B of the identity-column form)
     PIXEL_COLS = False
     # split: the pooled half by shpl_pull_once (k_sparse's walk + the empty rows' zeros, one launch); False: the
@@ -86,9 +123,8 @@ class FusedPipeline:
         self.Wi = int(np.floor(im_size[0] / self.stride[0]))
         self.n_cells = self.B * self.Hb * self.Wb
         self.n_pix = self.B * self.Hi * self.Wi
-        if rows is None:
-            rows = (self.B < self.ROWS_FRAMES and max(self.Hb * self.Wb, self.Hi * self.Wi) <= self.ROWS_MAX_KEYS
-                    and self.N < self.ROWS_MAX_CAP)  # the range CSR's 24-bit entry offsets
+        if rows is None:  # row-keyed pulls (one launch per pull, shpl_csr.key_range) by L.row_pulls' rule
+            rows = L.row_pulls(self.B, max(self.Hb * self.Wb, self.Hi * self.Wi), self.N)
         self.rows = bool(rows)
         self.buckets = self.rows if buckets is None else bool(buckets) and self.rows
         # dual layers in step_overlapped: the cell-keyed sparse pass beside img_fused's stream
@@ -114,14 +150,19 @@ class FusedPipeline:
                               identity_cols=not with_col, head_k=head_k)
             self.img_fused = torch.empty((self.B, self.Hi, self.Wi, self.Ci + self.Cb), dtype=dtype,
                                          device=dev)
+        # the two directions, each written once below: (bev, img) -> bv_fused through the cell CSR in nnz order,
+        # and -> img_fused through the pixel CSR in (column, row) order
+        dt = L.dtype_code(self.bv_fused)
+        self._side = {"cell": _Side(self.csr, L.BY_CELL, L.ORDER_ENTRY, self.Hb * self.Wb, 1, 0, self.Ci, self.Cb,
+                                    self.bv_fused, dt)}
+        if dual:
+            self._side["pixel"] = _Side(self.pcsr, L.BY_PIXEL, L.ORDER_COL_ROW, self.Hi * self.Wi, 0, 1, self.Cb,
+                                        self.Ci, self.img_fused, dt)
         if live:
-            for c in (self.csr, self.pcsr if dual else None):
-                if c is not None:
-                    c.live_frames(self.frame_off, self.frame_nnz)
+            for s in self._side.values():
+                s.csr.live_frames(self.frame_off, self.frame_nnz)
         self.live = bool(live)
-        # kept zeros: bv_fused's pooled half is zero except at self.csr's cells (class docstring); only an
-        # eagerly issued full step makes it so
-        self._pooled_clean = False
+        self._pooled_clean = False  # kept zeros: the state comment above _keeps_zeros
         self._lib = L.lib()
         if self.buckets:
             # zeroed once: its frame barrier words start at zero (every call leaves them so)
@@ -133,31 +174,30 @@ class FusedPipeline:
                                      self.bkt_ws.numel(), self.err.data_ptr())
 
     # ------------------------------------------------------------------ steps
+    def _sides(self, which=("cell", "pixel")):
+        """{name: direction} of those named in `which` that this pipeline has, cell first."""
+        return {w: s for w, s in self._side.items() if w in which}
+
+    def _launch(self, symbol, side, pull):
+        """symbol(pull over side's CSR) on the current stream."""
+        L.check(getattr(self._lib, symbol)(*pull.args(side.direction, side.csr), L.stream_of(self.dev)), symbol)
+
     def build_index(self, points, voxels, point_offsets, P, mval=None, point_counts=None, pass_copies=None):
         """pass_copies (bucketed pipelines): (bev, img) -- the forward's pass-through halves ride the index
         launches (shpl_pass_copy)."""
         assert points.is_contiguous() and point_offsets.is_contiguous() and P.is_contiguous()
         assert voxels.stride(1) == 1, "voxel rows must be contiguous"
         st = L.stream_of(self.dev)
+        lead = L.index_args(self.B, point_offsets, point_counts, self.max_points, points, voxels, P, self.im_size,
+                            self.bv_size, self.stride, mval, self.cell, self.pix, self.val)
+        outs = (L.ptr(self.frame_nnz), L.ptr(self.frame_off), L.ptr(self.err), L.ptr(self.index_ws),
+                self.index_ws.numel())
         if self.buckets:
-            L.check(self._lib.shpl_build_index_buckets(
-                self.B, L.ptr(point_offsets), L.ptr(point_counts), self.max_points, L.ptr(points),
-                L.F64 if points.dtype == torch.float64 else L.F32, L.ptr(voxels),
-                L.I64 if voxels.dtype == torch.int64 else L.I32, int(voxels.stride(0)), L.ptr(P),
-                float(self.im_size[0]), float(self.im_size[1]), float(self.bv_size[0]),
-                float(self.bv_size[1]), self.stride[0], self.stride[1], L.ptr(mval), L.ptr(self.cell),
-                L.ptr(self.pix), L.ptr(self.val), L.ptr(self.frame_nnz), L.ptr(self.frame_off),
-                L.ptr(self.err), L.ptr(self.index_ws), self.index_ws.numel(), self.N, L.ptr(self.bkt_ws),
-                self.bkt_ws.numel(), *self._copy_riders(pass_copies), st), "shpl_build_index_buckets")
+            L.check(self._lib.shpl_build_index_buckets(*lead, *outs, self.N, L.ptr(self.bkt_ws), self.bkt_ws.numel(),
+                                                       *self._copy_riders(pass_copies), st),
+                    "shpl_build_index_buckets")
             return
-        L.check(self._lib.shpl_build_index(
-            self.B, L.ptr(point_offsets), L.ptr(point_counts), self.max_points, L.ptr(points),
-            L.F64 if points.dtype == torch.float64 else L.F32, L.ptr(voxels),
-            L.I64 if voxels.dtype == torch.int64 else L.I32, int(voxels.stride(0)), L.ptr(P),
-            float(self.im_size[0]), float(self.im_size[1]), float(self.bv_size[0]),
-            float(self.bv_size[1]), self.stride[0], self.stride[1], L.ptr(mval), L.ptr(self.cell),
-            L.ptr(self.pix), L.ptr(self.val), None, None, L.ptr(self.frame_nnz), L.ptr(self.frame_off),
-            L.ptr(self.err), L.ptr(self.index_ws), self.index_ws.numel(), st), "shpl_build_index")
+        L.check(self._lib.shpl_build_index(*lead, None, None, *outs, st), "shpl_build_index")
 
     # shpl_build_csr_path's builder (L.CSR_AUTO: chosen by batch shape; tests force the others)
     csr_path = L.CSR_AUTO
@@ -166,72 +206,44 @@ class FusedPipeline:
         if "cell" in which:
             # the kept zeros are known by self.csr's cells: a caller building it outside the steps below gets
             # the full step next (the steps themselves put the flag back)
-            self._pooled_clean = False
+            self.invalidate()
         st = L.stream_of(self.dev)
         if self.buckets:  # both CSRs from the index build's buckets, one launch
             L.check(self._lib.shpl_build_csr_buckets(
                 ctypes.byref(self.bkt), self.csr.ref() if "cell" in which else None,
                 self.pcsr.ref() if self.dual and "pixel" in which else None, st), "shpl_build_csr_buckets")
             return
-        args = (self.B, L.ptr(self.frame_off), L.ptr(self.frame_nnz))
-        if "cell" in which:
+        for s in self._sides(which).values():
             L.check(self._lib.shpl_build_csr_path(
-                L.CSR_FRAME if self.split else self.csr_path, L.BY_CELL, L.ORDER_ENTRY, *args, self.Hb * self.Wb, L.ptr(self.cell), None, L.ptr(self.val),
-                L.ptr(self.pix), self.csr.ref(), L.ptr(self.csr.ws), self.csr.ws.numel(), st), "shpl_build_csr")
-        if self.dual and "pixel" in which:
-            L.check(self._lib.shpl_build_csr_path(
-                self.csr_path, L.BY_PIXEL, L.ORDER_COL_ROW, *args, self.Hi * self.Wi, L.ptr(self.cell), None, L.ptr(self.val),
-                L.ptr(self.pix), self.pcsr.ref(), L.ptr(self.pcsr.ws), self.pcsr.ws.numel(), st),
-                "shpl_build_csr")
-
-    def _pull(self, fn, csr, direction, src, cs, pass_, cp, out, st):
-        L.check(fn(direction, L.dtype_code(out), csr.ref(), L.ptr(src), cs, 0, cs, L.ptr(pass_), cp, 0, cp,
-                   L.OUT_CONCAT, L.ptr(out), cs + cp, st), "shpl_pull")
+                L.CSR_FRAME if self.split else self.csr_path, s.direction, s.order, self.B, L.ptr(self.frame_off),
+                L.ptr(self.frame_nnz), s.n_keys, L.ptr(self.cell), None, L.ptr(self.val), L.ptr(self.pix), s.csr.ref(),
+                L.ptr(s.csr.ws), s.csr.ws.numel(), st), "shpl_build_csr_path")
 
     def layer_dense(self, bev, img, which=("cell", "pixel")):
         """Streaming half of the layer (needs no M): pass-through copy + zeros.
         Row-keyed pulls (self.rows) have no separate streaming half; split: the pass-through copy alone."""
         if self.split:
             self._pass_copies(bev, img, ("cell",))
-            return
-        if self.rows:
-            return
-        st = L.stream_of(self.dev)
-        if "cell" in which:
-            self._pull(self._lib.shpl_pull_dense, self.csr, L.BY_CELL, img, self.Ci, bev, self.Cb, self.bv_fused,
-                       st)
-        if self.dual and "pixel" in which:
-            self._pull(self._lib.shpl_pull_dense, self.pcsr, L.BY_PIXEL, bev, self.Cb, img, self.Ci,
-                       self.img_fused, st)
+        elif not self.rows:
+            for s in self._sides(which).values():
+                self._launch("shpl_pull_dense", s, s.concat((bev, img)))
 
-    def _sparse(self, args):
-        """shpl_pull_sparse(*args) on the current stream; with row-keyed CSRs the
-        whole pull (shpl_pull's one launch)."""
-        if self.rows:
-            L.check(self._lib.shpl_pull(*args, L.stream_of(self.dev)), "shpl_pull")
-            return
-        L.check(self._lib.shpl_pull_sparse(*args, L.stream_of(self.dev)), "shpl_pull_sparse")
+    def _sparse(self, side, pull):
+        """shpl_pull_sparse on the current stream; with row-keyed CSRs the whole pull (shpl_pull's one launch)."""
+        self._launch("shpl_pull" if self.rows else "shpl_pull_sparse", side, pull)
 
-    def _concat_args(self, csr, direction, src, cs, pass_, cp, out):
-        return (direction, L.dtype_code(out), csr.ref(), L.ptr(src), cs, 0, cs, L.ptr(pass_), cp, 0, cp,
-                L.OUT_CONCAT, L.ptr(out), cs + cp)
-
-    def _pull_pair(self, cell_desc, pix_desc):
-        L.check(self._lib.shpl_pull_pair(self.csr.ref(), ctypes.byref(cell_desc) if cell_desc else None,
-                                         self.pcsr.ref() if self.dual else None,
-                                         ctypes.byref(pix_desc) if pix_desc else None,
-                                         L.stream_of(self.dev)), "shpl_pull_pair")
+    def _pull_pair(self, pulls):
+        """pulls: {"cell" / "pixel": L.Pull}, both in one launch (either may be missing)."""
+        descs = {k: p.desc() for k, p in pulls.items()}
+        ref = lambda k: ctypes.byref(descs[k]) if k in descs else None  # noqa: E731
+        L.check(self._lib.shpl_pull_pair(self.csr.ref(), ref("cell"), self.pcsr.ref() if self.dual else None,
+                                         ref("pixel"), L.stream_of(self.dev)), "shpl_pull_pair")
 
     def _copy_riders(self, pass_copies):
         if pass_copies is None:
             return None, None
-        bev, img = pass_copies
-        dt = L.dtype_code(self.bv_fused)
-        cell = L.ShplPassCopy(dt, bev.data_ptr(), self.Cb, self.bv_fused.data_ptr(), self.Cb + self.Ci, self.Cb)
-        pix = L.ShplPassCopy(dt, img.data_ptr(), self.Ci, self.img_fused.data_ptr(), self.Ci + self.Cb,
-                             self.Ci) if self.dual else None
-        self._riders = (cell, pix)  # kept alive until the call returns
-        return ctypes.byref(cell), (ctypes.byref(pix) if pix is not None else None)
+        self._riders = [s.rider(pass_copies) for s in self._side.values()]  # kept alive until the call returns
+        return [ctypes.byref(r) for r in self._riders] + [None] * (2 - len(self._riders))
 
     riders = True  # bucketed step_overlapped: pass-through halves ride the index launches (False: k_dense copies)
 
@@ -244,46 +256,24 @@ class FusedPipeline:
     def _pass_copies(self, bev, img, which=("cell", "pixel")):
         """The forward's pass-through halves alone (shpl_pull_dense over no pooled channels): bv_fused[..., :Cb]
         = bev, img_fused[..., :Ci] = img; they need no index."""
-        st = L.stream_of(self.dev)
-        dt = L.dtype_code(self.bv_fused)
-        if "cell" in which:
-            L.check(self._lib.shpl_pull_dense(L.BY_CELL, dt, self.csr.ref(), None, 0, 0, 0, L.ptr(bev), self.Cb, 0,
-                                              self.Cb, L.OUT_CONCAT, L.ptr(self.bv_fused), self.Cb + self.Ci, st),
-                    "shpl_pull_dense")
-        if self.dual and "pixel" in which:
-            L.check(self._lib.shpl_pull_dense(L.BY_PIXEL, dt, self.pcsr.ref(), None, 0, 0, 0, L.ptr(img), self.Ci, 0,
-                                              self.Ci, L.OUT_CONCAT, L.ptr(self.img_fused), self.Ci + self.Cb, st),
-                    "shpl_pull_dense")
+        for s in self._sides(which).values():
+            self._launch("shpl_pull_dense", s, s.pass_only((bev, img)))
 
-    def _pooled_descs(self, bev, img, which=("cell", "pixel")):
-        """The forward pair's pooled halves (SHPL_OUT_POOL into the output rows' pooled columns)."""
-        dt = L.dtype_code(self.bv_fused)
-        esz = self.bv_fused.element_size()
-        cell = pix = None
-        if "cell" in which:
-            cell = L.pull_desc(dt, img, self.Ci, 0, self.Ci, None, 0, 0, 0, L.OUT_POOL, self.bv_fused,
-                               self.Cb + self.Ci)
-            cell.out += self.Cb * esz
-        if self.dual and "pixel" in which:
-            pix = L.pull_desc(dt, bev, self.Cb, 0, self.Cb, None, 0, 0, 0, L.OUT_POOL, self.img_fused,
-                              self.Ci + self.Cb)
-            pix.out += self.Ci * esz
-        return cell, pix
+    def _pooled_pulls(self, bev, img, which=("cell", "pixel")):
+        """The forward pair's pooled halves."""
+        return {w: s.pooled_half((bev, img)) for w, s in self._sides(which).items()}
 
     def layer_sparse(self, bev, img, which=("cell", "pixel")):
         """Pooled rows, after layer_dense and build_csr (with buckets: the pass-through halves and
         then both pooled halves in one launch)."""
         if self.buckets:
             self._pass_copies(bev, img, which)
-            self._pull_pair(*self._pooled_descs(bev, img, which))
-            return
-        if self.split:
+            self._pull_pair(self._pooled_pulls(bev, img, which))
+        elif self.split:
             self._pooled_half(img)
-            return
-        if "cell" in which:
-            self._sparse(self._concat_args(self.csr, L.BY_CELL, img, self.Ci, bev, self.Cb, self.bv_fused))
-        if self.dual and "pixel" in which:
-            self._sparse(self._concat_args(self.pcsr, L.BY_PIXEL, bev, self.Cb, img, self.Ci, self.img_fused))
+        else:
+            for s in self._sides(which).values():
+                self._sparse(s, s.concat((bev, img)))
 
     def layer(self, bev, img):
         """bv_fused = [bev || pool(img)] (+ img_fused = [img || trans(bev)] if dual)."""
@@ -291,6 +281,14 @@ class FusedPipeline:
         self.layer_sparse(bev, img)
 
     # ------------------------------------------------------------------ kept zeros
+    # _pooled_clean says that bv_fused's pooled half is zero except at self.csr's cells (class docstring). Its
+    # transitions, each written once:
+    #   dirty -> clean   a full step of a pipeline that keeps zeros, issued eagerly (_step_done(False)); under
+    #                    stream capture nothing ran, so a dirty pipeline captures the full form and stays dirty
+    #   clean -> clean   the kept-zeros step (_clean_step: clear, index, CSR, copy, sparse, then _step_done(True)),
+    #                    eager or captured
+    #   any   -> dirty   invalidate(): the caller's own, build_csr's over the cell CSR (the steps call it too, and
+    #                    put the flag back through _step_done) and check()'s when a step was flagged
     def _keeps_zeros(self):
         """The pipelines whose steps may take the kept-zeros form."""
         return self.KEEP_ZEROS and not (self.dual or self.split or self.rows or self.live)
@@ -304,33 +302,48 @@ class FusedPipeline:
         L.check(self._lib.shpl_pull_clear(L.dtype_code(self.bv_fused), self.csr.ref(), self.Ci, L.ptr(self.bv_fused),
                                           self.Cb + self.Ci, self.Cb, L.stream_of(self.dev)), "shpl_pull_clear")
 
-    def _full_step_done(self):
-        """After a full step (every element written, self.csr the pooled cells): clean only when it really ran
-        -- a dirty pipeline under stream capture captures the full form and stays dirty."""
-        self._pooled_clean = self._keeps_zeros() and not torch.cuda.is_current_stream_capturing()
+    def _step_done(self, was_clean):
+        """After a step that wrote every element or kept the zeros, self.csr the pooled cells."""
+        self._pooled_clean = self._keeps_zeros() and (was_clean or not torch.cuda.is_current_stream_capturing())
+
+    def _clean_step(self, index, bev, img, side=None, events=None):
+        """The kept-zeros step: the previous step's cells cleared, the index chain, the pass-through copy and the
+        sparse pass. side: the copy runs there instead, issued first; the two streams write disjoint columns of
+        bv_fused, so the sparse pass waits for the copy only with KEEP_ZEROS_SERIAL."""
+        main = torch.cuda.current_stream(self.dev)
+        if side is not None:
+            with torch.cuda.stream(side):
+                _mark(events, 0, side)
+                self._pass_copies(bev, img, ("cell",))
+                _mark(events, 1, side)
+        self._clear_pooled()
+        self.build_index(*index)
+        self.build_csr(("cell",))
+        if side is None:
+            self._pass_copies(bev, img, ("cell",))
+        elif self.KEEP_ZEROS_SERIAL:
+            main.wait_stream(side)
+        _mark(events, 2, main)
+        self.layer_sparse(bev, img, ("cell",))
+        if side is not None:
+            main.wait_stream(side)
+        _mark(events, 3, main)
+        self._step_done(True)
 
     def step(self, points, voxels, point_offsets, P, bev, img, mval=None):
         if self._keeps_zeros() and self._pooled_clean:
-            self._clear_pooled()
-            self.build_index(points, voxels, point_offsets, P, mval)
-            self.build_csr()
-            self._pass_copies(bev, img, ("cell",))
-            self.layer_sparse(bev, img, ("cell",))
-            self._pooled_clean = True
+            self._clean_step((points, voxels, point_offsets, P, mval), bev, img)
             return
         self.build_index(points, voxels, point_offsets, P, mval)
         self.build_csr()
         self.layer(bev, img)
-        self._full_step_done()
+        self._step_done(False)
 
     def _pooled_half(self, img):
         """split: bv_fused[..., Cb:] = pool(img), every row written once (zeros where no entry lands): the
-        row-keyed pull over the cell CSR's key ranges (SHPL_OUT_POOL into the pooled columns)."""
-        esz = self.bv_fused.element_size()
-        out = ctypes.c_void_p(self.bv_fused.data_ptr() + self.Cb * esz)
-        fn = self._lib.shpl_pull_once if self.SPLIT_ONCE else self._lib.shpl_pull
-        L.check(fn(L.BY_CELL, L.dtype_code(self.bv_fused), self.csr.ref(), L.ptr(img), self.Ci, 0,
-                   self.Ci, None, 0, 0, 0, L.OUT_POOL, out, self.Cb + self.Ci, L.stream_of(self.dev)), "shpl_pull")
+        row-keyed pull over the cell CSR's key ranges."""
+        side = self._side["cell"]
+        self._launch("shpl_pull_once" if self.SPLIT_ONCE else "shpl_pull", side, side.pooled_half((None, img)))
 
     # split: the pooled half after the copy instead of beside it -- each alone at its own rate rather than
     # the two sharing HBM, and the step capturable in a graph (the chain only has to finish under the copy,
@@ -350,29 +363,26 @@ class FusedPipeline:
             chain = main
         else:
             chain.wait_stream(main)
+
+        def pooled_half():
+            self._pooled_half(img)
+            _mark(events, 3, chain)
         # the chain is issued (and, in a captured graph, its nodes created) first: its first launch is
         # dispatched before the copy's workgroups fill the chip
         with torch.cuda.stream(chain):
-            if events:
-                events[2].record(chain)
+            _mark(events, 2, chain)
             self.build_index(points, voxels, point_offsets, P)
             self.build_csr(("cell",))
             if not self.SPLIT_SERIAL:
-                self._pooled_half(img)
-                if events:
-                    events[3].record(chain)
+                pooled_half()
         with torch.cuda.stream(side):
-            if events:
-                events[0].record(side)
+            _mark(events, 0, side)
             self._pass_copies(bev, img, ("cell",))
-            if events:
-                events[1].record(side)
+            _mark(events, 1, side)
         if self.SPLIT_SERIAL:
             with torch.cuda.stream(chain):
                 chain.wait_stream(side)
-                self._pooled_half(img)
-                if events:
-                    events[3].record(chain)
+                pooled_half()
         main.wait_stream(side)
         if chain is not main:
             main.wait_stream(chain)
@@ -386,61 +396,36 @@ class FusedPipeline:
         `events` (4 timing events) bracket the dense and the sparse launches.
         A clean kept-zeros pipeline (class docstring): the copy alone on `side`, the clear, the index chain
         and the sparse pass on the current stream."""
+        main = torch.cuda.current_stream(self.dev)
         if self.buckets:
             # one stream: index + buckets with the pass-through halves riding its two launches, both CSRs
             # (1 launch), both pooled halves (1 launch). (The copies on `side` beside the index chain instead
             # cost 20-30 us of cross-queue waits per graph replay at config 3: profiles/r03_bpull_ab.log.)
-            main = torch.cuda.current_stream(self.dev)
-            if events:  # no streaming half of its own: the forward bracket [2, 3) is the whole forward
-                for e in events[:3]:
-                    e.record(main)
+            for i in range(3):  # no streaming half of its own: the forward bracket [2, 3) is the whole forward
+                _mark(events, i, main)
             riders = self.copy_riders_ok(bev, img)
             if not riders:
                 self._pass_copies(bev, img)
             self.build_index(points, voxels, point_offsets, P, mval, pass_copies=(bev, img) if riders else None)
             self.build_csr()
-            self._pull_pair(*self._pooled_descs(bev, img))
-            if events:
-                events[3].record(main)
+            self._pull_pair(self._pooled_pulls(bev, img))
+            _mark(events, 3, main)
             return
-        main = torch.cuda.current_stream(self.dev)
         side.wait_stream(main)            # inputs / previous step done
         if self._keeps_zeros() and self._pooled_clean:
-            # kept zeros: the pass-through copy alone on `side`; here the previous step's cells cleared, then
-            # the index chain and the sparse pass. The two streams write disjoint columns of bv_fused, so the
-            # sparse pass waits for the copy only with KEEP_ZEROS_SERIAL.
-            with torch.cuda.stream(side):
-                if events:
-                    events[0].record(side)
-                self._pass_copies(bev, img, ("cell",))
-                if events:
-                    events[1].record(side)
-            self._clear_pooled()
-            self.build_index(points, voxels, point_offsets, P, mval)
-            self.build_csr(("cell",))
-            if self.KEEP_ZEROS_SERIAL:
-                main.wait_stream(side)
-            if events:
-                events[2].record(main)
-            self.layer_sparse(bev, img, ("cell",))
-            main.wait_stream(side)
-            if events:
-                events[3].record(main)
-            self._pooled_clean = True
+            self._clean_step((points, voxels, point_offsets, P, mval), bev, img, side, events)
             return
         split = self.dual and side2 is not None
         # dual layers: the cell-keyed sparse pass needs only bv_fused's stream, so it runs
         # beside img_fused's stream (the gathers overlap the second dense pass)
         cell_streamed = torch.cuda.Event() if split and not self.rows and self.interleave else None
         with torch.cuda.stream(side):
-            if events:
-                events[0].record(side)
+            _mark(events, 0, side)
             self.layer_dense(bev, img, ("cell",))
             if cell_streamed is not None:
                 cell_streamed.record(side)
             self.layer_dense(bev, img, ("pixel",))
-            if events:
-                events[1].record(side)
+            _mark(events, 1, side)
         self.build_index(points, voxels, point_offsets, P, mval)
         if split:
             side2.wait_stream(main)       # M built
@@ -453,15 +438,13 @@ class FusedPipeline:
             main.wait_event(cell_streamed)  # the cell-keyed sparse pass overwrites rows bv_fused's stream wrote
         else:
             main.wait_stream(side)        # sparse overwrites rows the dense pass wrote
-        if events:
-            events[2].record(main)
+        _mark(events, 2, main)
         self.layer_sparse(bev, img, ("cell",) if split else ("cell", "pixel"))
         if split:
             main.wait_stream(side2)
         main.wait_stream(side)
-        if events:
-            events[3].record(main)
-        self._full_step_done()
+        _mark(events, 3, main)
+        self._step_done(False)
 
     def backward(self, g_bv, g_img, d_bev, d_img, side2=None):
         """TF gradient of the dual layer with the concat split and add_n fused:
@@ -472,26 +455,18 @@ class FusedPipeline:
         side2: the d_img pull runs there, beside the d_bev pull."""
         assert self.dual
         main = torch.cuda.current_stream(self.dev)
-        w = self.Cb + self.Ci
-        dt = L.dtype_code(d_bev)
+        cell, pix = self._side["cell"], self._side["pixel"]
+        pulls = {w: s.grad_add((g_bv, g_img), (d_bev, d_img)) for w, s in self._side.items()}
         if self.buckets:  # both gradient pulls, one launch, current stream
-            self._pull_pair(L.pull_desc(dt, g_img, w, self.Ci, self.Cb, g_bv, w, 0, self.Cb, L.OUT_ADD, d_bev,
-                                        self.Cb),
-                            L.pull_desc(dt, g_bv, w, self.Cb, self.Ci, g_img, w, 0, self.Ci, L.OUT_ADD, d_img,
-                                        self.Ci))
+            self._pull_pair(pulls)
             return
-        cell = (L.BY_CELL, dt, self.csr.ref(), L.ptr(g_img), w, self.Ci, self.Cb, L.ptr(g_bv), w, 0, self.Cb,
-                L.OUT_ADD, L.ptr(d_bev), self.Cb)
-        pix = (L.BY_PIXEL, dt, self.pcsr.ref(), L.ptr(g_bv), w, self.Cb, self.Ci, L.ptr(g_img), w, 0, self.Ci,
-               L.OUT_ADD, L.ptr(d_img), self.Ci)
-        pst = side2 if side2 is not None else main
         if side2 is not None:
             side2.wait_stream(main)       # forward done
-        L.check(self._lib.shpl_pull(*cell, L.stream_of(self.dev)), "shpl_pull")
-        with torch.cuda.stream(pst):
+        self._launch("shpl_pull", cell, pulls["cell"])
+        with torch.cuda.stream(side2 if side2 is not None else main):
             if not self.rows:
-                L.check(self._lib.shpl_pull_dense(*pix, L.stream_of(self.dev)), "shpl_pull_dense")
-            self._sparse(pix)
+                self._launch("shpl_pull_dense", pix, pulls["pixel"])
+            self._sparse(pix, pulls["pixel"])
         if side2 is not None:
             main.wait_stream(side2)
 
@@ -504,7 +479,7 @@ class FusedPipeline:
         bits = int(self.err.item()) & 0xFFFFFFFF
         if not bits:
             return
-        self._pooled_clean = False  # a flagged step's CSR need not name the cells it wrote: the full step next
+        self.invalidate()  # a flagged step's CSR need not name the cells it wrote: the full step next
         self.err.zero_()
         if bits & L.EBIT_BARRIER and self.buckets:
             L.bucket_workspace_reset(self.B, self.bkt_ws, self.dev)
@@ -548,7 +523,7 @@ class FramePipeline(FusedPipeline):
         self.maps = maps
         self.bev_ws = L.workspace(L.ws_bytes("shpl_bev", self.N, num_slices), self.dev)
         self.bev = None
-        self._velo_ws = None
+        self._maps = self._bev_input = self._velo_ws = self._velo_pts = None  # made on first use (_buffer)
 
     # velo_step with a side stream: where the BEV maps are written (shpl_bev_maps) -- "chain": on the
     # index chain after the CSR, beside the end of the streaming pass (step 2.66-2.67 ms); "stream": on the
@@ -571,29 +546,28 @@ class FramePipeline(FusedPipeline):
                                          maps=want and self.maps_form == "f64", ws=self.bev_ws,
                                          point_counts=point_counts)
         if want and self.maps_form == "bev_input":
-            self.bev.write_bev_input(self._input_buffer())
+            self.bev.write_bev_input(self._buffer("_bev_input"))
         return self.bev
 
-    def _input_buffer(self):
-        """The step's BEV input tensor [F,nz,nx,S+1] f32 (maps_form "bev_input"), allocated once."""
-        if getattr(self, "_bev_input", None) is None:
+    def _buffer(self, name, frames=None):
+        """The buffers made on first use, each allocated once: "_maps", the height / density maps ([F,S,nz,nx],
+        [F,nz,nx]) f64 that velo_step writes off the chain; "_bev_input", the BEV input [F,nz,nx,S+1] f32 (maps_form
+        "bev_input"); "_velo_ws" and "_velo_pts", shpl_velo_to_cam's workspace for `frames` and its [N,3] f64 clouds."""
+        if getattr(self, name) is None:
             (nz, nx), S = self.bv_size, int(self.bev_args[4])
-            self._bev_input = torch.empty((self.B, nz, nx, S + 1), dtype=torch.float32, device=self.dev)
-        return self._bev_input
+            empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.dev)  # noqa: E731
+            setattr(self, name, {
+                "_maps": lambda: (empty((self.B, S, nz, nx), torch.float64), empty((self.B, nz, nx), torch.float64)),
+                "_bev_input": lambda: empty((self.B, nz, nx, S + 1), torch.float32),
+                "_velo_ws": lambda: L.workspace(L.ws_bytes("shpl_velo", frames.n_frames, frames.max_points), self.dev),
+                "_velo_pts": lambda: empty((max(self.N, 1), 3), torch.float64)}[name]())
+        return getattr(self, name)
 
     def _write_maps(self, b):
         if self.maps_form == "bev_input":
-            b.write_bev_input(self._input_buffer())
+            b.write_bev_input(self._buffer("_bev_input"))
         else:
-            b.write_maps(*self._map_buffers(), zero=True)
-
-    def _map_buffers(self):
-        """The step's height / density maps, allocated once (velo_step writes them off the chain)."""
-        if getattr(self, "_maps", None) is None:
-            (nz, nx), S = self.bv_size, int(self.bev_args[4])
-            f64 = dict(dtype=torch.float64, device=self.dev)
-            self._maps = (torch.empty((self.B, S, nz, nx), **f64), torch.empty((self.B, nz, nx), **f64))
-        return self._maps
+            b.write_maps(*self._buffer("_maps"), zero=True)
 
     def frame_step(self, points, point_offsets, planes, P, bev_feat, img_feat, point_counts=None):
         b = self.build_bev(points, point_offsets, planes, point_counts)
@@ -607,75 +581,56 @@ class FramePipeline(FusedPipeline):
         side: a stream for the layer's streaming half (it needs no index), run beside
         the index chain. events: 9 timing events (dense start/end on `side`; then
         velo, bev, index, csr boundaries, sparse start/end on the current stream)."""
-        if self.dense_after not in self.DENSE_AFTER:
-            raise ValueError(f"dense_after must be one of {self.DENSE_AFTER}, not {self.dense_after!r}")
-        if self.maps_after not in self.MAPS_AFTER:
-            raise ValueError(f"maps_after must be one of {self.MAPS_AFTER}, not {self.maps_after!r}")
-        if self.maps_form not in self.MAPS_FORMS:
-            raise ValueError(f"maps_form must be one of {self.MAPS_FORMS}, not {self.maps_form!r}")
-        if side is not None:
-            # the 1.7 GB of f64 maps (64 frames) are written on `side` after the streaming pass, from the
-            # voxelizer's sorted words (shpl_bev_maps): off the index chain, and streaming after the
-            # stream instead of beside it
-            main = torch.cuda.current_stream(self.dev)
-            dense_done, bev_done = torch.cuda.Event(), torch.cuda.Event()
-
-            def dense():  # the streaming half on `side`, after what `main` has issued so far
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    if events:
-                        events[0].record(side)
-                    self.layer_dense(bev_feat, img_feat)
-                    dense_done.record(side)
-                    if events:
-                        events[1].record(side)
-
-            at = self.dense_after
-            if at == "start":
-                dense()
-            if events:
-                events[2].record(main)
+        for name, allowed in (("dense_after", self.DENSE_AFTER), ("maps_after", self.MAPS_AFTER),
+                              ("maps_form", self.MAPS_FORMS)):
+            if getattr(self, name) not in allowed:
+                raise ValueError(f"{name} must be one of {allowed}, not {getattr(self, name)!r}")
+        if side is None:
             self._velo(frames)
-            if events:
-                events[3].record(main)
-            if at == "velo":
-                dense()
-            b = self.build_bev(self.velo.points, frames.point_offsets, frames.planes, self.velo.counts,
-                               maps=False)
-            bev_done.record(main)
-            if at == "bev":
-                dense()
-            if self.maps and self.maps_after == "stream":
-                side.wait_event(bev_done)
-                with torch.cuda.stream(side):
-                    self._write_maps(b)
-            if events:
-                events[4].record(main)
-            self.build_index(b.pts_in_voxel, b.voxel_indices, frames.point_offsets, frames.P2,
-                             point_counts=b.frame_nvox)
-            if events:
-                events[5].record(main)
-            self.build_csr()
-            if events:
-                events[6].record(main)
-            if at == "csr":
-                dense()
-            if self.maps and self.maps_after == "chain":
-                self._write_maps(b)
-            main.wait_event(dense_done)  # the sparse pass overwrites rows the streaming pass wrote
-            if events:
-                events[7].record(main)
-            self.layer_sparse(bev_feat, img_feat)
-            if events:
-                events[8].record(main)
-            main.wait_stream(side)  # the maps
+            self.frame_step(self.velo.points, frames.point_offsets, frames.planes, frames.P2, bev_feat, img_feat,
+                            point_counts=self.velo.counts)
             return
+        # the same chain (_velo, build_bev, build_index, build_csr, the layer's two halves) with the streaming half
+        # on `side`. The 1.7 GB of f64 maps (64 frames) are written after the streaming pass, from the voxelizer's
+        # sorted words (shpl_bev_maps): off the index chain, and streaming after the stream instead of beside it
+        main = torch.cuda.current_stream(self.dev)
+        dense_done, bev_done = torch.cuda.Event(), torch.cuda.Event()
+
+        def dense_at(stage):  # the streaming half on `side` if it starts here, after what `main` has issued so far
+            if stage != self.dense_after:
+                return
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                _mark(events, 0, side)
+                self.layer_dense(bev_feat, img_feat)
+                dense_done.record(side)
+                _mark(events, 1, side)
+
+        dense_at("start")
+        _mark(events, 2, main)
         self._velo(frames)
-        self.frame_step(self.velo.points, frames.point_offsets, frames.planes, frames.P2, bev_feat, img_feat,
-                        point_counts=self.velo.counts)
+        _mark(events, 3, main)
+        dense_at("velo")
+        b = self.build_bev(self.velo.points, frames.point_offsets, frames.planes, self.velo.counts, maps=False)
+        bev_done.record(main)
+        dense_at("bev")
+        if self.maps and self.maps_after == "stream":
+            side.wait_event(bev_done)
+            with torch.cuda.stream(side):
+                self._write_maps(b)
+        _mark(events, 4, main)
+        self.build_index(b.pts_in_voxel, b.voxel_indices, frames.point_offsets, frames.P2, point_counts=b.frame_nvox)
+        _mark(events, 5, main)
+        self.build_csr()
+        _mark(events, 6, main)
+        dense_at("csr")
+        if self.maps and self.maps_after == "chain":
+            self._write_maps(b)
+        main.wait_event(dense_done)  # the sparse pass overwrites rows the streaming pass wrote
+        _mark(events, 7, main)
+        self.layer_sparse(bev_feat, img_feat)
+        _mark(events, 8, main)
+        main.wait_stream(side)  # the maps
 
     def _velo(self, frames):
-        if self._velo_ws is None:
-            self._velo_ws = L.workspace(L.ws_bytes("shpl_velo", frames.n_frames, frames.max_points), self.dev)
-            self._velo_pts = torch.empty((max(self.N, 1), 3), dtype=torch.float64, device=self.dev)
-        self.velo = frames.point_clouds(ws=self._velo_ws, out=self._velo_pts)
+        self.velo = frames.point_clouds(ws=self._buffer("_velo_ws", frames), out=self._buffer("_velo_pts"))

@@ -82,10 +82,8 @@ class ShplMap:
         raise_for_bits(self.error_bits())
 
     # ------------------------------------------------------------------ CSR
-    # Row-keyed pulls (shpl_csr.key_range: one launch per pull) for maps of fewer
-    # than ROWS_FRAMES frames with at most ROWS_MAX_KEYS destinations per frame;
+    # Row-keyed pulls (shpl_csr.key_range: one launch per pull) by L.row_pulls' rule;
     # ROW_PULLS = True / False forces the form (tests).
-    ROWS_FRAMES, ROWS_MAX_KEYS, ROWS_MAX_CAP = 32, 65536, 1 << 24
     ROW_PULLS = None
     # shpl_build_csr_path's builder for the flat CSRs (L.CSR_AUTO: the library's choice by batch shape)
     CSR_PATH = L.CSR_AUTO
@@ -104,9 +102,7 @@ class ShplMap:
         n_keys = self.n_cells if direction == L.BY_CELL else self.n_pix
         rows = self.ROW_PULLS
         if rows is None:
-            # (the range CSR carries entry offsets in 24 bits: capacities under 2^24 slots)
-            rows = (self.n_frames < self.ROWS_FRAMES and n_keys // max(self.n_frames, 1) <= self.ROWS_MAX_KEYS
-                    and self.nnz_cap < self.ROWS_MAX_CAP)
+            rows = L.row_pulls(self.n_frames, n_keys // max(self.n_frames, 1), self.nnz_cap)
         c = L.Csr(n_keys, self.nnz_cap, self.device, with_col=direction == L.BY_PIXEL, key_range=rows)
         L.check(L.lib().shpl_build_csr_path(self.CSR_PATH, direction, order, self.n_frames, L.ptr(self.frame_off),
                                             L.ptr(self.frame_nnz), n_keys // self.n_frames,
@@ -187,8 +183,8 @@ def pull(smap, direction, order, src, src_stride, src_off, c_pool, out, out_stri
     fn, name = {None: (L.lib().shpl_pull, "shpl_pull"), "dense": (L.lib().shpl_pull_dense, "shpl_pull_dense"),
                 "sparse": (L.lib().shpl_pull_sparse, "shpl_pull_sparse"),
                 "once": (L.lib().shpl_pull_once, "shpl_pull_once")}[part]
-    L.check(fn(direction, L.dtype_code(out), c.ref(), L.ptr(src), src_stride, src_off, c_pool, L.ptr(pass_),
-               pass_stride, pass_off, c_pass, mode, L.ptr(out), out_stride, L.stream_of(out.device)), name)
+    args = L.Pull.of(src, src_stride, src_off, c_pool, pass_, pass_stride, pass_off, c_pass, mode, out, out_stride)
+    L.check(fn(*args.args(direction, c), L.stream_of(out.device)), name)
     return out
 
 
@@ -340,16 +336,10 @@ def build_index_batch(points, voxels, point_offsets, P, im_size, bv_size, stride
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     if ws is None:
         ws = L.workspace(L.index_ws_bytes(n_frames, max_points), dev)
-    pdt = L.F64 if points.dtype == torch.float64 else L.F32
-    vit = L.I64 if voxels.dtype == torch.int64 else L.I32
-    L.check(L.lib().shpl_build_index(n_frames, L.ptr(point_offsets), L.ptr(point_counts), int(max_points),
-                                     L.ptr(points),
-                                     pdt, L.ptr(voxels), vit, int(voxels.stride(0)), L.ptr(P),
-                                     float(im_size[0]), float(im_size[1]), float(bv_size[0]),
-                                     float(bv_size[1]), s_img, s_bv, L.ptr(mval), L.ptr(cell),
-                                     L.ptr(pix), L.ptr(val), L.ptr(mij), L.ptr(flip),
-                                     L.ptr(frame_nnz), L.ptr(frame_off), L.ptr(err), L.ptr(ws),
-                                     ws.numel(), L.stream_of(dev)), "shpl_build_index")
+    lead = L.index_args(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_size, bv_size,
+                        stride, mval, cell, pix, val)
+    L.check(L.lib().shpl_build_index(*lead, L.ptr(mij), L.ptr(flip), L.ptr(frame_nnz), L.ptr(frame_off), L.ptr(err),
+                                     L.ptr(ws), ws.numel(), L.stream_of(dev)), "shpl_build_index")
     smap = ShplMap(cell, None, val, pix, N, n_frames * bhq * bwq, n_frames * hq * wq, N, dev,
                    frame_off=frame_off, frame_nnz=frame_nnz, n_frames=n_frames, err=err)
     return IndexBatch(smap, mij, flip, frame_nnz, frame_off, n_frames, (bhq, bwq), (hq, wq))

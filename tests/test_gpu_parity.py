@@ -1194,20 +1194,29 @@ def test_velodyne_to_fused_layer_pipeline(kitti_dir):
     torch.cuda.synchronize()
     assert int(pl.err.item()) == 0 and int(pl.bev.err.item()) == 0
     out, iout = _np(pl.bv_fused), _np(pl.img_fused)
+    for f, (hm, nnz, eb, ei) in enumerate(velodyne_layer_oracle(g, bev, img, im_size, stride)):
+        np.testing.assert_array_equal(_np(pl.bev.height_maps[f]), hm)
+        assert int(_np(pl.frame_nnz)[f]) == nnz > 0
+        _close_and_exact(out[f:f + 1], eb)
+        _close_and_exact(iout[f:f + 1], ei)
+
+
+def velodyne_layer_oracle(g, bev, img, im_size, stride):
+    """The oracle chain over the kitti_dir fixture's two frames (7, and 8 flipped) and the features bev / img: per
+    frame (height maps, entries of M, bv_fused, img_fused)."""
     clouds = [g["7_point_cloud"], g["8_flip_point_cloud"]]
     planes = [g["7_ground_plane"], g["8_flip_ground_plane"]]
     Ps = [g["7_p2"], g["8_flip_p2"]]
+    res = []
     for f in range(2):
         hm, dm, vox, upts = orc.bev_slices(clouds[f], planes[f], synth.AREA_EXTENTS, synth.VOXEL_SIZE,
                                            synth.HEIGHT_LO, synth.HEIGHT_HI, synth.NUM_SLICES)
-        np.testing.assert_array_equal(_np(pl.bev.height_maps[f]), hm)
         gi = orc.gen_sparse_pooling_input_avod(upts, vox, Ps[f], list(im_size), (hm.shape[1], hm.shape[2]))
         ref = orc.produce_sparse_pooling_input(gi, stride=stride)
-        assert int(_np(pl.frame_nnz)[f]) == ref["Mij_pool"].shape[0] > 0
         eb, ei = orc.sparse_pool_layer(bev[f:f + 1], img[f:f + 1], ref["Mij_pool"], ref["M_val"], ref["M_size"],
                                        ref["img_index_flip_pool"], dual=True)
-        _close_and_exact(out[f:f + 1], eb)
-        _close_and_exact(iout[f:f + 1], ei)
+        res.append((hm, ref["Mij_pool"].shape[0], eb, ei))
+    return res
 
 
 @pytest.mark.parametrize("form", ["f64", "bev_input"])
