@@ -130,6 +130,32 @@ int shpl_build_index(int n_frames, const int64_t *d_point_offsets, const int64_t
                      int64_t *d_flip, int64_t *d_frame_nnz, int64_t *d_frame_out_off,
                      uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream);
 
+/* shpl_build_index over a batch of frames of DIFFERENT image sizes (KITTI's left colour images come as
+ * 1242x375, 1224x370, 1238x374 and 1241x376; the reference hands every sample's own image_shape to
+ * gen_sparse_pooling_input_avod, kitti_dataset.py:376-377). The frames share one padded image feature map
+ * [n_frames, img_rows, img_cols, C]; instead of im_w, im_h:
+ *   d_im_sizes [n_frames, 2] f64 : (W_f, H_f), frame f's own full-resolution image size
+ *   img_rows, img_cols           : the padded map's size in strided pixels (>= 1; SHPL_ERR_BAD_SHAPE otherwise)
+ * Frame f is clipped against (W_f, H_f) (so its clip survivors, and with them the order of the second
+ * projection's products, are its own) and clamped against its own strided size floor(W_f / s_img),
+ * floor(H_f / s_img), computed on the device with make_geometry's division. Pixel ids use the padded pitch:
+ *   d_pix = f*img_rows*img_cols + v'*img_cols + u'
+ * Every other output is as shpl_build_index writes it: per frame d_mij, d_flip and d_frame_nnz are the
+ * reference's outputs for that frame called with its own im_size. An entry whose strided pixel lies outside the
+ * padded map (u' >= img_cols or v' >= img_rows: a frame larger than the map) gets pix = -1 and sets
+ * SHPL_EBIT_PIXEL, like a negative pixel. A size that is NaN, infinite, zero or negative keeps no point of its
+ * frame. The 2^31 bound on global ids is taken on n_frames * img_rows * img_cols; the workspace is
+ * shpl_build_index's. Arguments are checked in shpl_build_index's order (d_im_sizes with the pointers, the map
+ * size with the shapes). */
+int shpl_build_index_ragged(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
+                            int64_t max_points_per_frame,
+                            const void *d_points, int points_dtype, const void *d_voxels, int voxels_itype,
+                            int64_t vox_stride, const double *d_P, const double *d_im_sizes, int64_t img_rows,
+                            int64_t img_cols, double bv_h, double bv_w, double s_img, double s_bv,
+                            const float *d_mval, int32_t *d_cell, int32_t *d_pix, float *d_val, int64_t *d_mij,
+                            int64_t *d_flip, int64_t *d_frame_nnz, int64_t *d_frame_out_off,
+                            uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream);
+
 /* gen_sparse_pooling_input_avod alone (sparse_pool_utils.py:6-20), one frame:
  * outputs bv_index [nv,2] i64 and img_index 3 rows of stride ld f64 ([u;v;0]),
  * *d_nv = nv. Capacity n. */
@@ -528,6 +554,20 @@ int shpl_build_index_buckets(int n_frames, const int64_t *d_point_offsets, const
                              int64_t *d_frame_nnz, int64_t *d_frame_out_off, uint32_t *d_err, void *d_ws,
                              size_t ws_bytes, int64_t nnz_cap, void *d_bkt, size_t bkt_bytes,
                              const shpl_pass_copy *cell_copy, const shpl_pass_copy *pixel_copy, void *stream);
+/* shpl_build_index_buckets over frames of different image sizes (shpl_build_index_ragged's d_im_sizes, img_rows,
+ * img_cols in place of im_w, im_h), in all three forms (one launch, two launches, riders): the pixel key's
+ * buckets, the bucket limits and shpl_bucket_workspace_bytes' pix_per_frame are those of the padded map,
+ * img_rows * img_cols pixels per frame; pixel_copy copies all of them. An entry outside the padded map gets
+ * no bucket. */
+int shpl_build_index_buckets_ragged(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
+                                    int64_t max_points_per_frame, const void *d_points, int points_dtype,
+                                    const void *d_voxels, int voxels_itype, int64_t vox_stride, const double *d_P,
+                                    const double *d_im_sizes, int64_t img_rows, int64_t img_cols, double bv_h,
+                                    double bv_w, double s_img, double s_bv, const float *d_mval, int32_t *d_cell,
+                                    int32_t *d_pix, float *d_val, int64_t *d_frame_nnz, int64_t *d_frame_out_off,
+                                    uint32_t *d_err, void *d_ws, size_t ws_bytes, int64_t nnz_cap, void *d_bkt,
+                                    size_t bkt_bytes, const shpl_pass_copy *cell_copy,
+                                    const shpl_pass_copy *pixel_copy, void *stream);
 
 /* The map shpl_build_index_buckets left: its frame layout, index arrays and
  * bucket workspace (the same sizes as that call). */

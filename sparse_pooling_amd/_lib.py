@@ -161,6 +161,8 @@ def _declare(lib):
         "shpl_build_index_workspace_bytes": (i32, [i32, i64, psz]),
         "shpl_build_index": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, d, d, d, d, d, d, p,
                                    p, p, p, p, p, p, p, p, p, sz, p]),
+        "shpl_build_index_ragged": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, p, i64, i64, d, d, d, d, p,
+                                          p, p, p, p, p, p, p, p, p, sz, p]),
         "shpl_bev_workspace_bytes": (i32, [i64, i32, psz]),
         "shpl_mv3d_workspace_bytes": (i32, [i64, psz]),
         "shpl_mv3d_voxels": (i32, [i32, p, i64, p, i64, p, p, p, p, d, d, i32, p, i64, p, p, p, p, p, p,
@@ -189,6 +191,9 @@ def _declare(lib):
         "shpl_build_index_buckets": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, d, d, d, d, d, d, p,
                                            p, p, p, p, p, p, p, sz, i64, p, sz, ctypes.POINTER(ShplPassCopy),
                                            ctypes.POINTER(ShplPassCopy), p]),
+        "shpl_build_index_buckets_ragged": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, p, i64, i64, d, d, d, d, p,
+                                                  p, p, p, p, p, p, p, sz, i64, p, sz,
+                                                  ctypes.POINTER(ShplPassCopy), ctypes.POINTER(ShplPassCopy), p]),
         "shpl_build_csr_buckets": (i32, [ctypes.POINTER(ShplBuckets), ctypes.POINTER(ShplCsr),
                                          ctypes.POINTER(ShplCsr), p]),
         "shpl_pull_pair": (i32, [ctypes.POINTER(ShplCsr), ctypes.POINTER(ShplPullDesc), ctypes.POINTER(ShplCsr),
@@ -288,6 +293,16 @@ def index_args(n_frames, point_offsets, point_counts, max_points, points, voxels
             F64 if points.dtype == torch.float64 else F32, ptr(voxels), I64 if voxels.dtype == torch.int64 else I32,
             int(voxels.stride(0)), ptr(P), float(im_size[0]), float(im_size[1]), float(bv_size[0]), float(bv_size[1]),
             float(stride[0]), float(stride[1]), ptr(mval), ptr(cell), ptr(pix), ptr(val))
+
+
+def index_args_ragged(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_sizes, img_hw, bv_size,
+                      stride, mval, cell, pix, val):
+    """The twenty-one leading arguments shpl_build_index_ragged and shpl_build_index_buckets_ragged share:
+    im_sizes [n_frames, 2] f64 on the device ((W, H) per frame), img_hw the padded map's (rows, cols)."""
+    assert im_sizes.dtype == torch.float64 and im_sizes.is_contiguous() and im_sizes.numel() == 2 * n_frames
+    lead = index_args(n_frames, point_offsets, point_counts, max_points, points, voxels, P, (0, 0), bv_size, stride,
+                      mval, cell, pix, val)
+    return lead[:10] + (ptr(im_sizes), int(img_hw[0]), int(img_hw[1])) + lead[12:]
 
 
 # Row-keyed pulls (shpl_csr.key_range: one launch per pull) are the default for batches of fewer than ROWS_FRAMES

@@ -540,6 +540,11 @@ __global__ __launch_bounds__(IDX_BLOCK) void k_index1(Stage st, Frames fr, Bkt b
     if (threadIdx.x < 12) s_P[threadIdx.x] = st.P[12 * (int64_t)f + threadIdx.x];
     Stage sf = st;
     sf.P_frame = s_P;
+    if constexpr (Stage::RAGGED) {  // the frame's own image size and strided size beside it (the next two threads)
+        __shared__ double s_sz[4];
+        if (threadIdx.x >= 12 && threadIdx.x < 14) st.stage_dims(f, threadIdx.x - 12, s_sz);
+        sf.sz_frame = s_sz;
+    }
     typename Stage::In in;
     uint32_t m;
     typename Stage::Payload pl;

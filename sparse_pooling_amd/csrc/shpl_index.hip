@@ -87,13 +87,14 @@ struct Produced {
     bool inside;   // r < n_cells
 };
 
-__device__ __forceinline__ Produced produce(const Geometry &g, double ur, double vr, int64_t vx,
-                                            int64_t vz) {
+// (wq, hq): the strided image size the index is clamped to -- g's, or the frame's own (ragged batches).
+__device__ __forceinline__ Produced produce(const Geometry &g, double wq, double hq, double ur, double vr,
+                                            int64_t vx, int64_t vz) {
     Produced o = {};
     double u = floor(div_stride(ur, g.s_img, g.inv_img));
     double v = floor(div_stride(vr, g.s_img, g.inv_img));
-    if (u >= g.wq) u = g.wq - 1.0;
-    if (v >= g.hq) v = g.hq - 1.0;
+    if (u >= wq) u = wq - 1.0;
+    if (v >= hq) v = hq - 1.0;
     o.u = u;
     o.v = v;
     const double bx = floor(div_stride((double)vx, g.s_bv, g.inv_bv));
@@ -108,9 +109,33 @@ __device__ __forceinline__ Produced produce(const Geometry &g, double ur, double
 // writes kept point i at global position pos (frame starts at fstart);
 // touch() runs for every point in the write pass (in-place side effects).
 
-template <typename PT, typename VT>
-struct FusedStage {
+// Ragged batches (shpl_build_index_ragged): every frame is clipped against its own image size and clamped
+// against its own strided size, read from im_sizes[f] = (W_f, H_f); the frames share one padded image feature
+// map of g.hq x g.wq strided pixels (the pitch of the pixel ids, g.n_pix per frame). The uniform stage carries
+// none of this (an empty base: its kernel arguments are what they were).
+template <bool RAGGED>
+struct FrameDims {};
+template <>
+struct FrameDims<true> {
+    const double *im_sizes;             // [n_frames, 2] f64
+    const double *sz_frame = nullptr;   // k_index1: this frame's (W, H, wq, hq), staged in LDS beside P_frame
+};
+
+struct ImageDims {
+    double im_w, im_h, wq, hq;
+};
+
+// A frame's own size from the device array: a NaN or +inf size becomes NaN, which fails every comparison of
+// the clip (no point kept); zero, negative and -inf sizes fail `u >= 0 && u < w - 1` by themselves.
+__device__ __forceinline__ double frame_size(const double *im_sizes, int f, int k) {
+    const double s = im_sizes[2 * (int64_t)f + k];
+    return s < HUGE_VAL ? s : __builtin_nan("");
+}
+
+template <typename PT, typename VT, bool RAGGED_ = false>
+struct FusedStage : FrameDims<RAGGED_> {
     static constexpr bool HAS_BUCKETS = true;
+    static constexpr bool RAGGED = RAGGED_;
     const void *pts;
     const void *vox;
     int64_t vstride;
@@ -136,6 +161,27 @@ struct FusedStage {
         in.vx = load_idx<VT>(vox, i * vstride);
         in.vz = load_idx<VT>(vox, i * vstride + 1);
     }
+    // the image frame f is clipped and clamped against: g's, or (ragged) the frame's own
+    __device__ ImageDims dims(int f) const {
+        if constexpr (RAGGED) {
+            if (this->sz_frame) return ImageDims{this->sz_frame[0], this->sz_frame[1], this->sz_frame[2], this->sz_frame[3]};
+            return ImageDims{frame_size(this->im_sizes, f, 0), frame_size(this->im_sizes, f, 1), strided_size(f, 0),
+                             strided_size(f, 1)};
+        } else {
+            return ImageDims{g.im_w, g.im_h, g.wq, g.hq};
+        }
+    }
+    // floor(size / s_img) of frame f's width (k = 0) or height (1): make_geometry's division
+    __device__ double strided_size(int f, int k) const {
+        return floor(div_stride(frame_size(this->im_sizes, f, k), g.s_img, g.inv_img));
+    }
+    // k_index1 (ragged): threads t = 0, 1 stage frame f's (W, H, wq, hq) into lds[4]
+    __device__ void stage_dims(int f, int t, double *lds) const {
+        if constexpr (RAGGED) {
+            lds[t] = frame_size(this->im_sizes, f, t);
+            lds[2 + t] = strided_size(f, t);
+        }
+    }
     // AUX = inside the clip (the columns of the second projection)
     __device__ uint32_t eval(const Ctx &c, int f, int64_t, const In &in, Payload &pl) const {
         double u, v, Pf[12];
@@ -147,19 +193,25 @@ struct FusedStage {
             for (int k = 0; k < 12; ++k) Pf[k] = P[12 * f + k];
         }
         project(Pf, in.x, in.y, in.z, u, v, c.n_live == 1);
-        if (!in_image(u, v, g.im_w, g.im_h)) return 0u;
+        const ImageDims d = dims(f);
+        if (!in_image(u, v, d.im_w, d.im_h)) return 0u;
         if (c.n_aux == 1 && c.n_live != 1) project(Pf, in.x, in.y, in.z, u, v, true);
         const double ur = (double)(int64_t)rint(u);
         const double vr = (double)(int64_t)rint(v);
-        pl.pr = produce(g, ur, vr, in.vx, in.vz);
+        pl.pr = produce(g, d.wq, d.hq, ur, vr, in.vx, in.vz);
         return AUX | (pl.pr.inside ? KEEP_MULTI | KEEP_ONE : 0u);
+    }
+    // (ragged) the strided pixel lies inside the padded map: a frame larger than the map has pixels that do not
+    __device__ bool in_map(int64_t vi, int64_t ui) const {
+        if constexpr (RAGGED) return ui < (int64_t)g.wq && vi < (int64_t)g.hq;
+        return true;
     }
     __device__ void touch(int, int64_t, const Payload &, bool) const {}
     __device__ void emit(int f, int64_t i, int64_t pos, int64_t fstart, const Payload &pl) const {
         const int64_t r = pl.pr.r;
         const int64_t vi = (int64_t)pl.pr.v, ui = (int64_t)pl.pr.u;
         const bool rok = r >= 0;
-        const bool pok = vi >= 0 && ui >= 0;
+        const bool pok = vi >= 0 && ui >= 0 && in_map(vi, ui);
         if ((!rok || !pok) && err) atomicOr(err, (rok ? 0u : SHPL_EBIT_ROW) | (pok ? 0u : SHPL_EBIT_PIXEL));
         cell[pos] = rok ? (int32_t)(f * g.n_cells + r) : -1;
         pix[pos] = pok ? (int32_t)(f * g.n_pix + vi * (int64_t)g.wq + ui) : -1;
@@ -182,7 +234,7 @@ struct FusedStage {
     // frame-local destinations of a kept entry (buckets): the cell and pixel emit() writes, unless -1
     __device__ bool bucket_keys(const Payload &pl, int32_t &kc, int32_t &kp) const {
         const int64_t r = pl.pr.r, vi = (int64_t)pl.pr.v, ui = (int64_t)pl.pr.u;
-        if (r < 0 || vi < 0 || ui < 0) return false;
+        if (r < 0 || vi < 0 || ui < 0 || !in_map(vi, ui)) return false;
         kc = (int32_t)r;
         kp = (int32_t)(vi * (int64_t)g.wq + ui);
         return true;
@@ -255,7 +307,7 @@ struct ProduceStage {  // produce_sparse_pooling_input (in-place img_index updat
         in.vz = load_idx<VT>(bv, i * bstride + 1);
     }
     __device__ uint32_t eval(const Ctx &, int, int64_t, const In &in, Payload &pl) const {
-        pl.pr = produce(g, in.u, in.v, in.vx, in.vz);
+        pl.pr = produce(g, g.wq, g.hq, in.u, in.v, in.vx, in.vz);
         pl.w = in.w;
         return pl.pr.inside ? KEEP_MULTI | KEEP_ONE : 0u;
     }
@@ -302,28 +354,46 @@ extern "C" int shpl_build_index_workspace_bytes(int n_frames, int64_t max_points
     return SHPL_OK;
 }
 
-// shpl_build_index, optionally with the destination buckets (bk != NULL)
+// shpl_build_index, optionally with the destination buckets (bk != NULL); RAGGED: every frame against its own
+// image size d_im_sizes[f] (g then holds the padded map: make_geometry_ragged)
+template <bool RAGGED>
 static int build_index(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
                        int64_t max_points_per_frame, const void *d_points, int points_dtype, const void *d_voxels,
-                       int voxels_itype, int64_t vox_stride, const double *d_P, const Geometry &g,
-                       const float *d_mval, int32_t *d_cell, int32_t *d_pix, float *d_val, int64_t *d_mij,
-                       int64_t *d_flip, int64_t *d_frame_nnz, int64_t *d_frame_out_off, uint32_t *d_err, void *d_ws,
-                       size_t ws_bytes, hipStream_t s, const Bkt *bk) {
+                       int voxels_itype, int64_t vox_stride, const double *d_P, const double *d_im_sizes,
+                       const Geometry &g, const float *d_mval, int32_t *d_cell, int32_t *d_pix, float *d_val,
+                       int64_t *d_mij, int64_t *d_flip, int64_t *d_frame_nnz, int64_t *d_frame_out_off,
+                       uint32_t *d_err, void *d_ws, size_t ws_bytes, hipStream_t s, const Bkt *bk) {
     return by_point_types(points_dtype, voxels_itype, [&](auto pt, auto vt) {
-        FusedStage<typename decltype(pt)::T, typename decltype(vt)::T> st{
-            d_points, d_voxels, vox_stride, d_P, g, d_mval, d_cell, d_pix, d_val, d_mij, d_flip, d_err};
+        FrameDims<RAGGED> fd{};
+        if constexpr (RAGGED) fd.im_sizes = d_im_sizes;
+        FusedStage<typename decltype(pt)::T, typename decltype(vt)::T, RAGGED> st{
+            fd, d_points, d_voxels, vox_stride, d_P, g, d_mval, d_cell, d_pix, d_val, d_mij, d_flip, d_err};
         return run_compaction(st, n_frames, max_points_per_frame, d_point_offsets, d_point_counts, d_frame_nnz,
                               d_frame_out_off, d_err, d_ws, ws_bytes, s, bk);
     });
 }
 
+// The padded map of a ragged batch as a Geometry: wq x hq = img_cols x img_rows strided pixels (the pitch of
+// the pixel ids), n_pix their product (saturated: index_args refuses it); no image size of its own (NaN).
+static Geometry make_geometry_ragged(int64_t img_rows, int64_t img_cols, double bv_h, double bv_w, double s_img,
+                                     double s_bv) {
+    Geometry g = make_geometry(NAN, NAN, bv_h, bv_w, s_img, s_bv);
+    g.wq = (double)img_cols;
+    g.hq = (double)img_rows;
+    const bool fits = img_rows >= 1 && img_cols >= 1 && (double)img_rows * (double)img_cols < 4e18;
+    g.n_pix = fits ? img_rows * img_cols : (img_rows >= 1 && img_cols >= 1 ? INT64_MAX : 0);
+    return g;
+}
+
+// sizes_ok / map_ok: the ragged entries' own arguments (d_im_sizes given; img_rows, img_cols >= 1), checked
+// with the pointers resp. with the shapes
 static int index_args(int n_frames, const int64_t *d_point_offsets, int64_t max_points_per_frame,
                       const void *d_points, const void *d_voxels, int64_t vox_stride, const double *d_P,
                       double s_img, double s_bv, const int32_t *d_cell, const int32_t *d_pix, const float *d_val,
-                      const void *d_ws, const Geometry &g) {
-    if (n_frames < 1 || !d_point_offsets || !d_P || !d_ws) return SHPL_ERR_ARG;
+                      const void *d_ws, const Geometry &g, bool sizes_ok = true, bool map_ok = true) {
+    if (n_frames < 1 || !d_point_offsets || !d_P || !d_ws || !sizes_ok) return SHPL_ERR_ARG;
     if (max_points_per_frame > 0 && (!d_points || !d_voxels || !d_cell || !d_pix || !d_val)) return SHPL_ERR_ARG;
-    if (vox_stride < 2 || !(s_img > 0) || !(s_bv > 0)) return SHPL_ERR_BAD_SHAPE;
+    if (vox_stride < 2 || !(s_img > 0) || !(s_bv > 0) || !map_ok) return SHPL_ERR_BAD_SHAPE;
     if ((double)n_frames * (double)(g.n_cells > 0 ? g.n_cells : 0) >= 2147483647.0 ||
         (double)n_frames * (double)(g.n_pix > 0 ? g.n_pix : 0) >= 2147483647.0)
         return SHPL_ERR_BAD_SHAPE;
@@ -343,9 +413,30 @@ extern "C" int shpl_build_index(int n_frames, const int64_t *d_point_offsets, co
     const int rc = index_args(n_frames, d_point_offsets, max_points_per_frame, d_points, d_voxels, vox_stride, d_P,
                               s_img, s_bv, d_cell, d_pix, d_val, d_ws, g);
     if (rc) return rc;
-    return build_index(n_frames, d_point_offsets, d_point_counts, max_points_per_frame, d_points, points_dtype,
-                       d_voxels, voxels_itype, vox_stride, d_P, g, d_mval, d_cell, d_pix, d_val, d_mij, d_flip,
-                       d_frame_nnz, d_frame_out_off, d_err, d_ws, ws_bytes, (hipStream_t)stream, nullptr);
+    return build_index<false>(n_frames, d_point_offsets, d_point_counts, max_points_per_frame, d_points,
+                              points_dtype, d_voxels, voxels_itype, vox_stride, d_P, nullptr, g, d_mval, d_cell,
+                              d_pix, d_val, d_mij, d_flip, d_frame_nnz, d_frame_out_off, d_err, d_ws, ws_bytes,
+                              (hipStream_t)stream, nullptr);
+}
+
+extern "C" int shpl_build_index_ragged(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
+                                       int64_t max_points_per_frame, const void *d_points, int points_dtype,
+                                       const void *d_voxels, int voxels_itype, int64_t vox_stride,
+                                       const double *d_P, const double *d_im_sizes, int64_t img_rows,
+                                       int64_t img_cols, double bv_h, double bv_w, double s_img, double s_bv,
+                                       const float *d_mval, int32_t *d_cell, int32_t *d_pix, float *d_val,
+                                       int64_t *d_mij, int64_t *d_flip, int64_t *d_frame_nnz,
+                                       int64_t *d_frame_out_off, uint32_t *d_err, void *d_ws, size_t ws_bytes,
+                                       void *stream) {
+    const Geometry g = make_geometry_ragged(img_rows, img_cols, bv_h, bv_w, s_img, s_bv);
+    const int rc = index_args(n_frames, d_point_offsets, max_points_per_frame, d_points, d_voxels, vox_stride, d_P,
+                              s_img, s_bv, d_cell, d_pix, d_val, d_ws, g, d_im_sizes != nullptr,
+                              img_rows >= 1 && img_cols >= 1);
+    if (rc) return rc;
+    return build_index<true>(n_frames, d_point_offsets, d_point_counts, max_points_per_frame, d_points,
+                             points_dtype, d_voxels, voxels_itype, vox_stride, d_P, d_im_sizes, g, d_mval, d_cell,
+                             d_pix, d_val, d_mij, d_flip, d_frame_nnz, d_frame_out_off, d_err, d_ws, ws_bytes,
+                             (hipStream_t)stream, nullptr);
 }
 
 // bucket limits: 24-bit entry offsets, 512 ranges of BK_KEYS destinations per frame and key
@@ -373,18 +464,18 @@ extern "C" int shpl_bucket_workspace_reset(int n_frames, void *d_bkt, size_t bkt
                                                                                              : SHPL_ERR_HIP;
 }
 
-extern "C" int shpl_build_index_buckets(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
-                                        int64_t max_points_per_frame, const void *d_points, int points_dtype,
-                                        const void *d_voxels, int voxels_itype, int64_t vox_stride, const double *d_P,
-                                        double im_w, double im_h, double bv_h, double bv_w, double s_img,
-                                        double s_bv, const float *d_mval, int32_t *d_cell, int32_t *d_pix,
-                                        float *d_val, int64_t *d_frame_nnz, int64_t *d_frame_out_off,
-                                        uint32_t *d_err, void *d_ws, size_t ws_bytes, int64_t nnz_cap, void *d_bkt,
-                                        size_t bkt_bytes, const shpl_pass_copy *cell_copy,
-                                        const shpl_pass_copy *pixel_copy, void *stream) {
-    const Geometry g = make_geometry(im_w, im_h, bv_h, bv_w, s_img, s_bv);
+// shpl_build_index_buckets (d_im_sizes NULL) and shpl_build_index_buckets_ragged over the geometry g
+template <bool RAGGED>
+static int build_index_buckets(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
+                               int64_t max_points_per_frame, const void *d_points, int points_dtype,
+                               const void *d_voxels, int voxels_itype, int64_t vox_stride, const double *d_P,
+                               const double *d_im_sizes, bool map_ok, const Geometry &g, double s_img, double s_bv,
+                               const float *d_mval, int32_t *d_cell, int32_t *d_pix, float *d_val,
+                               int64_t *d_frame_nnz, int64_t *d_frame_out_off, uint32_t *d_err, void *d_ws,
+                               size_t ws_bytes, int64_t nnz_cap, void *d_bkt, size_t bkt_bytes,
+                               const shpl_pass_copy *cell_copy, const shpl_pass_copy *pixel_copy, void *stream) {
     int rc = index_args(n_frames, d_point_offsets, max_points_per_frame, d_points, d_voxels, vox_stride, d_P, s_img,
-                        s_bv, d_cell, d_pix, d_val, d_ws, g);
+                        s_bv, d_cell, d_pix, d_val, d_ws, g, !RAGGED || d_im_sizes != nullptr, map_ok);
     if (rc) return rc;
     if (!d_bkt || !d_frame_nnz) return SHPL_ERR_ARG;
     if (!bucket_shape_ok(max_points_per_frame, nnz_cap, g.n_cells, g.n_pix)) return SHPL_ERR_BAD_SHAPE;
@@ -400,9 +491,45 @@ extern "C" int shpl_build_index_buckets(int n_frames, const int64_t *d_point_off
         if (rc) return rc;
     }
     bk.cp_blocks = rider_blocks(n_frames, copy_bytes);
-    return build_index(n_frames, d_point_offsets, d_point_counts, max_points_per_frame, d_points, points_dtype,
-                       d_voxels, voxels_itype, vox_stride, d_P, g, d_mval, d_cell, d_pix, d_val, nullptr, nullptr,
-                       d_frame_nnz, d_frame_out_off, d_err, d_ws, ws_bytes, (hipStream_t)stream, &bk);
+    return build_index<RAGGED>(n_frames, d_point_offsets, d_point_counts, max_points_per_frame, d_points,
+                               points_dtype, d_voxels, voxels_itype, vox_stride, d_P, d_im_sizes, g, d_mval, d_cell,
+                               d_pix, d_val, nullptr, nullptr, d_frame_nnz, d_frame_out_off, d_err, d_ws, ws_bytes,
+                               (hipStream_t)stream, &bk);
+}
+
+extern "C" int shpl_build_index_buckets(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
+                                        int64_t max_points_per_frame, const void *d_points, int points_dtype,
+                                        const void *d_voxels, int voxels_itype, int64_t vox_stride, const double *d_P,
+                                        double im_w, double im_h, double bv_h, double bv_w, double s_img,
+                                        double s_bv, const float *d_mval, int32_t *d_cell, int32_t *d_pix,
+                                        float *d_val, int64_t *d_frame_nnz, int64_t *d_frame_out_off,
+                                        uint32_t *d_err, void *d_ws, size_t ws_bytes, int64_t nnz_cap, void *d_bkt,
+                                        size_t bkt_bytes, const shpl_pass_copy *cell_copy,
+                                        const shpl_pass_copy *pixel_copy, void *stream) {
+    return build_index_buckets<false>(n_frames, d_point_offsets, d_point_counts, max_points_per_frame, d_points,
+                                      points_dtype, d_voxels, voxels_itype, vox_stride, d_P, nullptr, true,
+                                      make_geometry(im_w, im_h, bv_h, bv_w, s_img, s_bv), s_img, s_bv, d_mval,
+                                      d_cell, d_pix, d_val, d_frame_nnz, d_frame_out_off, d_err, d_ws, ws_bytes,
+                                      nnz_cap, d_bkt, bkt_bytes, cell_copy, pixel_copy, stream);
+}
+
+extern "C" int shpl_build_index_buckets_ragged(int n_frames, const int64_t *d_point_offsets,
+                                               const int64_t *d_point_counts, int64_t max_points_per_frame,
+                                               const void *d_points, int points_dtype, const void *d_voxels,
+                                               int voxels_itype, int64_t vox_stride, const double *d_P,
+                                               const double *d_im_sizes, int64_t img_rows, int64_t img_cols,
+                                               double bv_h, double bv_w, double s_img, double s_bv,
+                                               const float *d_mval, int32_t *d_cell, int32_t *d_pix, float *d_val,
+                                               int64_t *d_frame_nnz, int64_t *d_frame_out_off, uint32_t *d_err,
+                                               void *d_ws, size_t ws_bytes, int64_t nnz_cap, void *d_bkt,
+                                               size_t bkt_bytes, const shpl_pass_copy *cell_copy,
+                                               const shpl_pass_copy *pixel_copy, void *stream) {
+    return build_index_buckets<true>(n_frames, d_point_offsets, d_point_counts, max_points_per_frame, d_points,
+                                     points_dtype, d_voxels, voxels_itype, vox_stride, d_P, d_im_sizes,
+                                     img_rows >= 1 && img_cols >= 1,
+                                     make_geometry_ragged(img_rows, img_cols, bv_h, bv_w, s_img, s_bv), s_img, s_bv,
+                                     d_mval, d_cell, d_pix, d_val, d_frame_nnz, d_frame_out_off, d_err, d_ws,
+                                     ws_bytes, nnz_cap, d_bkt, bkt_bytes, cell_copy, pixel_copy, stream);
 }
 
 // Writes the device [0, n] offsets of a single frame into the workspace tail.

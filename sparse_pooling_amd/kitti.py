@@ -209,6 +209,12 @@ class KittiFrames:
         self.flip = torch.as_tensor(np.asarray(flips, np.int32)).to(dev)
         self.image_shapes = [tuple(s) for s in image_shapes]
 
+    @property
+    def padded_im_size(self):
+        """(max W, max H) over the batch's images: the im_size of a ragged pipeline's padded image maps
+        (FramePipeline(..., ragged=True)), which every frame's own size fits into."""
+        return (max(int(s[1]) for s in self.image_shapes), max(int(s[0]) for s in self.image_shapes))
+
     @classmethod
     def from_dirs(cls, calib_dir, velo_dir, planes_dir, indices, image_shapes, flips=None, device="cuda"):
         """Read the samples' calib / velodyne / planes files (KITTI layout)."""

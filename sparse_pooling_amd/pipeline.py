@@ -90,8 +90,14 @@ class FusedPipeline:
 
     def __init__(self, n_frames, max_points_per_frame, total_points, im_size, bv_size, stride,
                  c_bev, c_img, dtype=torch.float32, device="cuda", dual=False, rows=None, live=False,
-                 buckets=None, split=False):
-        """live: the sparse passes walk each frame's live entries (shpl_csr frame layout) instead of the
+                 buckets=None, split=False, ragged=False):
+        """ragged: a batch of mixed image sizes (shpl_build_index_ragged / _buckets_ragged). im_size is then the
+        PADDED full-resolution size: the image feature maps are [B, Hi, Wi, C] with Hi, Wi its strided size, as
+        without ragged. Every frame is clipped and clamped against its own size in ``self.im_sizes`` ([B, 2] f64
+        (W, H) on the device, the padded size until ``set_image_sizes``); every step form runs unchanged on top.
+        Outside a frame's own window [:hq_f, :wq_f] of the padded map nothing is pooled: img_fused's pass-through
+        half is the input's padding copied and its pooled half is zero there.
+        live: the sparse passes walk each frame's live entries (shpl_csr frame layout) instead of the
         whole capacity -- for capacities far above the entry counts (FramePipeline: raw-scan slots per
         voxel point); at config 2 (capacity = entries) the capacity walk is faster (2.22 vs 2.24 ms).
         buckets (default: with rows): the index build also cuts M into destination buckets
@@ -138,6 +144,10 @@ class FusedPipeline:
         self.frame_off = torch.empty(self.B + 1, dtype=torch.int64, device=dev)
         self.err = torch.zeros(1, **i32)
         self.index_ws = L.workspace(L.index_ws_bytes(self.B, self.max_points), dev)
+        self.ragged = bool(ragged)
+        if self.ragged:
+            self.im_sizes = torch.tensor([[float(im_size[0]), float(im_size[1])]] * self.B, dtype=torch.float64,
+                                         device=dev)
         # rows pulls: with key_range
         head_k = self.HEAD_K if self.buckets else 0
         self.csr = L.Csr(self.n_cells, self.N, dev, with_col=False,
@@ -188,16 +198,34 @@ class FusedPipeline:
         assert points.is_contiguous() and point_offsets.is_contiguous() and P.is_contiguous()
         assert voxels.stride(1) == 1, "voxel rows must be contiguous"
         st = L.stream_of(self.dev)
-        lead = L.index_args(self.B, point_offsets, point_counts, self.max_points, points, voxels, P, self.im_size,
-                            self.bv_size, self.stride, mval, self.cell, self.pix, self.val)
+        if self.ragged:  # every frame against its own size in self.im_sizes, pixel ids in the padded Hi x Wi map
+            lead = L.index_args_ragged(self.B, point_offsets, point_counts, self.max_points, points, voxels, P,
+                                       self.im_sizes, (self.Hi, self.Wi), self.bv_size, self.stride, mval, self.cell,
+                                       self.pix, self.val)
+            tail = "_ragged"
+        else:
+            lead = L.index_args(self.B, point_offsets, point_counts, self.max_points, points, voxels, P, self.im_size,
+                                self.bv_size, self.stride, mval, self.cell, self.pix, self.val)
+            tail = ""
         outs = (L.ptr(self.frame_nnz), L.ptr(self.frame_off), L.ptr(self.err), L.ptr(self.index_ws),
                 self.index_ws.numel())
         if self.buckets:
-            L.check(self._lib.shpl_build_index_buckets(*lead, *outs, self.N, L.ptr(self.bkt_ws), self.bkt_ws.numel(),
-                                                       *self._copy_riders(pass_copies), st),
-                    "shpl_build_index_buckets")
+            name = "shpl_build_index_buckets" + tail
+            L.check(getattr(self._lib, name)(*lead, *outs, self.N, L.ptr(self.bkt_ws), self.bkt_ws.numel(),
+                                             *self._copy_riders(pass_copies), st), name)
             return
-        L.check(self._lib.shpl_build_index(*lead, None, None, *outs, st), "shpl_build_index")
+        name = "shpl_build_index" + tail
+        L.check(getattr(self._lib, name)(*lead, None, None, *outs, st), name)
+
+    def set_image_sizes(self, im_sizes):
+        """ragged pipelines: the frames' own image sizes for the steps that follow, [B, 2] (W, H) -- e.g.
+        KittiFrames.im_size. A stream-ordered copy into self.im_sizes on the current stream (of a device tensor:
+        no synchronisation, capturable in a graph; the index launches read the sizes on the device)."""
+        if not self.ragged:
+            raise ValueError("set_image_sizes: a pipeline made with ragged=True")
+        if tuple(im_sizes.shape) != (self.B, 2):
+            raise ValueError(f"im_sizes must be [{self.B}, 2] (W, H), not {tuple(im_sizes.shape)}")
+        self.im_sizes.copy_(im_sizes, non_blocking=True)
 
     # shpl_build_csr_path's builder (L.CSR_AUTO: chosen by batch shape; tests force the others)
     csr_path = L.CSR_AUTO
@@ -512,13 +540,16 @@ class FramePipeline(FusedPipeline):
 
     def __init__(self, n_frames, total_points, im_size, area_extents, voxel_size, height_lo, height_hi,
                  num_slices, stride, c_bev, c_img, dtype=torch.float32, device="cuda", dual=False, maps=True,
-                 max_points_per_frame=None):
+                 max_points_per_frame=None, ragged=False):
+        """ragged: im_size is the padded size of a batch of mixed image sizes (KittiFrames.padded_im_size);
+        velo_step copies the batch's own sizes (frames.im_size) in before its index build, frame_step takes them
+        as im_sizes, so every frame's index is built against its own image (FusedPipeline's ragged)."""
         from . import bev as _bev
         nx, nz = _bev.grid_divisions(area_extents, voxel_size)
         # a frame holds at most as many voxels as points (capacity layout)
         maxp = total_points if max_points_per_frame is None else max_points_per_frame
         super().__init__(n_frames, maxp, total_points, im_size, (nz, nx), stride, c_bev, c_img,
-                         dtype=dtype, device=device, dual=dual, live=True)
+                         dtype=dtype, device=device, dual=dual, live=True, ragged=ragged)
         self.bev_args = (area_extents, voxel_size, height_lo, height_hi, num_slices)
         self.maps = maps
         self.bev_ws = L.workspace(L.ws_bytes("shpl_bev", self.N, num_slices), self.dev)
@@ -569,7 +600,10 @@ class FramePipeline(FusedPipeline):
         else:
             b.write_maps(*self._buffer("_maps"), zero=True)
 
-    def frame_step(self, points, point_offsets, planes, P, bev_feat, img_feat, point_counts=None):
+    def frame_step(self, points, point_offsets, planes, P, bev_feat, img_feat, point_counts=None, im_sizes=None):
+        """im_sizes (ragged pipelines): the frames' own image sizes, copied in first (set_image_sizes)."""
+        if im_sizes is not None:
+            self.set_image_sizes(im_sizes)
         b = self.build_bev(points, point_offsets, planes, point_counts)
         self.build_index(b.pts_in_voxel, b.voxel_indices, point_offsets, P, point_counts=b.frame_nvox)
         self.build_csr()
@@ -585,6 +619,8 @@ class FramePipeline(FusedPipeline):
                               ("maps_form", self.MAPS_FORMS)):
             if getattr(self, name) not in allowed:
                 raise ValueError(f"{name} must be one of {allowed}, not {getattr(self, name)!r}")
+        if self.ragged:  # the batch's own image sizes, on the current stream ahead of the index build
+            self.set_image_sizes(frames.im_size)
         if side is None:
             self._velo(frames)
             self.frame_step(self.velo.points, frames.point_offsets, frames.planes, frames.P2, bev_feat, img_feat,

@@ -305,19 +305,26 @@ def trans_op(bev, smap, img_shape):
 class IndexBatch:
     """Result of the fused device index builder over a batch of frames."""
 
-    def __init__(self, smap, mij, flip, frame_nnz, frame_off, n_frames, bev_hw, img_hw):
+    def __init__(self, smap, mij, flip, frame_nnz, frame_off, n_frames, bev_hw, img_hw, img_hw_frames=None):
+        """img_hw: the image feature map's (rows, cols) -- of a ragged batch, the padded map's. img_hw_frames
+        (ragged batches): every frame's own strided (rows, cols), an [n_frames, 2] i64 device tensor."""
         self.map = smap
         self.mij, self.flip = mij, flip
         self.frame_nnz, self.frame_off = frame_nnz, frame_off
         self.n_frames = n_frames
         self.bev_hw, self.img_hw = bev_hw, img_hw
+        self.img_hw_frames = img_hw_frames
 
 
 def build_index_batch(points, voxels, point_offsets, P, im_size, bv_size, stride, max_points,
-                      mval=None, ref_outputs=False, ws=None, point_counts=None):
+                      mval=None, ref_outputs=False, ws=None, point_counts=None, im_sizes=None, img_hw=None):
     """Fused gen_sparse_pooling_input_avod + produce_sparse_pooling_input for a
     batch of frames in one pass (shpl_build_index). All inputs are device
-    tensors; nothing synchronises the host."""
+    tensors; nothing synchronises the host.
+    im_sizes ([n_frames, 2] f64 device tensor of (W, H), as KittiFrames.im_size): a batch of mixed image sizes
+    (shpl_build_index_ragged) -- every frame is clipped and clamped against its own size, and pixel ids take
+    the pitch of the padded image feature map img_hw = (rows, cols) in strided pixels (default: im_size's
+    strided size, im_size then being the padded full-resolution size)."""
     dev = points.device
     points, point_offsets, P = points.contiguous(), point_offsets.contiguous(), P.contiguous()
     if voxels.stride(1) != 1:
@@ -336,10 +343,23 @@ def build_index_batch(points, voxels, point_offsets, P, im_size, bv_size, stride
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     if ws is None:
         ws = L.workspace(L.index_ws_bytes(n_frames, max_points), dev)
-    lead = L.index_args(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_size, bv_size,
-                        stride, mval, cell, pix, val)
-    L.check(L.lib().shpl_build_index(*lead, L.ptr(mij), L.ptr(flip), L.ptr(frame_nnz), L.ptr(frame_off), L.ptr(err),
-                                     L.ptr(ws), ws.numel(), L.stream_of(dev)), "shpl_build_index")
+    outs = (L.ptr(mij), L.ptr(flip), L.ptr(frame_nnz), L.ptr(frame_off), L.ptr(err), L.ptr(ws), ws.numel(),
+            L.stream_of(dev))
+    hw_frames = None
+    if im_sizes is None and img_hw is None:
+        lead = L.index_args(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_size, bv_size,
+                            stride, mval, cell, pix, val)
+        L.check(L.lib().shpl_build_index(*lead, *outs), "shpl_build_index")
+    else:
+        if im_sizes is None:
+            raise ValueError("img_hw goes with im_sizes (the frames' own image sizes)")
+        if img_hw is not None:
+            hq, wq = int(img_hw[0]), int(img_hw[1])
+        im_sizes = im_sizes.to(device=dev, dtype=torch.float64).reshape(n_frames, 2).contiguous()
+        lead = L.index_args_ragged(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_sizes,
+                                   (hq, wq), bv_size, stride, mval, cell, pix, val)
+        L.check(L.lib().shpl_build_index_ragged(*lead, *outs), "shpl_build_index_ragged")
+        hw_frames = torch.floor(im_sizes / s_img).flip(1).to(torch.int64)  # IEEE division, as the device's
     smap = ShplMap(cell, None, val, pix, N, n_frames * bhq * bwq, n_frames * hq * wq, N, dev,
                    frame_off=frame_off, frame_nnz=frame_nnz, n_frames=n_frames, err=err)
-    return IndexBatch(smap, mij, flip, frame_nnz, frame_off, n_frames, (bhq, bwq), (hq, wq))
+    return IndexBatch(smap, mij, flip, frame_nnz, frame_off, n_frames, (bhq, bwq), (hq, wq), hw_frames)
