@@ -156,6 +156,43 @@ int shpl_build_index_ragged(int n_frames, const int64_t *d_point_offsets, const 
                             int64_t *d_flip, int64_t *d_frame_nnz, int64_t *d_frame_out_off,
                             uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream);
 
+/* shpl_build_index for up to SHPL_MAX_INDEX_LEVELS fusion levels in ONE pass over the points. The reference's
+ * AVOD RPN pools at two levels of one network (stride 1 over the BEV map, stride 8 over the BEV input padded by
+ * 4 rows) and its feed code reads sparse_pooling_inputs[0] and [1] (avod/avod/core/models/rpn_model.py:841-862);
+ * the dataset builds each entry by running gen_sparse_pooling_input_avod and produce_sparse_pooling_input over
+ * the same points, voxel indices, calibration and image shape with that level's bv_size and stride
+ * (avod/avod/datasets/kitti/kitti_dataset.py:374-389). Here every point is loaded, projected, clipped and
+ * rounded once; each level then takes its own strides, BEV flatten, in-grid filter and stable compaction (the
+ * kept set, the entry slots and nnz differ from level to level). Two launches, as shpl_build_index.
+ *
+ * `levels` is a HOST array of n_levels entries; their device pointers follow shpl_build_index's layout. Every
+ * array of level l holds, over its whole capacity, the bits shpl_build_index writes when called with that
+ * level's (s_img, s_bv, bv_h, bv_w) and the same other arguments (global ids per level: f*Hb'*Wb' + r and
+ * f*Hi'*Wi' + v'*Wi' + u' with the level's own strided sizes). *d_err (nullable) is the OR over the levels;
+ * d_frame_out_off (nullable) is shared: entry slots are the point slots at every level.
+ * Status, in shpl_build_index's order: n_frames < 1 or a NULL d_point_offsets / d_P / d_ws / levels:
+ * SHPL_ERR_ARG; n_levels outside [1, SHPL_MAX_INDEX_LEVELS]: SHPL_ERR_BAD_SHAPE (before levels[] is read); a
+ * level's NULL frame_nnz and (max_points_per_frame > 0) a NULL d_points / d_voxels or a level's NULL cell / pix /
+ * val: SHPL_ERR_ARG; vox_stride < 2, a level's stride not > 0 or BEV size negative or not finite, a level's
+ * n_frames * cells or n_frames * pixels >= 2^31: SHPL_ERR_BAD_SHAPE; then the workspace (SHPL_ERR_WORKSPACE) and
+ * the type codes (SHPL_ERR_ARG). A refused call writes nothing.
+ * The workspace holds one count per chunk for the clip and one per level; with n_levels == 1 its size is
+ * shpl_build_index's. Frames of one image size only (no ragged form). */
+#define SHPL_MAX_INDEX_LEVELS 4
+typedef struct {
+    double s_img, s_bv, bv_h, bv_w;   /* this level's stride[0], stride[1] and full-resolution BEV (H, W) */
+    int32_t *cell, *pix; float *val;  /* [N] each, shpl_build_index's layout and global ids for this level */
+    int64_t *mij, *flip;              /* optional [N,2], [N,3] */
+    int64_t *frame_nnz;               /* [n_frames] */
+} shpl_index_level;
+int shpl_build_index_levels_workspace_bytes(int n_frames, int64_t max_points_per_frame, int n_levels, size_t *bytes);
+int shpl_build_index_levels(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
+                            int64_t max_points_per_frame, const void *d_points, int points_dtype,
+                            const void *d_voxels, int voxels_itype, int64_t vox_stride, const double *d_P,
+                            double im_w, double im_h, const float *d_mval, int n_levels,
+                            const shpl_index_level *levels /* host array */, int64_t *d_frame_out_off,
+                            uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream);
+
 /* gen_sparse_pooling_input_avod alone (sparse_pool_utils.py:6-20), one frame:
  * outputs bv_index [nv,2] i64 and img_index 3 rows of stride ld f64 ([u;v;0]),
  * *d_nv = nv. Capacity n. */

@@ -118,6 +118,17 @@ class ShplPassCopy(ctypes.Structure):
                 ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int64), ("channels", ctypes.c_int64)]
 
 
+class ShplIndexLevel(ctypes.Structure):
+    """struct shpl_index_level of include/shpl.h: one fusion level of shpl_build_index_levels."""
+    _fields_ = [("s_img", ctypes.c_double), ("s_bv", ctypes.c_double), ("bv_h", ctypes.c_double),
+                ("bv_w", ctypes.c_double), ("cell", ctypes.c_void_p), ("pix", ctypes.c_void_p),
+                ("val", ctypes.c_void_p), ("mij", ctypes.c_void_p), ("flip", ctypes.c_void_p),
+                ("frame_nnz", ctypes.c_void_p)]
+
+
+MAX_INDEX_LEVELS = 4  # SHPL_MAX_INDEX_LEVELS
+
+
 def _addr(t, col=0):
     """Device pointer of a tensor as an integer, `col` elements on (None for None)."""
     return None if t is None else t.data_ptr() + (col and col * t.element_size())
@@ -163,6 +174,9 @@ def _declare(lib):
                                    p, p, p, p, p, p, p, p, p, sz, p]),
         "shpl_build_index_ragged": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, p, i64, i64, d, d, d, d, p,
                                           p, p, p, p, p, p, p, p, p, sz, p]),
+        "shpl_build_index_levels_workspace_bytes": (i32, [i32, i64, i32, psz]),
+        "shpl_build_index_levels": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, d, d, p, i32,
+                                          ctypes.POINTER(ShplIndexLevel), p, p, p, sz, p]),
         "shpl_bev_workspace_bytes": (i32, [i64, i32, psz]),
         "shpl_mv3d_workspace_bytes": (i32, [i64, psz]),
         "shpl_mv3d_voxels": (i32, [i32, p, i64, p, i64, p, p, p, p, d, d, i32, p, i64, p, p, p, p, p, p,
@@ -334,6 +348,20 @@ def ws_bytes(symbol, *args):
 
 def index_ws_bytes(n_frames, max_points):
     return ws_bytes("shpl_build_index", n_frames, max_points)
+
+
+def index_levels_ws_bytes(n_frames, max_points, n_levels):
+    return ws_bytes("shpl_build_index_levels", n_frames, max_points, n_levels)
+
+
+def index_levels(levels):
+    """The host array shpl_build_index_levels takes: levels = [(stride, bv_size, cell, pix, val, mij, flip,
+    frame_nnz)], tensors or None."""
+    arr = (ShplIndexLevel * len(levels))()
+    for a, (stride, bv_size, *tensors) in zip(arr, levels):
+        a.s_img, a.s_bv, a.bv_h, a.bv_w = float(stride[0]), float(stride[1]), float(bv_size[0]), float(bv_size[1])
+        a.cell, a.pix, a.val, a.mij, a.flip, a.frame_nnz = (_addr(t) for t in tensors)
+    return arr
 
 
 def csr_ws_bytes(n_keys, nnz_cap):

@@ -212,6 +212,33 @@ def feat_stride(level: str) -> int:
     return 2 ** int(level[-1])
 
 
+def fusion_levels(cfg: ShplConfig, bv_size):
+    """The (stride, bv_size) of every SHPL level a parsed config implies, in the order of the dataset's
+    sparse_pooling_input list (kitti_dataset.py:374-389): what build_sparse_pooling_inputs and
+    shpl_map.build_index_levels take as ``levels``. bv_size: the BEV input's (H, W).
+
+    * rpn_use_sparse_pooling: the full-resolution SHPL, ((1, 1), bv_size) (rpn_model.py:328-336), entry [0];
+    * rpn_sparse_pooling_after_vgg: the after-VGG SHPL at stride 8 over the BEV input "padded by 4"
+      (kitti_dataset.py:384-388; bev_vgg_pyramid.py:58), ((8, 8), (bv_h + 4, bv_w)). The feed code reads it from
+      entry [1] whether or not the full-resolution SHPL is on (rpn_model.py:856-857), so the stride-1 level
+      holds entry [0] then too, as in the dataset's list of two;
+    * RetinaNet: its one pyramid level, stride feat_stride(use_pyramid_level_at_SHPL) (kitti_dataset.py:375).
+
+    Empty when the dataset emits no indices or the config pools nowhere."""
+    bv_h, bv_w = int(bv_size[0]), int(bv_size[1])
+    if not cfg.dataset.output_indices:
+        return []
+    if cfg.rpn.rpn_use_sparse_pooling or cfg.rpn.rpn_sparse_pooling_after_vgg:
+        levels = [((1, 1), (bv_h, bv_w))]
+        if cfg.rpn.rpn_sparse_pooling_after_vgg:
+            levels.append(((8, 8), (bv_h + 4, bv_w)))
+        return levels
+    if cfg.retinanet.use_sparse_pooling:
+        s = feat_stride(cfg.dataset.use_pyramid_level_at_SHPL)
+        return [((s, s), (bv_h, bv_w))]
+    return []
+
+
 def fill_sparse_pooling_feed(placeholder_inputs, sparse_pooling_inputs, use_sparse_pooling,
                              after_vgg=False, use_after_vgg=False):
     """RpnModel/RetinanetModel.create_feed_dict (rpn_model.py:841-868,

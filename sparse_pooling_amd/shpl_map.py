@@ -363,3 +363,48 @@ def build_index_batch(points, voxels, point_offsets, P, im_size, bv_size, stride
     smap = ShplMap(cell, None, val, pix, N, n_frames * bhq * bwq, n_frames * hq * wq, N, dev,
                    frame_off=frame_off, frame_nnz=frame_nnz, n_frames=n_frames, err=err)
     return IndexBatch(smap, mij, flip, frame_nnz, frame_off, n_frames, (bhq, bwq), (hq, wq), hw_frames)
+
+
+def build_index_levels(points, voxels, point_offsets, P, im_size, levels, max_points, mval=None, ref_outputs=False,
+                       ws=None, point_counts=None):
+    """build_index_batch for several fusion levels in one pass over the points (shpl_build_index_levels): the
+    list the reference's dataset builds by running its index builders once per level over the same frame
+    (kitti_dataset.py:374-389; rpn_model.py:841-862 reads entries [0] and [1]). levels: a sequence of
+    (stride, bv_size), at most L.MAX_INDEX_LEVELS. Returns one IndexBatch per level, each with its own ShplMap --
+    what build_index_batch returns for that level's stride and bv_size, bit for bit -- so the CSR builders, the
+    pulls and the fused modules take them unchanged. The maps share one err tensor (the OR over the levels).
+    All inputs are device tensors; nothing synchronises the host."""
+    dev = points.device
+    points, point_offsets, P = points.contiguous(), point_offsets.contiguous(), P.contiguous()
+    if voxels.stride(1) != 1:
+        voxels = voxels.contiguous()
+    levels = [(tuple(stride), tuple(bv_size)) for stride, bv_size in levels]
+    if not 1 <= len(levels) <= L.MAX_INDEX_LEVELS:
+        raise ValueError(f"1 to {L.MAX_INDEX_LEVELS} levels, got {len(levels)}")
+    n_frames = int(point_offsets.numel()) - 1
+    N = int(points.shape[0])
+    frame_off = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if ws is None:
+        ws = L.workspace(L.index_levels_ws_bytes(n_frames, max_points, len(levels)), dev)
+    outs = []
+    for _ in levels:
+        cell, pix = _i32(N, dev), _i32(N, dev)
+        val = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+        mij = torch.empty((max(N, 1), 2), dtype=torch.int64, device=dev) if ref_outputs else None
+        flip = torch.empty((max(N, 1), 3), dtype=torch.int64, device=dev) if ref_outputs else None
+        outs.append((cell, pix, val, mij, flip, torch.empty(n_frames, dtype=torch.int64, device=dev)))
+    arr = L.index_levels([(stride, bv_size, *o) for (stride, bv_size), o in zip(levels, outs)])
+    lead = L.index_args(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_size, (0, 0), (1, 1),
+                        mval, None, None, None)
+    L.check(L.lib().shpl_build_index_levels(*lead[:12], lead[16], len(levels), arr, L.ptr(frame_off), L.ptr(err),
+                                            L.ptr(ws), ws.numel(), L.stream_of(dev)), "shpl_build_index_levels")
+    batches = []
+    for (stride, bv_size), (cell, pix, val, mij, flip, frame_nnz) in zip(levels, outs):
+        s_img, s_bv = float(stride[0]), float(stride[1])
+        wq, hq = int(np.floor(im_size[0] / s_img)), int(np.floor(im_size[1] / s_img))
+        bhq, bwq = int(np.floor(bv_size[0] / s_bv)), int(np.floor(bv_size[1] / s_bv))
+        smap = ShplMap(cell, None, val, pix, N, n_frames * bhq * bwq, n_frames * hq * wq, N, dev,
+                       frame_off=frame_off, frame_nnz=frame_nnz, n_frames=n_frames, err=err)
+        batches.append(IndexBatch(smap, mij, flip, frame_nnz, frame_off, n_frames, (bhq, bwq), (hq, wq)))
+    return batches

@@ -29,7 +29,7 @@ from .errors import InvalidArgumentError
 
 __all__ = ["SparseTensor", "gen_sparse_pooling_input_avod", "produce_sparse_pooling_input",
            "sparse_pool_layer", "_sparse_pool_op", "_sparse_pool_trans_op", "concat_bn_op",
-           "build_sparse_pooling_input"]
+           "build_sparse_pooling_input", "build_sparse_pooling_inputs"]
 
 
 class SparseTensor(NamedTuple):
@@ -163,6 +163,32 @@ def build_sparse_pooling_input(points, voxel_indices, stereo_calib, im_size, bv_
         M_val = torch.ones(k, dtype=torch.float64, device=dev)
     return {"Mij_pool": ib.mij[:k], "M_val": M_val, "M_size": M_size,
             "img_index_flip_pool": ib.flip[:k], "bev_index_flip_pool": np.zeros((0, 3))}
+
+
+def build_sparse_pooling_inputs(points, voxel_indices, stereo_calib, im_size, levels):
+    """build_sparse_pooling_input for several fusion levels in one device pass over the frame's points
+    (shpl_build_index_levels): the list KittiDataset.load_samples stores under KEY_SPARSE_POOLING_INPUT, one
+    dict per (stride, bv_size) of ``levels`` (kitti_dataset.py:374-389), which fill_sparse_pooling_feed reads
+    as entries [0] and [1] (rpn_model.py:841-862). config.fusion_levels gives ``levels`` for a parsed config.
+    Each dict is what build_sparse_pooling_input returns for that level."""
+    dev = _device()
+    pts = _to_dev(points, torch.float64, dev).reshape(-1, 3)
+    vox = _to_dev(np.asarray(voxel_indices) if not isinstance(voxel_indices, torch.Tensor)
+                  else voxel_indices, torch.int64, dev)
+    n = pts.shape[0]
+    vox = vox.reshape(n, -1) if n else vox.reshape(0, 2)
+    P = _to_dev(np.asarray(stereo_calib.p2, dtype=np.float64).reshape(1, 12), torch.float64, dev)
+    off = torch.tensor([0, n], dtype=torch.int64, device=dev)
+    levels = [(tuple(stride), tuple(bv_size)) for stride, bv_size in levels]
+    batches = sm.build_index_levels(pts, vox, off, P, im_size, levels, n, ref_outputs=True)
+    nnz = torch.stack([ib.frame_nnz[0] for ib in batches]).cpu().tolist()  # one read for all levels
+    out = []
+    for (stride, bv_size), ib, k in zip(levels, batches, nnz):
+        bq = np.floor(np.asarray(bv_size, dtype=np.float64) / float(stride[1]))
+        out.append({"Mij_pool": ib.mij[:k], "M_val": torch.ones(k, dtype=torch.float64, device=dev),
+                    "M_size": np.array([bq[0] * bq[1], k]).astype(int),
+                    "img_index_flip_pool": ib.flip[:k], "bev_index_flip_pool": np.zeros((0, 3))})
+    return out
 
 
 # ---------------------------------------------------------------- op layer
