@@ -177,7 +177,8 @@ int shpl_build_index_ragged(int n_frames, const int64_t *d_point_offsets, const 
  * n_frames * cells or n_frames * pixels >= 2^31: SHPL_ERR_BAD_SHAPE; then the workspace (SHPL_ERR_WORKSPACE) and
  * the type codes (SHPL_ERR_ARG). A refused call writes nothing.
  * The workspace holds one count per chunk for the clip and one per level; with n_levels == 1 its size is
- * shpl_build_index's. Frames of one image size only (no ragged form). */
+ * shpl_build_index's. Frames of one image size; shpl_build_index_levels_ragged (below) takes a batch of mixed
+ * image sizes. */
 #define SHPL_MAX_INDEX_LEVELS 4
 typedef struct {
     double s_img, s_bv, bv_h, bv_w;   /* this level's stride[0], stride[1] and full-resolution BEV (H, W) */
@@ -192,6 +193,33 @@ int shpl_build_index_levels(int n_frames, const int64_t *d_point_offsets, const 
                             double im_w, double im_h, const float *d_mval, int n_levels,
                             const shpl_index_level *levels /* host array */, int64_t *d_frame_out_off,
                             uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream);
+
+/* shpl_build_index_levels over a batch of frames of DIFFERENT image sizes: shpl_build_index_ragged for several
+ * fusion levels in one pass over the points. Instead of im_w, im_h:
+ *   d_im_sizes   [n_frames, 2] f64, on the device : (W_f, H_f), frame f's own full-resolution image size
+ *   level_img_hw HOST array [n_levels][2] i64     : (img_rows, img_cols), the padded image feature map of each
+ *                                                   level in that level's strided pixels
+ * Every array of level l holds, over its whole capacity, the bits shpl_build_index_ragged writes when called
+ * with that level's (s_img, s_bv, bv_h, bv_w, img_rows, img_cols) and the same other arguments. Frame f is
+ * clipped ONCE against its own (W_f, H_f): its clip survivor count is its own and selects the order of the second
+ * projection's products for all levels. At level l the index is clamped against floor(W_f / s_img_l),
+ * floor(H_f / s_img_l) (make_geometry's division, on the device) and
+ *   pix = f*img_rows_l*img_cols_l + v'*img_cols_l + u'
+ * A strided pixel outside the level's padded map gets pix = -1 and sets SHPL_EBIT_PIXEL (at that level only). A
+ * size that is NaN, infinite, zero or negative keeps no point of its frame at any level. *d_err is the OR over
+ * the levels; d_frame_out_off is shared.
+ * Status, in shpl_build_index_levels' order: d_im_sizes and level_img_hw are checked with the pointers
+ * (SHPL_ERR_ARG); a level's img_rows < 1 or img_cols < 1 with that level's shapes (SHPL_ERR_BAD_SHAPE); the 2^31
+ * bound is taken per level on n_frames * cells and on n_frames * img_rows * img_cols (the product saturated,
+ * not wrapped). A refused call launches and writes nothing. The workspace is
+ * shpl_build_index_levels_workspace_bytes'. */
+int shpl_build_index_levels_ragged(int n_frames, const int64_t *d_point_offsets, const int64_t *d_point_counts,
+                                   int64_t max_points_per_frame, const void *d_points, int points_dtype,
+                                   const void *d_voxels, int voxels_itype, int64_t vox_stride, const double *d_P,
+                                   const double *d_im_sizes, const float *d_mval, int n_levels,
+                                   const shpl_index_level *levels /* host array */,
+                                   const int64_t *level_img_hw /* host array */, int64_t *d_frame_out_off,
+                                   uint32_t *d_err, void *d_ws, size_t ws_bytes, void *stream);
 
 /* gen_sparse_pooling_input_avod alone (sparse_pool_utils.py:6-20), one frame:
  * outputs bv_index [nv,2] i64 and img_index 3 rows of stride ld f64 ([u;v;0]),

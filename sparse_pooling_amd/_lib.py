@@ -177,6 +177,9 @@ def _declare(lib):
         "shpl_build_index_levels_workspace_bytes": (i32, [i32, i64, i32, psz]),
         "shpl_build_index_levels": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, d, d, p, i32,
                                           ctypes.POINTER(ShplIndexLevel), p, p, p, sz, p]),
+        "shpl_build_index_levels_ragged": (i32, [i32, p, p, i64, p, i32, p, i32, i64, p, p, p, i32,
+                                                 ctypes.POINTER(ShplIndexLevel), ctypes.POINTER(ctypes.c_int64),
+                                                 p, p, p, sz, p]),
         "shpl_bev_workspace_bytes": (i32, [i64, i32, psz]),
         "shpl_mv3d_workspace_bytes": (i32, [i64, psz]),
         "shpl_mv3d_voxels": (i32, [i32, p, i64, p, i64, p, p, p, p, d, d, i32, p, i64, p, p, p, p, p, p,
@@ -361,6 +364,15 @@ def index_levels(levels):
     for a, (stride, bv_size, *tensors) in zip(arr, levels):
         a.s_img, a.s_bv, a.bv_h, a.bv_w = float(stride[0]), float(stride[1]), float(bv_size[0]), float(bv_size[1])
         a.cell, a.pix, a.val, a.mij, a.flip, a.frame_nnz = (_addr(t) for t in tensors)
+    return arr
+
+
+def index_level_maps(img_hws):
+    """The host array level_img_hw of shpl_build_index_levels_ragged: [n_levels][2] i64, each level's padded image
+    feature map as (img_rows, img_cols) in that level's strided pixels."""
+    arr = (ctypes.c_int64 * (2 * len(img_hws)))()
+    for l, (rows, cols) in enumerate(img_hws):
+        arr[2 * l], arr[2 * l + 1] = int(rows), int(cols)
     return arr
 
 

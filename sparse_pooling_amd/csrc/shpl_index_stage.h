@@ -63,6 +63,18 @@ Geometry make_geometry(double im_w, double im_h, double bv_h, double bv_w, doubl
     return g;
 }
 
+// The padded map of a ragged batch as a Geometry: wq x hq = img_cols x img_rows strided pixels (the pitch of
+// the pixel ids), n_pix their product (saturated: index_args refuses it); no image size of its own (NaN).
+Geometry make_geometry_ragged(int64_t img_rows, int64_t img_cols, double bv_h, double bv_w, double s_img,
+                              double s_bv) {
+    Geometry g = make_geometry(NAN, NAN, bv_h, bv_w, s_img, s_bv);
+    g.wq = (double)img_cols;
+    g.hq = (double)img_rows;
+    const bool fits = img_rows >= 1 && img_cols >= 1 && (double)img_rows * (double)img_cols < 4e18;
+    g.n_pix = fits ? img_rows * img_cols : (img_rows >= 1 && img_cols >= 1 ? INT64_MAX : 0);
+    return g;
+}
+
 // produce_sparse_pooling_input (sparse_pool_utils.py:22-58) on one rounded
 // image index (ur, vr) and one voxel index (vx, vz).
 struct Produced {

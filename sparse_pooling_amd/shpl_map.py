@@ -366,14 +366,20 @@ def build_index_batch(points, voxels, point_offsets, P, im_size, bv_size, stride
 
 
 def build_index_levels(points, voxels, point_offsets, P, im_size, levels, max_points, mval=None, ref_outputs=False,
-                       ws=None, point_counts=None):
+                       ws=None, point_counts=None, im_sizes=None, img_hws=None):
     """build_index_batch for several fusion levels in one pass over the points (shpl_build_index_levels): the
     list the reference's dataset builds by running its index builders once per level over the same frame
     (kitti_dataset.py:374-389; rpn_model.py:841-862 reads entries [0] and [1]). levels: a sequence of
     (stride, bv_size), at most L.MAX_INDEX_LEVELS. Returns one IndexBatch per level, each with its own ShplMap --
     what build_index_batch returns for that level's stride and bv_size, bit for bit -- so the CSR builders, the
     pulls and the fused modules take them unchanged. The maps share one err tensor (the OR over the levels).
-    All inputs are device tensors; nothing synchronises the host."""
+    All inputs are device tensors; nothing synchronises the host.
+    im_sizes ([n_frames, 2] device tensor of (W, H), as KittiFrames.im_size): a batch of mixed image sizes
+    (shpl_build_index_levels_ragged) -- every frame is clipped once against its own size and clamped per level
+    against its own strided size; im_size is then the padded full-resolution size, and every level has one padded
+    image feature map, img_hws[l] = (rows, cols) in that level's strided pixels (default: im_size's strided size
+    at the level). Each IndexBatch is what build_index_batch(im_sizes=, img_hw=img_hws[l]) returns for its level,
+    bit for bit, img_hw_frames included."""
     dev = points.device
     points, point_offsets, P = points.contiguous(), point_offsets.contiguous(), P.contiguous()
     if voxels.stride(1) != 1:
@@ -397,14 +403,30 @@ def build_index_levels(points, voxels, point_offsets, P, im_size, levels, max_po
     arr = L.index_levels([(stride, bv_size, *o) for (stride, bv_size), o in zip(levels, outs)])
     lead = L.index_args(n_frames, point_offsets, point_counts, max_points, points, voxels, P, im_size, (0, 0), (1, 1),
                         mval, None, None, None)
-    L.check(L.lib().shpl_build_index_levels(*lead[:12], lead[16], len(levels), arr, L.ptr(frame_off), L.ptr(err),
-                                            L.ptr(ws), ws.numel(), L.stream_of(dev)), "shpl_build_index_levels")
+    # every level's image feature map (rows, cols): im_size's strided size, or (ragged) the padded map given
+    maps = [(int(np.floor(im_size[1] / float(s[0]))), int(np.floor(im_size[0] / float(s[0])))) for s, _ in levels]
+    tail = (L.ptr(frame_off), L.ptr(err), L.ptr(ws), ws.numel(), L.stream_of(dev))
+    if im_sizes is None and img_hws is None:
+        L.check(L.lib().shpl_build_index_levels(*lead[:12], lead[16], len(levels), arr, *tail),
+                "shpl_build_index_levels")
+    else:
+        if im_sizes is None:
+            raise ValueError("img_hws goes with im_sizes (the frames' own image sizes)")
+        if img_hws is not None:
+            if len(img_hws) != len(levels):
+                raise ValueError(f"one padded map per level: {len(levels)} levels, {len(img_hws)} maps")
+            maps = [(int(hw[0]), int(hw[1])) for hw in img_hws]
+        im_sizes = im_sizes.to(device=dev, dtype=torch.float64).reshape(n_frames, 2).contiguous()
+        L.check(L.lib().shpl_build_index_levels_ragged(*lead[:10], L.ptr(im_sizes), lead[16], len(levels), arr,
+                                                       L.index_level_maps(maps), *tail),
+                "shpl_build_index_levels_ragged")
     batches = []
-    for (stride, bv_size), (cell, pix, val, mij, flip, frame_nnz) in zip(levels, outs):
+    for (stride, bv_size), (hq, wq), (cell, pix, val, mij, flip, frame_nnz) in zip(levels, maps, outs):
         s_img, s_bv = float(stride[0]), float(stride[1])
-        wq, hq = int(np.floor(im_size[0] / s_img)), int(np.floor(im_size[1] / s_img))
         bhq, bwq = int(np.floor(bv_size[0] / s_bv)), int(np.floor(bv_size[1] / s_bv))
         smap = ShplMap(cell, None, val, pix, N, n_frames * bhq * bwq, n_frames * hq * wq, N, dev,
                        frame_off=frame_off, frame_nnz=frame_nnz, n_frames=n_frames, err=err)
-        batches.append(IndexBatch(smap, mij, flip, frame_nnz, frame_off, n_frames, (bhq, bwq), (hq, wq)))
+        # (ragged) every frame's own strided (rows, cols) at this level: IEEE division, as the device's
+        hw_frames = None if im_sizes is None else torch.floor(im_sizes / s_img).flip(1).to(torch.int64)
+        batches.append(IndexBatch(smap, mij, flip, frame_nnz, frame_off, n_frames, (bhq, bwq), (hq, wq), hw_frames))
     return batches
