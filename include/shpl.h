@@ -763,6 +763,22 @@ int shpl_conv3x3_rows_form(int dtype, int n_frames, int64_t h, int64_t w, const 
                            const shpl_csr *pool, const int64_t *d_frame_off, const void *d_weights, int64_t c_out,
                            int act, const void *d_out, int64_t out_stride, int stats, int *rows_form);
 
+/* Whether shpl_conv3x3 with these arguments (the same as shpl_conv3x3_rows_form's) runs the wide bf16 kernel
+ * (k_conv_wide: input channels in whole chunks of 64, more than 64 of them, output channels in whole blocks
+ * of 256, no statistics, 16-byte aligned rows, offsets and pointers), and on which second operand. *form:
+ *   0  not the wide kernel (the row-streaming or the tiled form, f32, or no pixel);
+ *   1  wide, B a dense map or absent;
+ *   2  wide over the compact pooled runs (one pooled row per occupied cell, computed into the workspace);
+ *   3  wide over the pooled map, materialised in the workspace by shpl_pull (a map past the occupancy
+ *      table: h * ceil(w / 32) > 18432 words, or pool->nnz_cap * c_b * 2 >= 2^31 bytes).
+ * The wide kernel addresses a frame's rows by signed 32-bit byte offsets: a call whose A, dense B or
+ * materialised map has h * w * row stride * 2 >= 2^31 bytes answers 0 and runs the tiled form, which
+ * addresses in 64 bits. The same predicate shpl_conv3x3 decides by. */
+int shpl_conv3x3_wide_form(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a, int64_t a_stride,
+                           int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride, int64_t b_off, int64_t c_b,
+                           const shpl_csr *pool, const int64_t *d_frame_off, const void *d_weights, int64_t c_out,
+                           int act, const void *d_out, int64_t out_stride, int stats, int *form);
+
 /* BatchNorm in training mode over rows x c, from d_stats of shpl_conv3x3 and
  * count = rows: mean = sum/count, var = sumsq/count - mean^2,
  * y = act((x - mean) * gamma / sqrt(var + eps) + beta), written to d_y

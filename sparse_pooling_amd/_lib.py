@@ -226,6 +226,9 @@ def _declare(lib):
         "shpl_conv3x3_rows_form": (i32, [i32, i32, i64, i64, p, i64, i64, i64, p, i64, i64, i64,
                                          ctypes.POINTER(ShplCsr), p, p, i64, i32, p, i64, i32,
                                          ctypes.POINTER(ctypes.c_int)]),
+        "shpl_conv3x3_wide_form": (i32, [i32, i32, i64, i64, p, i64, i64, i64, p, i64, i64, i64,
+                                         ctypes.POINTER(ShplCsr), p, p, i64, i32, p, i64, i32,
+                                         ctypes.POINTER(ctypes.c_int)]),
         "shpl_batch_norm": (i32, [i32, i64, p, p, i64, i64, p, d, ctypes.c_float, p, p, i32, p, p,
                                   ctypes.c_float, p, p, p, p]),
         "shpl_batch_norm_backward_workspace_bytes": (i32, [i64, i64, psz]),

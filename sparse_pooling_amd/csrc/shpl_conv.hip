@@ -606,6 +606,10 @@ struct ConvPlan : TilePlan {
     int64_t pool_cap;
 };
 
+// Whether rows of `stride` bf16 elements keep every byte offset inside a frame of px > 0 pixels below 2^31
+// (k_conv_wide's halo offsets are signed 32-bit).
+bool frame_fits31(int64_t px, int64_t stride) { return stride <= ((1LL << 30) - 1) / px; }
+
 // The tiles are TH x TW output pixels at both dtypes, for the forward and the weight gradient alike. pool_cap:
 // the pooling CSR's entry capacity (pooled forward: sizes the compact buffer of pooled runs).
 int conv_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_t c_b, int64_t c_out, bool pooled,
@@ -631,7 +635,8 @@ int conv_plan(int dtype, int n_frames, int64_t h, int64_t w, int64_t c_a, int64_
     pl->rows = dtype == SHPL_BF16 && pl->qa + pl->qb <= 4 && c_a % 8 == 0 && c_b % 8 == 0 && h > 0 &&
                w > 0 && rows::supported(pl->qa + pl->qb, pl->qa) && (!pooled || occ_fits) && n_items < (1LL << 31);
     pl->wide = dtype == SHPL_BF16 && !stats && !pl->rows && h > 0 && w > 0 &&
-               wide::supported(c_a, c_b, c_out) && (int64_t)n_frames * h * w * (c_b > 0 ? c_b : 1) < (1LL << 40);
+               wide::supported(c_a, c_b, c_out) && (int64_t)n_frames * h * w * (c_b > 0 ? c_b : 1) < (1LL << 40) &&
+               (!pooled || occ_fits || frame_fits31(h * w, c_b));  // the materialised map, in rows of c_b
     pl->wide_cmp = pl->wide && pooled && occ_fits;
     pl->pool_cap = pool_cap;
     size_t wp_bytes = (size_t)pl->n_cob * (pl->qa + pl->qb) * W_ROWS * chunk_b;
@@ -711,6 +716,21 @@ bool rows_forward(const ConvPlan &pl, const ConvArgs &a, bool pooled, bool stats
            (!stats || (a.act == 0 && rows::supported_st(pl.qa + pl.qb, pl.qa, pooled)));
 }
 
+// Which form of the wide bf16 kernel (k_conv_wide) a forward with this plan and these arguments runs: 0 none
+// (the row or tiled kernels), 1 with B dense or absent, 2 over the compact pooled runs (wide::prep), 3 over
+// the pooled map materialised by shpl_pull. The one predicate conv_launch and shpl_conv3x3_wide_form share.
+// k_conv_wide keeps a lane's halo source as a signed 32-bit byte offset inside its frame, so every map it
+// reads by rows -- A, a dense B, the materialised map -- must end within 2^31 bytes of its frame's start; the
+// tiled kernel, which addresses in 64 bits, takes the rest.
+int wide_forward(const ConvPlan &pl, const ConvArgs &a, const shpl_csr *pool, bool stats) {
+    if (!pl.wide || stats || a.out2 || !a.vec_a || (a.c_b != 0 && !a.vec_b) || !a.vec_out || a.n_frames <= 0)
+        return 0;
+    const int64_t px = (int64_t)a.h * a.w;
+    if (!frame_fits31(px, a.a_stride)) return 0;
+    if (!pool) return a.c_b == 0 || frame_fits31(px, a.b_stride) ? 1 : 0;
+    return pl.wide_cmp ? 2 : 3;  // the map's rows of c_b elements: conv_plan has counted them
+}
+
 // The wide bf16 form (k_conv_wide). Pooled: B's rows are the compact pooled runs (wide::prep), or -- past
 // the occupancy table -- the pooled map, materialised first by shpl_pull (the same arithmetic as the tiled
 // staging: the conv of [a || map] is the fused conv's).
@@ -763,8 +783,7 @@ int conv_launch(const ConvPlan &pl, ConvArgs &a, void *ws, bool pooled, bool sta
                 const int64_t *frame_off, double *d_stats, hipStream_t s, int transpose = 0,
                 const shpl_csr *pool = nullptr) {
     if constexpr (sizeof(T) == 2) {
-        if (pl.wide && !stats && !transpose && !a.out2 && a.vec_a && (a.c_b == 0 || a.vec_b) && a.vec_out &&
-            a.n_frames > 0 && (!pooled || pool))
+        if (!transpose && (!pooled || pool) && wide_forward(pl, a, pooled ? pool : nullptr, stats))
             return conv_wide_launch(pl, a, ws, pooled ? pool : nullptr, frame_off, w, s);
     }
     if (const int rc = pack_weights<T>(a, w, pl.n_cob, transpose, s)) return rc;
@@ -1088,6 +1107,24 @@ extern "C" int shpl_conv3x3_rows_form(int dtype, int n_frames, int64_t h, int64_
                                  const_cast<void *>(d_out), out_stride, stats != 0, nullptr, 0, false, pl, a, &empty);
     if (rc) return rc;
     *rows_form = !empty && dtype == SHPL_BF16 && rows_forward(pl, a, pool != nullptr, stats != 0);
+    return SHPL_OK;
+}
+
+extern "C" int shpl_conv3x3_wide_form(int dtype, int n_frames, int64_t h, int64_t w, const void *d_a,
+                                      int64_t a_stride, int64_t a_off, int64_t c_a, const void *d_b, int64_t b_stride,
+                                      int64_t b_off, int64_t c_b, const shpl_csr *pool, const int64_t *d_frame_off,
+                                      const void *d_weights, int64_t c_out, int act, const void *d_out,
+                                      int64_t out_stride, int stats, int *form) {
+    if (!form) return SHPL_ERR_ARG;
+    *form = 0;
+    ConvPlan pl;
+    ConvArgs a;
+    bool empty;
+    const int rc = forward_setup(dtype, n_frames, h, w, {d_a, a_stride, a_off, c_a}, {d_b, b_stride, b_off, c_b}, pool,
+                                 d_frame_off, d_weights, c_out, nullptr, nullptr, nullptr, act,
+                                 const_cast<void *>(d_out), out_stride, stats != 0, nullptr, 0, false, pl, a, &empty);
+    if (rc) return rc;
+    *form = !empty && dtype == SHPL_BF16 ? wide_forward(pl, a, pool, stats != 0) : 0;
     return SHPL_OK;
 }
 

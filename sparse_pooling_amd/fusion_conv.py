@@ -63,21 +63,32 @@ def conv_ws_bytes(dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap, stats):
     return L.ws_bytes("shpl_conv3x3", dtype, n_frames, h, w, c_a, c_b, c_out, pool_cap, bool(stats))
 
 
-def rows_form(a, weights, b=None, pool=None, frame_off=None, relu=True, stats=False, out=None, c_out=None):
-    """Whether conv3x3 with these arguments runs the row-streaming form (shpl_conv3x3_rows_form): only then
-    does its workspace hold the pooled operand shpl_conv3x3_wgrad_reuse reads. ``out`` None: a fresh
-    contiguous output (16-byte aligned, as torch allocates)."""
+def _form(symbol, a, weights, b, pool, frame_off, relu, stats, out, c_out):
+    """The answer of a dispatch query of conv3x3 (shpl_conv3x3_rows_form, shpl_conv3x3_wide_form)."""
     B, H, W, Ca = (int(s) for s in a.shape)
     Cb = 0 if b is None else int(b.shape[-1])
     Cout = int(weights.shape[3]) if c_out is None else int(c_out)
     flag = ctypes.c_int(0)
     out_ptr = L.ptr(out) if out is not None else ctypes.c_void_p(256)  # a stand-in aligned address
-    L.check(L.lib().shpl_conv3x3_rows_form(L.dtype_code(a), B, H, W, L.ptr(a), Ca, 0, Ca, L.ptr(b), Cb, 0, Cb,
-                                           None if pool is None else pool.ref(), L.ptr(frame_off), L.ptr(weights),
-                                           Cout, L.ACT_RELU if relu else L.ACT_NONE, out_ptr,
-                                           Cout if out is None else int(out.stride(2)), int(bool(stats)),
-                                           ctypes.byref(flag)), "shpl_conv3x3_rows_form")
-    return bool(flag.value)
+    L.check(getattr(L.lib(), symbol)(L.dtype_code(a), B, H, W, L.ptr(a), Ca, 0, Ca, L.ptr(b), Cb, 0, Cb,
+                                     None if pool is None else pool.ref(), L.ptr(frame_off), L.ptr(weights),
+                                     Cout, L.ACT_RELU if relu else L.ACT_NONE, out_ptr,
+                                     Cout if out is None else int(out.stride(2)), int(bool(stats)),
+                                     ctypes.byref(flag)), symbol)
+    return flag.value
+
+
+def rows_form(a, weights, b=None, pool=None, frame_off=None, relu=True, stats=False, out=None, c_out=None):
+    """Whether conv3x3 with these arguments runs the row-streaming form (shpl_conv3x3_rows_form): only then
+    does its workspace hold the pooled operand shpl_conv3x3_wgrad_reuse reads. ``out`` None: a fresh
+    contiguous output (16-byte aligned, as torch allocates)."""
+    return bool(_form("shpl_conv3x3_rows_form", a, weights, b, pool, frame_off, relu, stats, out, c_out))
+
+
+def wide_form(a, weights, b=None, pool=None, frame_off=None, relu=True, stats=False, out=None, c_out=None):
+    """Which form of the wide bf16 kernel conv3x3 with these arguments runs (shpl_conv3x3_wide_form): 0 none,
+    1 with b dense or absent, 2 over the compact pooled runs, 3 over the materialised pooled map."""
+    return _form("shpl_conv3x3_wide_form", a, weights, b, pool, frame_off, relu, stats, out, c_out)
 
 
 # A forward of the library over [a || b]: its symbol (the workspace query is <symbol>_workspace_bytes), the output's

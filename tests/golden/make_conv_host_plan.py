@@ -1,5 +1,5 @@
 """Record tests/golden/conv_host_plan.json: what the conv / BatchNorm host code of libshpl.so answers
-without a GPU -- workspace sizes, the row-streaming predicate, and the status of calls it rejects before
+without a GPU -- workspace sizes, the row-streaming and the wide kernel's predicate, and the status of calls it rejects before
 its first HIP call. tests/test_conv_host_plan.py replays every row against the built library.
 
 Each row is {"fn", "args", "status", "out"}. args are the C arguments in order, with
@@ -20,7 +20,7 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 TABLE = os.path.join(HERE, "conv_host_plan.json")
 
 F32, BF16 = 0, 1
-INT_OUT = {"shpl_conv3x3_rows_form"}  # writes an int; the other "OUT" calls a size_t
+INT_OUT = {"shpl_conv3x3_rows_form", "shpl_conv3x3_wide_form"}  # write an int; the other "OUT" calls a size_t
 
 
 def replay(lib, L, fn, args):
@@ -124,6 +124,66 @@ def rows_form_calls():
     yield rows_form(*g, pool=csr(176 * 200 - 1))
     yield rows_form(*g, pool=one, frame_off=None)
     yield rows_form(*g, out=None)
+
+
+def wide_form(*args, **kw):
+    """shpl_conv3x3_wide_form: rows_form's arguments."""
+    return "shpl_conv3x3_wide_form", rows_form(*args, **kw)[1]
+
+
+def wide_form_calls():
+    """Each form (out 1, 2, 3), then one row per rule of wide::supported and of the shared predicate (out 0)."""
+    g, px = (BF16, NF, 17, 33), NF * 17 * 33
+    yield wide_form(*g, 128, 0, 256)                                     # 1: A only
+    yield wide_form(*g, 64, 64, 256)                                     # 1: the smallest, Q = 2
+    yield wide_form(*g, 128, 64, 256)
+    yield wide_form(*g, 256, 256, 512)                                   # 1: two output blocks
+    yield wide_form(*g, 64, 64, 256, act=1)
+    yield wide_form(*g, 64, 64, 256, pool=csr(px))                       # 2: the compact pooled runs
+    yield wide_form(*g, 64, 64, 256, pool=csr(px, cap=0))                # 2: an empty pool
+    yield wide_form(BF16, NF, 18432, 3, 64, 64, 256, pool=csr(NF * 18432 * 3))  # 2: the occupancy table's last map
+    yield wide_form(BF16, NF, 18433, 3, 64, 64, 256, pool=csr(NF * 18433 * 3))  # 3: past OCC_MAX_WORDS
+    yield wide_form(*g, 64, 64, 256, pool=csr(px, cap=(1 << 24) - 1))    # 2: pool_cap * c_b * 2 = 2^31 - 128
+    yield wide_form(*g, 64, 64, 256, pool=csr(px, cap=1 << 24))          # 3: pool_cap * c_b * 2 = 2^31
+    # wide::supported
+    yield wide_form(*g, 0, 128, 256)                                     # c_a = 0
+    yield wide_form(*g, 32, 96, 256)                                     # c_a = 32
+    yield wide_form(*g, 64, 96, 256)                                     # c_b no multiple of 64
+    yield wide_form(*g, 64, 0, 256)                                      # c_a + c_b = 64: the row form's
+    yield wide_form(*g, 32, 32, 256)
+    yield wide_form(*g, 64, 64, 128)                                     # c_out no multiple of 256
+    yield wide_form(*g, 64, 64, 257)
+    yield wide_form(F32, NF, 17, 33, 64, 64, 256)
+    yield wide_form(*g, 64, 64, 256, stats=1)
+    yield wide_form(BF16, 0, 17, 33, 64, 64, 256)                        # no frame
+    # alignment: offsets, rows and pointers off the 16-byte grid (a whole piece off it is fine)
+    yield wide_form(*g, 64, 64, 256, a_off=8, b_off=8, out_stride=264)   # 1
+    yield wide_form(*g, 64, 64, 256, a_off=3)
+    yield wide_form(*g, 64, 64, 256, b_off=3)
+    yield wide_form(*g, 64, 64, 256, b_off=3, pool=csr(px))
+    yield wide_form(*g, 64, 64, 256, a_stride=68)
+    yield wide_form(*g, 64, 64, 256, out_stride=260)
+    yield wide_form(*g, 64, 64, 256, a="Q")
+    yield wide_form(*g, 64, 64, 256, b="Q")
+    yield wide_form(*g, 64, 64, 256, out="Q")
+    # a frame's rows end 2^31 bytes or more past its start (k_conv_wide's 32-bit halo offsets): A, a dense B, the
+    # materialised map in rows of c_b; the compact runs are bounded by pool_cap
+    big = (BF16, 1, 1025, 1024, 64, 64, 256)
+    yield wide_form(BF16, 1, 1024, 1024, 64, 64, 256, a_stride=1016, b_stride=1016)  # 1: 2^31 - 2^24 bytes
+    yield wide_form(BF16, 1, 1024, 1024, 64, 64, 256, a_stride=1024)
+    yield wide_form(*big, a_stride=1024)
+    yield wide_form(*big, b_stride=1024)
+    yield wide_form(*big, a_stride=1024, b_stride=1024)
+    yield wide_form(*big, a_stride=1024, pool=csr(1025 * 1024))
+    yield wide_form(*big, b_stride=1024, pool=csr(1025 * 1024))          # 3: the pooled image's rows do not count
+    yield wide_form(*big)                                                # 1: contiguous, 2^27 + 2^17 bytes
+    yield wide_form(BF16, 1, 1 << 20, 15, 64, 64, 256, pool=csr(15 << 20))  # 3: a map of 15 * 2^27 bytes
+    yield wide_form(BF16, 1, 1 << 20, 16, 64, 64, 256, pool=csr(16 << 20))  # a map of 2^31 bytes
+    # rejected: the checks it shares with shpl_conv3x3
+    yield wide_form(*g, 64, 64, 256, act=2)
+    yield wide_form(*g, 64, 64, 256, weights=None)
+    yield wide_form(*g, 64, 64, 256, pool=csr(px - 1))
+    yield wide_form(*g, 64, 64, 256, out=None)
 
 
 def conv(dt=BF16, nf=1, h=176, w=200, a="P", a_stride=32, a_off=0, ca=32, b="P", b_stride=32, b_off=0, cb=32,
@@ -287,7 +347,8 @@ def record():
     from sparse_pooling_amd import _lib as L
     lib = L.lib()
     table = {}
-    for kind, calls in (("workspace", workspace_calls), ("rows_form", rows_form_calls), ("rejected", rejected_calls)):
+    for kind, calls in (("workspace", workspace_calls), ("rows_form", rows_form_calls), ("wide_form", wide_form_calls),
+                        ("rejected", rejected_calls)):
         table[kind] = []
         for fn, args in calls():
             rc, out = replay(lib, L, fn, args)

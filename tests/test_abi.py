@@ -109,6 +109,28 @@ def test_argument_validation_is_host_side():
         assert rf.value == want, (dt, cb, stats)
     assert lib.shpl_conv3x3_rows_form(L.BF16, 1, 176, 200, P, 32, 0, 32, P, 32, 0, 32, ctypes.byref(ccell1), P, P,
                                       16, L.ACT_NONE, P, 16, 0, ctypes.byref(rf)) == L.OK and rf.value == 0
+    # the wide kernel's predicate (shpl_conv3x3_wide_form): 1 dense, 2 over the compact pooled runs, 3 over the
+    # materialised map (past the occupancy table); 0 at f32, with statistics, at 32 + 32 channels (the row form) and
+    # for a frame whose rows end 2^31 bytes or more past its start
+    wf = ctypes.c_int(-1)
+    cwide = L.ShplCsr(256, 256, 256, None, 18433 * 3, 1000)
+
+    def wide(dt, h, w, ca, cb, pool, stats, a_stride=None, co=256):
+        assert lib.shpl_conv3x3_wide_form(dt, 1, h, w, P, ca if a_stride is None else a_stride, 0, ca, P, cb, 0, cb,
+                                          pool, P if pool is not None else N, P, co, L.ACT_RELU, P, co, stats,
+                                          ctypes.byref(wf)) == L.OK
+        return wf.value
+    assert wide(L.BF16, 176, 200, 64, 64, N, 0) == 1
+    assert wide(L.BF16, 176, 200, 64, 64, ctypes.byref(ccell1), 0) == 2
+    assert wide(L.BF16, 18433, 3, 64, 64, ctypes.byref(cwide), 0) == 3
+    assert wide(L.F32, 176, 200, 64, 64, N, 0) == 0
+    assert wide(L.BF16, 176, 200, 64, 64, N, 1) == 0
+    assert wide(L.BF16, 176, 200, 32, 32, N, 0) == 0
+    assert wide(L.BF16, 176, 200, 64, 64, N, 0, co=128) == 0
+    assert wide(L.BF16, 1024, 1024, 64, 64, N, 0, a_stride=1016) == 1
+    assert wide(L.BF16, 1025, 1024, 64, 64, N, 0, a_stride=1024) == 0
+    assert lib.shpl_conv3x3_wide_form(L.BF16, 1, 176, 200, P, 64, 0, 64, P, 64, 0, 64, N, N, P, 256, L.ACT_RELU, P,
+                                      256, 0, N) == L.ERR_ARG
     # the occupancy-limited input gradient: no pool / forward workspace / second map, keys that are not the map's,
     # a split outside (0, c_dx), a forward workspace smaller than that forward's plan -- all before any launch
     dg = (L.BF16, 1, 176, 200, P, 32, 32, P, 64, P, 32)

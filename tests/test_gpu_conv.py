@@ -188,6 +188,10 @@ def test_retinanet_fusion_conv_shape(dtype):
     conv.weights = _t(w).to(dt)
     conv.bias = _t(np.random.default_rng(4).standard_normal(Co).astype(np.float32) * 0.5)
     bv_fused = sm.pool_img_to_bev(ib.map, ti, tb.shape, bev=tb)
+    # bf16: the wide kernel, over the compact pooled runs fused and over one dense source unfused
+    pool = ib.map.csr(*fc.SIDE_BEV.fwd)
+    assert fc.wide_form(tb, conv.weights, b=ti, pool=pool, frame_off=ib.map.frame_off) == (2 if bf else 0)
+    assert fc.wide_form(bv_fused, conv.weights) == (1 if bf else 0)
     y_unf = conv(bv_fused)
     y_fus = conv.fused(tb, ti, ib.map)
     torch.cuda.synchronize()
@@ -236,9 +240,11 @@ def test_bf16_wide_conv_dense(shape):
     ta, tw = _bf16(a), _bf16(w)
     tb = _bf16(b) if cb else None
     f32 = lambda v: None if v is None else _t(v)  # noqa: E731
+    assert fc.wide_form(ta, tw, b=tb, relu=relu) == 1
     y = fc.conv3x3(ta, tw, b=tb, center=f32(center), scale=f32(scale), shift=f32(shift), relu=relu)
     x = np.concatenate([a, b], -1) if cb else a
     if cb:  # two sources == one concatenated source, bitwise (the same K order: 64-channel chunks)
+        assert fc.wide_form(_bf16(x), tw, relu=relu) == 1
         y1 = fc.conv3x3(_bf16(x), tw, center=f32(center), scale=f32(scale), shift=f32(shift), relu=relu)
         assert torch.equal(y, y1)
     ref = orc.conv3x3(x, w, center, scale, shift, relu)
@@ -299,9 +305,11 @@ def test_bf16_wide_fused_materialised_map():
             fc.conv_ws_bytes(L.BF16, 1, hb, wb, cb, ci, cout, None, False)) >= R * ci * 2
     wts = _bf16(_weights(cb + ci, cout, 92))
     bias = _t(np.random.default_rng(93).standard_normal(cout).astype(np.float32) * 0.5)
+    assert fc.wide_form(bev, wts, b=img, pool=pool, frame_off=smap.frame_off, relu=True) == 3
     fused = fc.conv3x3(bev, wts, b=img, pool=pool, frame_off=smap.frame_off, shift=bias, relu=True)
     bv = sm.pool_img_to_bev(smap, img, (1, hb, wb, cb), bev=bev)
     assert bool((bv[..., cb:] != 0).any())
+    assert fc.wide_form(bv[..., :cb].contiguous(), wts, b=bv[..., cb:].contiguous(), relu=True) == 1
     unf = fc.conv3x3(bv[..., :cb].contiguous(), wts, b=bv[..., cb:].contiguous(), shift=bias, relu=True)
     torch.cuda.synchronize()
     assert torch.equal(fused, unf)

@@ -313,6 +313,8 @@ def case_wide_prep(key):
     tw = _bf16(w)
     bias = np.random.default_rng(52).standard_normal(cout).astype(np.float32) * 0.5
     assert not fc.rows_form(ta, tw, b=tb, pool=pool, frame_off=foff, relu=True)
+    assert fc.wide_form(ta, tw, b=tb, pool=pool, frame_off=foff, relu=True) == 2  # over the compact pooled runs
+    assert fc.wide_form(mat[..., :ca].contiguous(), tw, b=mat[..., ca:].contiguous(), relu=True) == 1
     y = fc.conv3x3(ta, tw, b=tb, pool=pool, frame_off=foff, shift=_t(bias), relu=True)
     yu = fc.conv3x3(mat[..., :ca].contiguous(), tw, b=mat[..., ca:].contiguous(), shift=_t(bias), relu=True)
     assert torch.equal(y, yu)
