@@ -388,7 +388,9 @@ int shpl_mv3d_voxels_aug(int n_frames, const int64_t *d_point_offsets, int64_t t
  *   d_rect      [n_frames,3,4] f64 rows 0-2 of R0_rect4 . Tr_velo_to_cam4 (numpy's
  *               4x4 product on the host, as calib_utils.py:404 forms it)
  *   d_P, d_im_size  [n_frames,3,4] P2 and [n_frames,2] (w, h); both NULL = no filter
- *   min_intensity   NaN = none (see DESIGN.md for the reference's mask bug)
+ *   min_intensity   NaN = none (see DESIGN.md for the reference's mask bug); any
+ *               number, 0 included: keep (double)i > min_intensity (the reference's
+ *               "0 means none" and f32 comparison belong to kitti.get_lidar_point_cloud)
  *   d_flip      optional [n_frames] i32, nonzero = negate x of the kept points
  * Outputs, capacity layout: d_points [N,3] f64 (frame f's kept points at
  * [off[f], off[f] + d_counts[f]) in scan order, NaN rows after). The result

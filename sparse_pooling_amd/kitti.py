@@ -115,6 +115,9 @@ def velo_to_cam_batch(xyzi, point_offsets, rect, P=None, im_size=None, min_inten
     xyzi [N,4] f32, point_offsets [F+1] i64, rect [F,3,4] f64 (``rect_matrix``),
     P [F,3,4] f64 and im_size [F,2] (w, h) -- both None: no FOV filter --, flip [F]
     (nonzero: kitti_aug.flip_point_cloud). All device tensors (or array-likes).
+    min_intensity: None = no intensity filter (NaN in the C ABI); any number, 0 included, keeps the points
+    with f64(i) > min_intensity -- the reference's "0 means none" and its f32 comparison are rules of the
+    single-frame wrapper ``get_lidar_point_cloud``, not of this entry point.
     Returns a VeloBatch: points [N,3] f64 with frame f's kept points at
     [off[f], off[f] + counts[f]) in scan order (NaN rows after)."""
     dev = xyzi.device
@@ -161,12 +164,16 @@ def get_lidar_point_cloud(img_idx, calib_dir, velo_dir, im_size=None, min_intens
     """obj_utils.get_lidar_point_cloud (obj_utils.py:220-268) with the transform and the
     filter on the device: returns the (3, N') camera-frame cloud as a device f64 tensor.
     im_size [w, h]. min_intensity compares each kept point's own intensity (the
-    reference's mask-length bug is not replicated)."""
+    reference's mask-length bug is not replicated); as there, a false
+    min_intensity (None, 0) means no intensity filter (``if not min_intensity``,
+    obj_utils.py:262), and the threshold is compared in f32, numpy's type for an f32
+    array against a Python float (obj_utils.py:266)."""
     fc = read_calibration(calib_dir, img_idx)
     xyzi = read_lidar_xyzi(velo_dir, img_idx)
     dev = torch.device("cuda", torch.cuda.current_device())
     off = torch.tensor([0, xyzi.shape[0]], dtype=torch.int64, device=dev)
     filt = im_size is not None and len(im_size) > 0
+    min_intensity = float(np.float32(min_intensity)) if min_intensity else None
     b = velo_to_cam_batch(torch.as_tensor(xyzi).to(dev), off, rect_matrix(fc)[None],
                           fc.p2[None] if filt else None, [list(im_size)] if filt else None, min_intensity)
     k = int(b.counts[0].item())

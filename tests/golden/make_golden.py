@@ -22,7 +22,7 @@ Reference functions executed (file:line, relative to /root/reference):
   ``kitti_aug.flip_point_cloud`` / ``flip_stereo_calib_p2`` / ``flip_ground_plane``
   (avod/avod/datasets/kitti/kitti_aug.py:24-29, 88-121) on synthetic KITTI files
 
-Run:  python tests/golden/make_golden.py [case ...]   (e.g. ``kitti``; no argument: all)
+Run:  python tests/golden/make_golden.py [case ...]   (e.g. ``kitti``, ``kitti_edges``; no argument: all)
 """
 import os
 import sys
@@ -388,6 +388,205 @@ def _kitti_case():
     np.savez_compressed(os.path.join(HERE, "kitti_frames.npz"), **rec)
 
 
+def _calib_text(calib):
+    return "".join(f"{k}: " + " ".join(f"{v:.12e}" for v in vals) + "\n" for k, vals in calib.items())
+
+
+def _rect_rows(fc):
+    """Rows 0-2 of lidar_to_cam_frame's 4x4 product (calib_utils.py:388-406), for the searches below."""
+    r0 = np.pad(fc.r0_rect, ((0, 1), (0, 1)), "constant", constant_values=0)
+    r0[3, 3] = 1
+    tf = np.pad(fc.tr_velodyne_to_cam, ((0, 1), (0, 0)), "constant", constant_values=0)
+    tf[3, 3] = 1
+    return np.dot(r0, tf)[0:3]
+
+
+def _cam(rect, p, dot):
+    a = (float(p[0]), float(p[1]), float(p[2]), 1.0)
+    return [dot(rect[r], a) for r in range(3)]
+
+
+def _kitti_edges_case():
+    """get_lidar_point_cloud / lidar_to_cam_frame / flip_point_cloud at the loader's edges
+    (tests/kitti_cases.py): strict bounds under an exact calibration, three grossly different
+    calibrations, the dgemm / dgemv boundary of the projection across chunks, the intensity
+    threshold. Keys: <record>_velo, _p2, _r0_rect, _tr, _im_size (w, h), _calib_text,
+    _point_cloud (FOV), _point_cloud_all (im_size=None), _flip_point_cloud[_all]."""
+    import tempfile
+    from wavedata.tools.core import calib_utils
+    from wavedata.tools.obj_detection import obj_utils
+    from avod.datasets.kitti import kitti_aug
+    rec = {}
+    f32 = np.float32
+    with tempfile.TemporaryDirectory() as d:
+        cdir, vdir = os.path.join(d, "calib"), os.path.join(d, "velodyne")
+        os.makedirs(cdir)
+        os.makedirs(vdir)
+        n_files = [0]
+
+        def write(calib, scan):
+            idx = n_files[0]
+            n_files[0] += 1
+            with open(os.path.join(cdir, "%06d.txt" % idx), "w") as fh:
+                fh.write(_calib_text(calib))
+            np.ascontiguousarray(scan, f32).tofile(os.path.join(vdir, "%06d.bin" % idx))
+            return idx, calib_utils.read_calibration(cdir, idx)
+
+        def cloud(idx, im_size=None, min_intensity=None):
+            with np.errstate(all="ignore"):
+                return obj_utils.get_lidar_point_cloud(idx, cdir, vdir, im_size=im_size, min_intensity=min_intensity)
+
+        def record(name, calib, scan, im_size, flips=("fov",), with_all=True):
+            idx, fc = write(calib, scan)
+            pc = cloud(idx, list(im_size))
+            rec.update({f"{name}_velo": np.ascontiguousarray(scan, f32), f"{name}_calib_text": np.array(_calib_text(calib)),
+                        f"{name}_p2": fc.p2, f"{name}_r0_rect": fc.r0_rect, f"{name}_tr": fc.tr_velodyne_to_cam,
+                        f"{name}_im_size": np.array(im_size, np.float64), f"{name}_point_cloud": pc})
+            if "fov" in flips:
+                rec[f"{name}_flip_point_cloud"] = kitti_aug.flip_point_cloud(pc)
+            if with_all:
+                pa = cloud(idx)
+                rec[f"{name}_point_cloud_all"] = pa
+                if "all" in flips:
+                    rec[f"{name}_flip_point_cloud_all"] = kitti_aug.flip_point_cloud(pa)
+            print(f"kitti_edges {name}: scan {len(scan)} -> FOV {pc.shape[1]}")
+            return idx, fc, pc
+
+        # kat: u = x, v = y, w = 1 exactly; camera z is the lidar z
+        W, H = 1242.0, 375.0
+        exact = dict(KITTI_CALIB)
+        exact["R0_rect"] = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+        exact["Tr_velo_to_cam"] = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]
+        exact["P2"] = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1]
+        den, tiny = np.nextafter(f32(0), f32(1)), np.finfo(f32).tiny
+
+        def around(b):
+            b = f32(b)
+            return [f32(0.0), f32(-0.0), den, tiny, b, np.nextafter(b, f32(0)), np.nextafter(b, f32(np.inf)),
+                    b - f32(0.5), f32(np.inf), f32(np.nan)]
+        zs = [f32(1.0), f32(0.0), f32(-0.0), den, f32(-1.0), f32(np.nan), f32(np.inf)]
+        pts = np.array([(x, y, z, 0.5) for x in around(W) for y in around(H) for z in zs], f32)
+        pts = pts[np.random.default_rng(61).permutation(len(pts))]
+        _, _, pc = record("kat", exact, pts, [W, H], flips=("fov", "all"))
+        assert 0 < pc.shape[1] < len(pts)
+
+        # calibs: one scan under three grossly different calibrations and image shapes
+        rng = np.random.default_rng(62)
+        calibs, sizes = [], []
+        for shape in [(375, 1242), (370, 1224), (376, 1241)]:
+            ang = np.deg2rad(rng.uniform(1.0, 4.0, 3) * rng.choice([-1, 1], 3))
+            cx, cy, cz = np.cos(ang)
+            sx, sy, sz = np.sin(ang)
+            rot = (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+                   @ np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]))
+            tr = np.array(KITTI_CALIB["Tr_velo_to_cam"]).reshape(3, 4)
+            tr = np.concatenate([rot @ tr[:, :3], tr[:, 3:] + rng.uniform(0.2, 0.6, (3, 1)) * rng.choice([-1, 1], (3, 1))], 1)
+            p2 = np.array(KITTI_CALIB["P2"]).reshape(3, 4)
+            p2[0, 0] = p2[1, 1] = p2[0, 0] * (1 + rng.uniform(0.03, 0.08) * rng.choice([-1, 1]))
+            p2[0, 2] *= 1 + rng.uniform(0.03, 0.08) * rng.choice([-1, 1])
+            p2[1, 2] *= 1 + rng.uniform(0.03, 0.08) * rng.choice([-1, 1])
+            calib = dict(KITTI_CALIB)
+            calib["Tr_velo_to_cam"], calib["P2"] = list(tr.reshape(-1)), list(p2.reshape(-1))
+            calibs.append(calib)
+            sizes.append([float(shape[1]), float(shape[0])])
+        for seed in range(620, 640):  # a scan on which every other frame's im_size alone changes the cloud too
+            scan = synthetic_scan(np.random.default_rng(seed), 2049)
+            ok = True
+            for k in range(3):
+                idx, _ = write(calibs[k], scan)
+                n_own = cloud(idx, sizes[k]).shape[1]
+                ok = ok and all(cloud(idx, sizes[o]).shape[1] != n_own for o in range(3) if o != k)
+            if ok:
+                break
+        assert ok
+        clouds = []
+        for k in range(3):
+            # (the scan once; the unfiltered cloud under the first calibration, the flip under the second)
+            _, _, pc = record(f"calibs{k}", calibs[k], scan, sizes[k], flips=("fov",) if k == 1 else (),
+                              with_all=k == 0)
+            if k:
+                del rec[f"calibs{k}_velo"]
+            clouds.append(pc)
+        for a in range(3):  # a wrong frame index must show
+            for b in range(a + 1, 3):
+                assert clouds[a].shape[1] != clouds[b].shape[1]
+                m = min(clouds[a].shape[1], clouds[b].shape[1])
+                assert not np.array_equal(clouds[a][:, :m], clouds[b][:, :m])
+
+        # one_front_late / two_front: the lone z > 0 point sits in chunk 2 of 3; its u differs between the
+        # dgemm chain and dgemv's order, and the image's width is the larger of the two
+        rng = np.random.default_rng(63)
+        n, at = 2500, 2300
+        behind = np.stack([rng.uniform(-30, -5, n), rng.uniform(-5, 5, n), rng.uniform(-1, 1, n),
+                           rng.uniform(0.5, 1, n)], 1).astype(f32)
+        _, fc0 = write(KITTI_CALIB, behind[:2])
+        rect, P = _rect_rows(fc0), fc0.p2
+        edge = None
+        for cand in synthetic_scan(rng, 4000):
+            c = _cam(rect, cand, _dot_chain)
+            if not c[2] > 0:
+                continue
+            (uc, vc), (ug, vg) = _uv(P, c, _dot_chain), _uv(P, c, _dot_gemv)
+            if uc != ug and min(uc, ug) > 1 and max(uc, ug) < 1241 and 1 < min(vc, vg) and max(vc, vg) < 374:
+                edge, w_edge = cand, max(uc, ug)
+                break
+        assert edge is not None
+        edge[3] = 0.9
+        one = behind.copy()
+        one[at] = edge
+        two = one.copy()
+        two[10] = [20.0, 60.0, 0.0, 0.9]  # in front, far left of the image
+        im = [w_edge, 375.0]
+        _, _, pc1 = record("one_front_late", KITTI_CALIB, one, im, with_all=False)
+        _, _, pc2 = record("two_front", KITTI_CALIB, two, im, flips=(), with_all=False)
+        del rec["two_front_velo"]  # one_front_late's scan with this row at index 10
+        rec["two_front_row10"] = two[10]
+        assert pc1.shape[1] + pc2.shape[1] == 1, (pc1.shape, pc2.shape)  # exactly one order keeps the point
+
+        # one_point: both products in dgemv's order; kept under that order alone
+        found = None
+        for cand in synthetic_scan(rng, 20000):
+            us = []
+            for d1 in (_dot_gemv, _dot_chain):
+                c = _cam(rect, cand, d1)
+                for d2 in (_dot_gemv, _dot_chain):
+                    us.append(_uv(P, c, d2) if c[2] > 0 else (np.nan, np.nan))
+            u = [q[0] for q in us]
+            v = [q[1] for q in us]
+            if (not np.isnan(u).any() and u[0] < min(u[1:]) and u[0] > 1 and max(u) < 1241 and min(v) > 1
+                    and max(v) < 374 and _cam(rect, cand, _dot_gemv) != _cam(rect, cand, _dot_chain)):
+                found, w_one = cand, min(u[1:])
+                break
+        assert found is not None
+        _, _, pc = record("one_point", KITTI_CALIB, found[None], [w_one, 375.0], flips=())
+        assert pc.shape[1] == 1
+
+        # all_front_intensity: the only scans on which the reference's min_intensity branch does not raise
+        # (its intensity mask has one entry per scan point, its image mask one per z > 0 point, obj_utils.py:266-267)
+        rng = np.random.default_rng(64)
+        n = 600
+        front = np.stack([rng.uniform(4, 60, n), rng.uniform(-25, 25, n), rng.uniform(-1.7, 1.0, n),
+                          rng.uniform(0, 1, n)], 1).astype(f32)
+        front[::7, 3] = 0.0  # KITTI scans hold many zero intensities
+        for k, t in enumerate((0.35, 0.1)):  # f32(0.35) < 0.35, f32(0.1) > 0.1
+            front[3 + 40 * k:500:97, 3] = f32(t)
+            front[5 + 40 * k:500:97, 3] = np.nextafter(f32(t), f32(1))
+            front[9 + 40 * k:500:97, 3] = np.nextafter(f32(t), f32(0))
+        idx, fc, pc = record("all_front_intensity", KITTI_CALIB, front, [1242.0, 375.0], flips=())
+        assert np.array_equal(cloud(idx, [1242.0, 375.0]), pc)
+        for key, t in (("035", 0.35), ("01", 0.1), ("0", 0)):
+            rec[f"all_front_intensity_min{key}"] = cloud(idx, [1242.0, 375.0], t)
+            print(f"kitti_edges all_front_intensity min_intensity {t}: {rec[f'all_front_intensity_min{key}'].shape[1]}")
+        assert rec["all_front_intensity_min0"].shape[1] == pc.shape[1] > rec["all_front_intensity_min035"].shape[1]
+
+        # lidar_to_cam_frame on 1, 2 and 5 points (f32-exact coordinates)
+        for k in (1, 2, 5):
+            xyz = synthetic_scan(rng, k)[:, :3].astype(np.float64)
+            rec[f"lidar_to_cam{k}_xyz"] = xyz
+            rec[f"lidar_to_cam{k}_out"] = calib_utils.lidar_to_cam_frame(xyz, fc)
+    np.savez_compressed(os.path.join(HERE, "kitti_edges.npz"), **rec)
+
+
 def main():
     _install_stubs()
     c1 = synth.CONFIG1
@@ -420,6 +619,7 @@ def main():
     _mv3d_voxel_case(dense=True)
     _kitti_case()
     _kitti_single_case()
+    _kitti_edges_case()
     _mv3d_calib_case()
 
 

@@ -1085,6 +1085,13 @@ def test_mv3d_augment_fv_index_transform():
 
 # ---------------------------------------------------------------- KITTI loader (§8f item 3)
 
+def _same_bytes(got, want):
+    """f64 arrays equal as bytes: assert_array_equal on floats cannot tell -0.0 from 0.0."""
+    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64))
+
+
 def test_kitti_loader_vs_reference_golden(kitti_dir):
     """get_lidar_point_cloud from the KITTI files, transform + FOV filter on the device."""
     from sparse_pooling_amd import kitti
@@ -1092,9 +1099,9 @@ def test_kitti_loader_vs_reference_golden(kitti_dir):
     for idx in (7, 8):
         h, w = g[f"{idx}_image_shape"]
         pc = kitti.get_lidar_point_cloud(idx, os.path.join(d, "calib"), os.path.join(d, "velodyne"), im_size=[w, h])
-        np.testing.assert_array_equal(_np(pc), g[f"{idx}_point_cloud"])
+        _same_bytes(_np(pc), g[f"{idx}_point_cloud"])
         pa = kitti.get_lidar_point_cloud(idx, os.path.join(d, "calib"), os.path.join(d, "velodyne"))
-        np.testing.assert_array_equal(_np(pa), g[f"{idx}_point_cloud_all"])
+        _same_bytes(_np(pa), g[f"{idx}_point_cloud_all"])
     fr = kitti.KittiFrames.from_dirs(os.path.join(d, "calib"), os.path.join(d, "velodyne"), os.path.join(d, "planes"),
                            [7, 8, 7], [tuple(g["7_image_shape"]), tuple(g["8_image_shape"]),
                                        tuple(g["7_image_shape"])], flips=[False, True, True])
@@ -1103,14 +1110,14 @@ def test_kitti_loader_vs_reference_golden(kitti_dir):
     off, n = _np(fr.point_offsets), _np(b.counts)
     want = [g["7_point_cloud"], g["8_flip_point_cloud"], g["7_flip_point_cloud"]]
     for f in range(3):
-        np.testing.assert_array_equal(_np(b.points[off[f]:off[f] + n[f]]).T, want[f])
+        _same_bytes(_np(b.points[off[f]:off[f] + n[f]]).T, want[f])
         assert np.isnan(_np(b.points[off[f] + n[f]:off[f + 1]])).all()
-    np.testing.assert_array_equal(_np(fr.planes[1]), g["8_flip_ground_plane"])
-    np.testing.assert_array_equal(_np(fr.P2[1]), g["8_flip_p2"])
+    _same_bytes(_np(fr.planes[1]), g["8_flip_ground_plane"])
+    _same_bytes(_np(fr.P2[1]), g["8_flip_p2"])
 
 
 def test_kitti_loader_batch_vs_oracle():
-    """Scans of ragged sizes across the 4096-point chunks, the intensity filter, flips."""
+    """Scans of ragged sizes across the 1024-point chunks (IDX_CHUNK), the intensity filter, flips."""
     from sparse_pooling_amd import kitti
     mg = synth
     rng = np.random.default_rng(5)
@@ -1131,7 +1138,7 @@ def test_kitti_loader_batch_vs_oracle():
         n = _np(b.counts)
         for f in range(6):
             e = orc.velo_to_cam(scans[f], rect, P, [1242, 375], min_intensity=mi, flip=flips[f])
-            np.testing.assert_array_equal(_np(b.points[off[f]:off[f] + n[f]]).T, e)
+            _same_bytes(_np(b.points[off[f]:off[f] + n[f]]).T, e)
         assert int(b.err.item()) == 0
 
 
@@ -1156,9 +1163,9 @@ def test_kitti_loader_single_column_vs_reference_golden(golden_dir):
         n = _np(b.counts)
         key = "point_cloud" if filt else "point_cloud_all"
         for f, want in ((0, g[f"0_{key}"]), (2, g[f"1_{key}"])):
-            np.testing.assert_array_equal(_np(b.points[off[f]:off[f] + n[f]]).T, want)
+            _same_bytes(_np(b.points[off[f]:off[f] + n[f]]).T, want)
         e = orc.velo_to_cam(big, rect, g["0_p2"] if filt else None, [w, h] if filt else None)
-        np.testing.assert_array_equal(_np(b.points[off[1]:off[1] + n[1]]).T, e)
+        _same_bytes(_np(b.points[off[1]:off[1] + n[1]]).T, e)
 
 
 def test_mv3d_one_point_frame_projects_like_numpy():
