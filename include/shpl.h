@@ -1106,6 +1106,71 @@ int shpl_head1x1_drop_wgrad(int dtype, int64_t rows, const void *d_a, int64_t a_
                             float *d_dbias, double keep_prob, uint64_t seed, void *d_ws, size_t ws_bytes,
                             void *stream);
 
+/* ---------------------------------------------------------------------------
+ * SHPL concat with BatchNorm on both halves (the intent of use_bn=True)
+ * ------------------------------------------------------------------------- */
+
+/* out[d] = [BN(pass[d]) || BN(pooled[d])] for every destination row d of csr, C = c_pass + c_pool channels,
+ * pooled[d] the f32 run sum of shpl_pull (same entry order, separate multiply and add, per-column partials for
+ * a pixel-keyed CSR with ent_col) -- never stored, and in bf16 never rounded before it is normalised. Each
+ * channel has its own BatchNorm: every per-channel array below is [C], the pass-through half's c_pass entries
+ * first. csr must carry key_range (shpl_pull_once's requirement; SHPL_ERR_ARG without).
+ *   training : per channel, in f64: s1 = sum x, s2 = sum x^2 -- over all rows for the pass-through half, over
+ *              the occupied rows only for the pooled half (its other rows are 0) -- count = csr->n_keys (all
+ *              rows of the batch) for both; mean = s1 / count, var = max(s2 / count - mean^2, 0),
+ *              scale = gamma / sqrt(var + eps), moving averages m -= (m - v)(1 - decay) with the Bessel-
+ *              corrected variance, d_batch_mean / d_batch_var optional (shpl_batch_norm's finalize).
+ *              Summation order: blocks of rows (4096, at most 1024 blocks), inside a block each of its row
+ *              lanes adds its rows in ascending order, the lanes are added in lane order, the blocks' partials
+ *              in a fixed strided order; no floating-point atomics: two runs give the same bits.
+ *   inference: mean = d_moving_mean, scale = gamma / sqrt(d_moving_var + eps) (both required, read only);
+ *              one launch, no statistics pass, no workspace.
+ *   y = (x - mean) * scale (+ beta), one rounded f32 operation at a time; an empty row's pooled half is the
+ *   per-channel constant (0 - mean) * scale + beta, one bit pattern per channel.
+ * d_gamma NULL: 1 (slim's scale=False); d_beta NULL: 0. d_save [2][C] (required in training, optional in
+ * inference) receives mean and scale, which shpl_concat_bn_backward takes. Training launches: the partial
+ * statistics, their reduction, the finalize, the apply; it reads the pass-through half and the gathered source
+ * rows twice and writes out once. 16-byte chunks under shpl_pull's alignment rule, one element otherwise.
+ * Errors: csr NULL or without key_range, c_pass or c_pool <= 0, d_out / d_src / d_pass NULL, out_stride <
+ * c_pass + c_pool, a dtype or direction outside the enums, training without a workspace (or d_save) or with
+ * ws_bytes below shpl_concat_bn_workspace_bytes, inference without moving statistics: SHPL_ERR_ARG, nothing
+ * launched; the size limits and stride rules of shpl_pull: SHPL_ERR_BAD_SHAPE.
+ * Replaces: sparse_pool_utils.py:69-70 / :84-85 with concat_bn_op :120-124, as intended -- BatchNorm on each
+ * half, then concat. The reference's own code at those lines calls slim.batch_norm(x, training=...), a keyword
+ * slim does not have, and raises TypeError; sparse_pool_layer(use_bn=True) of this library keeps doing that. */
+int shpl_concat_bn_workspace_bytes(int64_t rows, int64_t c_pass, int64_t c_pool, size_t *bytes);
+int shpl_concat_bn(int direction, int dtype, const shpl_csr *csr, const void *d_src, int64_t src_stride,
+                   int64_t src_off, int64_t c_pool, const void *d_pass, int64_t pass_stride, int64_t pass_off,
+                   int64_t c_pass, void *d_out, int64_t out_stride, int training, float eps, float decay,
+                   const float *d_gamma, const float *d_beta, float *d_moving_mean, float *d_moving_var,
+                   float *d_batch_mean, float *d_batch_var, float *d_save, void *d_ws, size_t ws_bytes,
+                   void *stream);
+
+/* The autodiff of shpl_concat_bn (no activation). d_g [rows][>= C] at g_stride; d_save the forward's mean and
+ * scale; xhat = (x - mean) * scale / gamma with x the pass-through value or the run sum (0 at an empty row).
+ * Per channel, in f64 and the forward's summation order: dbeta = sum g, dgamma = sum g * xhat; for the pooled
+ * half sum g * xhat = xhat_empty * sum g + the sum over the occupied rows of g * (xhat - xhat_empty), with
+ * xhat_empty = (0 - mean) * scale / gamma. Then
+ *   training:  g_x = scale * (g - dbeta / rows - xhat * dgamma / rows)
+ *   inference: g_x = scale * g
+ * written for the pass-through half to d_gpass [rows][c_pass] (gpass_stride, the feature dtype), and for the
+ * pooled half, at the occupied rows only, to d_gpool f32 [rows][c_pool] (contiguous rows, caller-owned scratch
+ * that is never cleared and never read elsewhere). With d_gsrc set, csr_grad -- the CSR of the same map keyed by
+ * the source's rows (the other direction, SHPL_ORDER_COL_ENTRY) -- carries d_gpool back: d_gsrc f32
+ * [csr_grad->n_keys][c_pool] (gsrc_stride) = shpl_pull(the other direction, SHPL_F32, SHPL_OUT_POOL) of
+ * d_gpool, which reads the occupied rows only. Both are f32 in either dtype: the source's gradient is summed
+ * from unrounded g_x and rounded once, by the caller that wants it in bf16.
+ * Every entry of the map must lie inside its frame in both CSRs. d_dbeta / d_dgamma [C], optional.
+ * Errors as shpl_concat_bn's; d_g, d_gpass, d_gpool or d_save NULL, d_gsrc without csr_grad: SHPL_ERR_ARG. */
+int shpl_concat_bn_backward_workspace_bytes(int64_t rows, int64_t c_pass, int64_t c_pool, size_t *bytes);
+int shpl_concat_bn_backward(int direction, int dtype, const shpl_csr *csr, const shpl_csr *csr_grad,
+                            const void *d_src, int64_t src_stride, int64_t src_off, int64_t c_pool,
+                            const void *d_pass, int64_t pass_stride, int64_t pass_off, int64_t c_pass,
+                            const void *d_g, int64_t g_stride, const float *d_save, const float *d_gamma,
+                            int training, void *d_gpass, int64_t gpass_stride, void *d_gpool, void *d_gsrc,
+                            int64_t gsrc_stride, float *d_dbeta, float *d_dgamma, void *d_ws, size_t ws_bytes,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -266,6 +266,12 @@ def _declare(lib):
         "shpl_head1x1_drop_wgrad_workspace_bytes": (i32, [i32, i64, i64, i64, i64, i64, i32, psz]),
         "shpl_head1x1_drop_wgrad": (i32, [i32, i64, p, i64, i64, i64, p, i64, i64, i64, i64, ctypes.POINTER(ShplCsr),
                                           p, i64, i64, p, p, d, u64, p, sz, p]),
+        "shpl_concat_bn_workspace_bytes": (i32, [i64, i64, i64, psz]),
+        "shpl_concat_bn": (i32, [i32, i32, ctypes.POINTER(ShplCsr), p, i64, i64, i64, p, i64, i64, i64, p, i64, i32,
+                                 ctypes.c_float, ctypes.c_float, p, p, p, p, p, p, p, p, sz, p]),
+        "shpl_concat_bn_backward_workspace_bytes": (i32, [i64, i64, i64, psz]),
+        "shpl_concat_bn_backward": (i32, [i32, i32, ctypes.POINTER(ShplCsr), ctypes.POINTER(ShplCsr), p, i64, i64, i64,
+                                          p, i64, i64, i64, p, i64, p, p, i32, p, i64, p, p, i64, p, p, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -202,6 +202,13 @@ def rpn_uses_sparse_pooling(cfg: ShplConfig) -> bool:
     return bool(cfg.rpn.rpn_use_sparse_pooling and cfg.dataset.output_indices)
 
 
+def rpn_sparse_pooling_uses_batch_norm(cfg: ShplConfig) -> bool:
+    """rpn_model.py:329-336 hands rpn_sparse_pooling_use_batch_norm to sparse_pool_layer as use_bn, where the
+    reference raises TypeError (concat_bn_op); here the switch asks for
+    sparse_pool_utils.sparse_pool_layer_bn / fusion_bn.FusionConcatBN: BatchNorm on both halves, then concat."""
+    return bool(rpn_uses_sparse_pooling(cfg) and cfg.rpn.rpn_sparse_pooling_use_batch_norm)
+
+
 def retinanet_uses_sparse_pooling(cfg: ShplConfig) -> bool:
     """RetinanetModel.__init__ (retinanet_model.py:144)."""
     return bool(cfg.retinanet.use_sparse_pooling and cfg.dataset.output_indices)

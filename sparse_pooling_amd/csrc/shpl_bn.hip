@@ -8,30 +8,7 @@
 namespace shpl {
 namespace {
 
-// BatchNorm (training) from the batch statistics: mean, biased variance for
-// the normalisation, Bessel-corrected variance for the moving average (TF
-// FusedBatchNorm), then y = act((x - mean) * gamma / sqrt(var + eps) + beta)
-// in place.
-__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_finalize(const double *stats, double count, int c, float eps,
-                                                            const float *gamma, float *mean_out, float *scale_out,
-                                                            float *moving_mean, float *moving_var, float decay,
-                                                            float *batch_mean, float *batch_var) {
-    for (int ch = threadIdx.x; ch < c; ch += SHPL_BLOCK) {
-        const double mean = stats[ch] / count;
-        double var = stats[c + ch] / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)mean, vf = (float)var;
-        const float g = gamma ? gamma[ch] : 1.0f;
-        mean_out[ch] = mf;
-        scale_out[ch] = __fmul_rn(g, __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(vf, eps))));
-        const float vu = count > 1.0 ? (float)(var * count / (count - 1.0)) : vf;
-        if (moving_mean) moving_mean[ch] = __fsub_rn(moving_mean[ch], __fmul_rn(__fsub_rn(moving_mean[ch], mf), 1.0f - decay));
-        if (moving_var) moving_var[ch] = __fsub_rn(moving_var[ch], __fmul_rn(__fsub_rn(moving_var[ch], vu), 1.0f - decay));
-        if (batch_mean) batch_mean[ch] = mf;
-        if (batch_var) batch_var[ch] = vu;
-    }
-}
-
+// k_bn_finalize (shpl_conv_bn.h), then y = act((x - mean) * gamma / sqrt(var + eps) + beta) in place.
 template <typename T>
 __global__ __launch_bounds__(SHPL_BLOCK) void k_bn_apply(const T *x, T *y, int64_t rows, int64_t stride, int c,
                                                          const float *mean, const float *scale, const float *beta,
@@ -386,13 +363,6 @@ bool bn_vector_form(int dtype, int64_t c, int64_t stride, std::initializer_list<
 int bn_apply_grid(int dtype, int64_t rows, int64_t c, bool vform) {
     const int vec = dtype == SHPL_F32 ? 4 : 8;
     return grid_for(rows * c / (vform ? vec : 1), SHPL_BLOCK * bn_rows_per_thread(16 / vec), 1 << 22);
-}
-
-int bn_bwd_blocks(int64_t rows) {
-    int64_t nb = (rows + 4095) / 4096;
-    if (nb < 1) nb = 1;
-    if (nb > 1024) nb = 1024;
-    return (int)nb;
 }
 
 }  // namespace

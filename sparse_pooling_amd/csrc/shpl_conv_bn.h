@@ -62,5 +62,37 @@ __device__ __forceinline__ double block_sum(double s, double *red) {
     return s;
 }
 
+// BatchNorm (training) from the batch statistics [sum x, sum x^2] (c each): mean, biased variance (clamped
+// at 0) for the normalisation, Bessel-corrected variance for the moving average (TF FusedBatchNorm); mean and
+// scale = gamma / sqrt(var + eps) are left for the apply kernels (shpl_bn.hip, shpl_concat_bn.hip).
+__global__ __launch_bounds__(SHPL_BLOCK) void k_bn_finalize(const double *stats, double count, int c, float eps,
+                                                            const float *gamma, float *mean_out, float *scale_out,
+                                                            float *moving_mean, float *moving_var, float decay,
+                                                            float *batch_mean, float *batch_var) {
+    for (int ch = threadIdx.x; ch < c; ch += SHPL_BLOCK) {
+        const double mean = stats[ch] / count;
+        double var = stats[c + ch] / count - mean * mean;
+        if (var < 0.0) var = 0.0;
+        const float mf = (float)mean, vf = (float)var;
+        const float g = gamma ? gamma[ch] : 1.0f;
+        mean_out[ch] = mf;
+        scale_out[ch] = __fmul_rn(g, __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(vf, eps))));
+        const float vu = count > 1.0 ? (float)(var * count / (count - 1.0)) : vf;
+        if (moving_mean) moving_mean[ch] = __fsub_rn(moving_mean[ch], __fmul_rn(__fsub_rn(moving_mean[ch], mf), 1.0f - decay));
+        if (moving_var) moving_var[ch] = __fsub_rn(moving_var[ch], __fmul_rn(__fsub_rn(moving_var[ch], vu), 1.0f - decay));
+        if (batch_mean) batch_mean[ch] = mf;
+        if (batch_var) batch_var[ch] = vu;
+    }
+}
+
+// Blocks of the per-channel partial sums over `rows` rows (the BatchNorm backward's, the fused concat's
+// statistics): 4096 rows each, at most 1024 blocks.
+inline int bn_bwd_blocks(int64_t rows) {
+    int64_t nb = (rows + 4095) / 4096;
+    if (nb < 1) nb = 1;
+    if (nb > 1024) nb = 1024;
+    return (int)nb;
+}
+
 }  // namespace
 }  // namespace shpl

@@ -88,8 +88,17 @@ class ShplMap:
     # shpl_build_csr_path's builder for the flat CSRs (L.CSR_AUTO: the library's choice by batch shape)
     CSR_PATH = L.CSR_AUTO
 
-    def csr(self, direction, order):
+    def csr(self, direction, order, key_range=False):
+        """The map's entries sorted by destination (built once, kept on the map). key_range=True: the CSR must
+        carry key ranges (the row-keyed kernels of fusion_bn): the plain one when it has them, else a second one
+        built with them and kept beside it -- the plain pulls keep the form L.row_pulls chose for them. Key ranges
+        need nnz_cap < 2^24 (the builders' entry offsets); maps past the range builder's 65536 destinations per
+        frame take the frame builder."""
         key = (direction, order)
+        if key_range:
+            c = self._csr.get(key)
+            if c is None or c.key_range is None:
+                return self._csr_rows(direction, order)
         if key in self._csr:
             c = self._csr[key]
             if key in self._pending:  # built on a side stream: the current one waits for it, and owns its buffers
@@ -103,13 +112,30 @@ class ShplMap:
         rows = self.ROW_PULLS
         if rows is None:
             rows = L.row_pulls(self.n_frames, n_keys // max(self.n_frames, 1), self.nnz_cap)
-        c = L.Csr(n_keys, self.nnz_cap, self.device, with_col=direction == L.BY_PIXEL, key_range=rows)
-        L.check(L.lib().shpl_build_csr_path(self.CSR_PATH, direction, order, self.n_frames, L.ptr(self.frame_off),
+        c = self._build_csr(direction, order, n_keys, rows, self.CSR_PATH)
+        self._csr[key] = c
+        return c
+
+    def _build_csr(self, direction, order, n_keys, key_range, path):
+        c = L.Csr(n_keys, self.nnz_cap, self.device, with_col=direction == L.BY_PIXEL, key_range=key_range)
+        L.check(L.lib().shpl_build_csr_path(path, direction, order, self.n_frames, L.ptr(self.frame_off),
                                             L.ptr(self.frame_nnz), n_keys // self.n_frames,
                                             L.ptr(self.cell), L.ptr(self.col), L.ptr(self.val),
                                             L.ptr(self.pix), c.ref(), L.ptr(c.ws), c.ws.numel(),
                                             L.stream_of(self.device)), "shpl_build_csr_path")
-        self._csr[key] = c
+        return c
+
+    def _csr_rows(self, direction, order):
+        key = (direction, order, "rows")
+        c = self._csr.get(key)
+        if c is None:
+            if self.nnz_cap >= L.ROWS_MAX_CAP:
+                raise ValueError(f"a CSR with key ranges holds fewer than {L.ROWS_MAX_CAP} entries; this map's "
+                                 f"capacity is {self.nnz_cap}")
+            n_keys = self.n_cells if direction == L.BY_CELL else self.n_pix
+            per_frame = n_keys // max(self.n_frames, 1)
+            path = self.CSR_PATH if per_frame <= L.ROWS_MAX_KEYS else L.CSR_FRAME
+            c = self._csr[key] = self._build_csr(direction, order, n_keys, True, path)
         return c
 
     def prefetch_csr(self, direction, order):

@@ -28,7 +28,7 @@ from . import shpl_map as sm
 from .errors import InvalidArgumentError
 
 __all__ = ["SparseTensor", "gen_sparse_pooling_input_avod", "produce_sparse_pooling_input",
-           "sparse_pool_layer", "_sparse_pool_op", "_sparse_pool_trans_op", "concat_bn_op",
+           "sparse_pool_layer", "sparse_pool_layer_bn", "_sparse_pool_op", "_sparse_pool_trans_op", "concat_bn_op",
            "build_sparse_pooling_input", "build_sparse_pooling_inputs"]
 
 
@@ -264,3 +264,29 @@ def sparse_pool_layer(inputs, feature_depths, M, img_index_flip=None, bv_index=N
         raise InvalidArgumentError("only batch size 1 is supported (as in the reference)")
     smap = _pack(M, img_index_flip, tuple(input_img.shape), Hb * Wb)
     return sm.layer(input_bv, input_img, smap, dual=dual)
+
+
+def sparse_pool_layer_bn(inputs, feature_depths, M, img_index_flip=None, bv_index=None, bn=None, training=True):
+    """What sparse_pool_layer(..., use_bn=True) was meant to compute (sparse_pool_utils.py:69-70, :84-85,
+    :120-124), under a name of its own -- the reference's function, and sparse_pool_layer above, raise
+    TypeError there. Same argument order as sparse_pool_layer; ``bn`` is the fusion_bn.FusionConcatBN that
+    holds the four BatchNorms' beta and moving statistics (the variables slim.batch_norm would create).
+    Returns (bv_fused, img_fused) = ([BN(bev) || BN(img_pooled)], [BN(img) || BN(bv_pooled)] when dual)."""
+    from .fusion_bn import FusionConcatBN
+    input_bv, input_img = inputs[0], inputs[1]
+    if img_index_flip is None:
+        if bv_index is not None:
+            raise ValueError("dual sparse pooling needs img_index_flip (reference :83)")
+        return input_bv, input_img
+    if not isinstance(bn, FusionConcatBN):
+        raise TypeError("sparse_pool_layer_bn needs bn=FusionConcatBN(c_bev, c_img)")
+    if int(feature_depths[0]) != input_img.shape[-1]:
+        raise InvalidArgumentError("feature_depths[0] must equal the image feature depth")
+    dual = bv_index is not None
+    if dual and int(feature_depths[1]) != input_bv.shape[-1]:
+        raise InvalidArgumentError("feature_depths[1] must equal the BEV feature depth")
+    if input_bv.shape[0] != 1:
+        raise InvalidArgumentError("only batch size 1 is supported (as in the reference)")
+    Hb, Wb = int(input_bv.shape[1]), int(input_bv.shape[2])
+    smap = _pack(M, img_index_flip, tuple(input_img.shape), Hb * Wb)
+    return bn(input_bv, input_img, smap, dual=dual, is_training=training)
